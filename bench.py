@@ -10,11 +10,18 @@ replicated in every GPU's HBM, and one batch of 10^9 random queries -- 50 % posi
 reverse-complemented), 50 % uniform random (tools/perf.hpp:38-74), seeded, drawn on the device -- sharded over
 the ranks ("scaling": "strong"). `--workload c2` selects configs[1] (S. enterica pangenome scale, 10^8 queries).
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload c3|c2|c4] [--bases B --queries Q] [--canonical]
+    python bench.py [--gpus N --steps K --warmup W] [--workload c3|c2|c4] [--bases B --queries Q] [--canonical] [--full] [--dump-outputs DIR]
     python bench.py --workload c4 --streaming [--gpus N --reads R]      the streaming query of configs[3], read-sharded
 
-The default run (C3, one GPU) appends `other_workloads`: the C2 line, the C4 (k = 63) line, the C4 streaming line and the k = 31 streaming line, each a
-child run of this script with its own oracle check, roofline and cpu_baseline.
+A plain run sets up, warms up, times the steps and prints the line: `value`, `ms_per_step` and the per-rank times. Everything else
+is behind `--full`: the oracle check of the ids (or streaming counters), the roofline, the CPU baseline, the side measurements (other
+query mixes, table-less paths, host-buffer entry points, the FASTQ query), the index statistics, the random-line probe and, on the
+default run (C3, one GPU), `other_workloads`: the C2 line, the C4 (k = 63) line, the C4 streaming line and the k = 31 streaming line,
+each a child run of this script with its own oracle check, roofline and cpu_baseline.
+
+`--dump-outputs DIR` writes what the last timed step returned, after the timed region: DIR/kmer_id.npy (float64; -1 for a miss) holds
+the ids at DUMP_SAMPLE positions of the batch drawn with a fixed seed (all of them for a smaller batch), DIR/report.npy (float64) the six
+streaming counters. The batch and the dictionary are seeded, so runs with the same arguments can be compared output for output.
 
 `--gpus N` with N > 1 starts the N ranks itself (python -m torch.distributed.run, rendezvous on 127.0.0.1);
 launched under torch.distributed.run it uses the ranks it is given. One process per GPU; no collective on the
@@ -97,6 +104,23 @@ PARITY_NOTE = {"pinned": "ids, orientation, string fields (reference-compiled pr
 def split_batch(total: int, world: int, rank: int) -> tuple[int, int]:
     """Contiguous share [lo, hi) of a batch of `total` queries for `rank` (tests/test_multiproc_gloo.py)."""
     return total * rank // world, total * (rank + 1) // world
+
+
+DUMP_SAMPLE = 1 << 22  # ids --dump-outputs writes at most: 32 MiB as float64
+
+
+def dump_positions(total: int, seed: int) -> np.ndarray:
+    """Positions in the batch whose ids --dump-outputs writes, ascending: all of them up to DUMP_SAMPLE, else a seeded sample."""
+    if total <= DUMP_SAMPLE:
+        return np.arange(total, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(total, DUMP_SAMPLE, replace=False))
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(a, dtype=np.float64))
+    log(f"outputs written to {directory}: " + ", ".join(f"{name}.npy ({np.size(a)} values)" for name, a in arrays.items()))
 
 
 def get_index(args, rank: int, world: int, barrier):
@@ -398,7 +422,7 @@ def run_other_workload(args, extra, env_extra=None):
     memory): the child's JSON line, or the reason there is none."""
     record = os.path.join(args.cache_dir, f"sshash_amd_bench_child_{os.getpid()}.json")
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup), "--cache-dir", args.cache_dir,
-           "--seed", str(args.seed), "--no-extra-mixes", "--no-other-paths", "--no-file-query", "--no-other-workloads", "--no-line-probe",
+           "--seed", str(args.seed), "--full", "--no-extra-mixes", "--no-other-paths", "--no-file-query", "--no-other-workloads", "--no-line-probe",
            "--full-record", record, "--quiet-record"] + extra
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(env_extra or {})
@@ -512,32 +536,42 @@ def streaming_mode(args, d, index_path, rank, world, local_rank, dev, use_dist, 
     assert rep["num_kmers"] == rep["num_positive_kmers"] + rep["num_negative_kmers"] + rep["num_invalid_kmers"], rep
     assert rep["num_positive_kmers"] == rep["num_searches"] + rep["num_extensions"], rep
     assert sum(r["report"][0] for r in per_rank) == rep["num_kmers"]
-    # parity: the first reads of rank 0's share through the CPU oracle's restated state machine (oracle = checker only)
-    from oracle import oracle as O
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"report": counters.cpu().numpy()})
+    m = roofline = cpu = None
+    if args.full:
+        # parity: the first reads of rank 0's share through the CPU oracle's restated state machine (oracle = checker only)
+        from oracle import oracle as O
 
-    ora = O.OracleIndex(index_path)
-    m = min(n, args.stream_oracle_reads)
-    sample = [bytes(r) for r in reads[:m].cpu().numpy()]
-    t0 = time.perf_counter()
-    want = ora.streaming_query(sample)
-    t_oracle = time.perf_counter() - t0
-    part = torch.zeros(6, dtype=torch.int64, device=dev)
-    d.streaming_query_device(local_rank, reads.data_ptr(), offsets.data_ptr(), m, part.data_ptr(), stream=stream.cuda_stream, total_bases=m * L)
-    torch.cuda.synchronize()
-    got = dict(zip(names, (int(v) for v in part.cpu().tolist())))
-    if got != {f: int(v) for f, v in want.items()}:
-        raise SystemExit(f"PARITY FAILURE: streaming counters of the first {m} reads: GPU {got} vs oracle {want}")
-    # algorithmic bytes (SURVEY 8(d) rule, applied to the streaming query k-mer by k-mer): 1 B per base of the reads + 8 B per distinct
-    # 64-bit index word the REFERENCE's state machine dereferences for a k-mer -- the lookups of a seed() that its unchanged-minimizer
-    # test does not cut short, the strings' next k-mer of an extension --, counted by the instrumented oracle on the sample it has just
-    # checked (the first `m` reads of rank 0's share) and scaled by k-mers. (Until round 5 every negative was priced as a full lookup,
-    # which the reference does not do either: a line that skips what the reference skips then sat above the roofline.)
-    W = d.words_per_kmer()
-    bytes_per_kmer = ora.streaming_count_bytes(sample) / max(1, want["num_kmers"])
-    algorithmic = bytes_per_kmer * rep["num_kmers"]
-    bytes_per_lookup = None
-    n_local_kmers = per_rank[0]["report"][0]
-    achieved = algorithmic * (n_local_kmers / rep["num_kmers"]) / (avg_kernel_ms * 1e-3) / 1e9
+        ora = O.OracleIndex(index_path)
+        m = min(n, args.stream_oracle_reads)
+        sample = [bytes(r) for r in reads[:m].cpu().numpy()]
+        t0 = time.perf_counter()
+        want = ora.streaming_query(sample)
+        t_oracle = time.perf_counter() - t0
+        part = torch.zeros(6, dtype=torch.int64, device=dev)
+        d.streaming_query_device(local_rank, reads.data_ptr(), offsets.data_ptr(), m, part.data_ptr(), stream=stream.cuda_stream, total_bases=m * L)
+        torch.cuda.synchronize()
+        got = dict(zip(names, (int(v) for v in part.cpu().tolist())))
+        if got != {f: int(v) for f, v in want.items()}:
+            raise SystemExit(f"PARITY FAILURE: streaming counters of the first {m} reads: GPU {got} vs oracle {want}")
+        # algorithmic bytes (SURVEY 8(d) rule, applied to the streaming query k-mer by k-mer): 1 B per base of the reads + 8 B per distinct
+        # 64-bit index word the REFERENCE's state machine dereferences for a k-mer -- the lookups of a seed() that its unchanged-minimizer
+        # test does not cut short, the strings' next k-mer of an extension --, counted by the instrumented oracle on the sample it has just
+        # checked (the first `m` reads of rank 0's share) and scaled by k-mers. (Until round 5 every negative was priced as a full lookup,
+        # which the reference does not do either: a line that skips what the reference skips then sat above the roofline.)
+        W = d.words_per_kmer()
+        bytes_per_kmer = ora.streaming_count_bytes(sample) / max(1, want["num_kmers"])
+        algorithmic = bytes_per_kmer * rep["num_kmers"]
+        bytes_per_lookup = None
+        n_local_kmers = per_rank[0]["report"][0]
+        achieved = algorithmic * (n_local_kmers / rep["num_kmers"]) / (avg_kernel_ms * 1e-3) / 1e9
+        roofline = streaming_roofline(d, args, n, W, achieved, avg_kernel_ms, kernel_ms, algorithmic, rep, n_local_kmers, bytes_per_lookup)
+        cpu = {"value": round(want["num_kmers"] / t_oracle, 1), "unit": "k-mers/s", "cores": 1, "kind": "port",
+               "sample": f"the first {m} reads of the same set through the oracle's streaming state machine on one thread (the reference's query "
+                         f"tool is single-threaded): {t_oracle / max(1, want['num_kmers']) * 1e9:.1f} ns per k-mer",
+               "published_reference_ns_per_kmer": "89.5 (k=31) / 190.6 (k=63): human, high-hit, gzipped FASTQ, one 5.4 GHz core; "
+                                                  "benchmarks/results-21-01-26/k{31,63}/regular-streaming-queries-high-hit.json:3"}
     total_kmers = rep["num_kmers"] * args.steps
     return {
         "metric": "streaming_query k-mers/sec (synthetic reads resident in HBM, six counters; BASELINE.json configs[3])",
@@ -557,12 +591,8 @@ def streaming_mode(args, d, index_path, rank, world, local_rank, dev, use_dist, 
                    "counters_equal_oracle_on_reads": m, "parity": PARITY_NOTE, "num_bases": d.num_bases(), "device_stats": stats},
         "per_rank": per_rank,
         "traffic_key": traffic_key(args),
-        "roofline": streaming_roofline(d, args, n, W, achieved, avg_kernel_ms, kernel_ms, algorithmic, rep, n_local_kmers, bytes_per_lookup),
-        "cpu_baseline": {"value": round(want["num_kmers"] / t_oracle, 1), "unit": "k-mers/s", "cores": 1, "kind": "port",
-                         "sample": f"the first {m} reads of the same set through the oracle's streaming state machine on one thread (the reference's query "
-                                   f"tool is single-threaded): {t_oracle / max(1, want['num_kmers']) * 1e9:.1f} ns per k-mer",
-                         "published_reference_ns_per_kmer": "89.5 (k=31) / 190.6 (k=63): human, high-hit, gzipped FASTQ, one 5.4 GHz core; "
-                                                            "benchmarks/results-21-01-26/k{31,63}/regular-streaming-queries-high-hit.json:3"},
+        "roofline": roofline,
+        "cpu_baseline": cpu,
     }
 
 
@@ -607,6 +637,12 @@ def main():
                     help="where rank 0 writes the FULL record (children, histograms, per-step times, the rules in prose); stdout carries the compact line")
     ap.add_argument("--quiet-record", action="store_true", help="do not echo the full record on stderr")
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and side measurements (oracle parity, roofline, cpu_baseline, other mixes / paths / workloads, "
+                         "FASTQ query, index statistics, random-line probe); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help=f"after the timed steps, write what the last step returned as DIR/<name>.npy (float64; ids: a seeded sample of at "
+                         f"most {DUMP_SAMPLE})")
     args = ap.parse_args()
     bases, recipe, queries, what = WORKLOADS[args.workload]
     if args.bases is None:
@@ -752,7 +788,7 @@ def main():
         elapsed = float(t.item())
         # every rank's own GPU under the random-line probe (the boxes -- and the GPUs of one node -- differ by several per cent): after
         # the timed region, all ranks at once, each on its own device
-        probe = {} if (args.no_line_probe or world == 1) else random_line_probe(device=local_rank)
+        probe = {} if (not args.full or args.no_line_probe or world == 1) else random_line_probe(device=local_rank)
         mine = torch.tensor([float(n), own_elapsed / args.steps * 1e3, avg_kernel_ms, upload_window[0], upload_window[1],
                              float(probe.get("probe_units_per_s", 0.0))], dtype=torch.float64, device=coll_dev)
         every = [torch.zeros_like(mine) for _ in range(world)]
@@ -762,50 +798,62 @@ def main():
                      "kernel_ms_per_step": round(float(v[2].item()), 3), "upload_s": round(float((v[4] - v[3]).item()), 2),
                      "upload_window_s": [round(float(v[3].item()) - first, 2), round(float(v[4].item()) - first, 2)],
                      "random_line_probe_units_per_s": float(v[5].item()) or None} for r, v in enumerate(every)]
+    if args.dump_outputs:
+        pos = dump_positions(args.queries, args.seed)
+        local_pos = pos[(pos >= lo) & (pos < hi)] - lo
+        ids = out[torch.from_numpy(local_pos).to(dev)].cpu().numpy()
+        if use_dist:
+            every = [None] * world
+            dist.all_gather_object(every, ids)  # (shares are contiguous and in rank order: so are the positions)
+            ids = np.concatenate(every)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"kmer_id": ids})
 
     # ---- parity spot check + algorithmic bytes (oracle = checker only) ---------------------------
     result = None
     if rank == 0:
-        from oracle import oracle as O
+        sample = found = roofline = None
+        if args.full:
+            from oracle import oracle as O
 
-        ora = O.OracleIndex(index_path)
-        sample = min(200_000, n)
-        head = dq[: max(sample, min(n, args.cpu_sample * 64)) * W].cpu().numpy().view(np.uint64)
-        got = out[:sample].cpu().numpy().view(np.uint64)
-        want = ora.lookup_ids(head[: sample * W], num_threads=effective_cores())
-        if not (got == want).all():
-            bad = np.nonzero(got != want)[0]
-            raise SystemExit(f"PARITY FAILURE: GPU ids differ from the CPU oracle for {bad.size} of {sample} sampled queries; first: "
-                             + ", ".join(f"#{int(i)} kmer={int(head[i * W]):#x} got={int(got[i])} want={int(want[i])}" for i in bad[:6]))
-        found = float((out != -1).float().mean().item())
-        bytes_per_lookup = ora.count_bytes(head[: min(sample, 100_000) * W]) / min(sample, 100_000)
-        achieved = bytes_per_lookup * n / (avg_kernel_ms * 1e-3) / 1e9
-        pieces = -(-n // (1 << 27))  # launch sequences per step (engine.hip: at most 2^27 queries per sequence, equal pieces)
-        traffic, provenance = traffic_record(d, n, args)
-        roofline = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_provenance": provenance,
-                    "kernel": "fast_lookup_kernel<W=%d,canonical=%d,ids,%s> (%s) + deferred_lookup_kernel (%d launch "
-                              "sequence(s) of equal size per step; avg_kernel_ms = HIP-event time around one step, on the launch stream)"
-                              % (W, int(d.canonical()), "super-k-mer table" if stats["sk_slots"] else "directory / MPHF",
-                                 ("every probe finished inside the first pass" if W == 1 else "+ resume_lookup_kernel") if stats["sk_slots"]
-                                 else "+ scan_lookup_kernel", pieces),
-                    "launches_per_step": pieces,
-                    "algorithmic_bytes_per_lookup": round(bytes_per_lookup, 2),
-                    "algorithmic_bytes_rule": "SURVEY 8(d): 8 B per distinct 64-bit index word the REFERENCE algorithm dereferences "
-                                              "+ query in + id out, counted by the instrumented oracle on this batch",
-                    "avg_kernel_ms": round(avg_kernel_ms, 3), "kernel_ms_steps": kernel_ms_steps,
-                    # what bounds a structure of one random bucket per query on this chip is random UNITS, not bytes: 43.8 G
-                    # random 64-byte units/s, 39.9 G 128-byte ones (tools/tlb_probe; HISTORY.md)
-                    "random_unit_bound": {"probe_units_per_s": RANDOM_UNIT_PROBE, "source": "profiles/r02/tlb_probe_128_256_byte_units.jsonl",
-                                          "lookups_per_s_this_gpu": round(n / (avg_kernel_ms * 1e-3), 1), "units_per_s_this_gpu": round(n / (avg_kernel_ms * 1e-3), 1),
-                                          "frac": round(n / (avg_kernel_ms * 1e-3) / RANDOM_UNIT_PROBE, 4)}}
-        if traffic:
-            # the kernels' own bytes: what the PMC passes of this very workload saw moving between L2 and HBM per step
-            # (64 B per bucket line -- both slots of a line are compared --, the query and id streams, the pass queues)
-            roofline["frac_hbm_traffic"] = round(traffic / (avg_kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
-            roofline["hbm_traffic_bytes_per_lookup"] = round(traffic / n, 2)
+            ora = O.OracleIndex(index_path)
+            sample = min(200_000, n)
+            head = dq[: max(sample, min(n, args.cpu_sample * 64)) * W].cpu().numpy().view(np.uint64)
+            got = out[:sample].cpu().numpy().view(np.uint64)
+            want = ora.lookup_ids(head[: sample * W], num_threads=effective_cores())
+            if not (got == want).all():
+                bad = np.nonzero(got != want)[0]
+                raise SystemExit(f"PARITY FAILURE: GPU ids differ from the CPU oracle for {bad.size} of {sample} sampled queries; first: "
+                                 + ", ".join(f"#{int(i)} kmer={int(head[i * W]):#x} got={int(got[i])} want={int(want[i])}" for i in bad[:6]))
+            found = float((out != -1).float().mean().item())
+            bytes_per_lookup = ora.count_bytes(head[: min(sample, 100_000) * W]) / min(sample, 100_000)
+            achieved = bytes_per_lookup * n / (avg_kernel_ms * 1e-3) / 1e9
+            pieces = -(-n // (1 << 27))  # launch sequences per step (engine.hip: at most 2^27 queries per sequence, equal pieces)
+            traffic, provenance = traffic_record(d, n, args)
+            roofline = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_provenance": provenance,
+                        "kernel": "fast_lookup_kernel<W=%d,canonical=%d,ids,%s> (%s) + deferred_lookup_kernel (%d launch "
+                                  "sequence(s) of equal size per step; avg_kernel_ms = HIP-event time around one step, on the launch stream)"
+                                  % (W, int(d.canonical()), "super-k-mer table" if stats["sk_slots"] else "directory / MPHF",
+                                     ("every probe finished inside the first pass" if W == 1 else "+ resume_lookup_kernel") if stats["sk_slots"]
+                                     else "+ scan_lookup_kernel", pieces),
+                        "launches_per_step": pieces,
+                        "algorithmic_bytes_per_lookup": round(bytes_per_lookup, 2),
+                        "algorithmic_bytes_rule": "SURVEY 8(d): 8 B per distinct 64-bit index word the REFERENCE algorithm dereferences "
+                                                  "+ query in + id out, counted by the instrumented oracle on this batch",
+                        "avg_kernel_ms": round(avg_kernel_ms, 3), "kernel_ms_steps": kernel_ms_steps,
+                        # what bounds a structure of one random bucket per query on this chip is random UNITS, not bytes: 43.8 G
+                        # random 64-byte units/s, 39.9 G 128-byte ones (tools/tlb_probe; HISTORY.md)
+                        "random_unit_bound": {"probe_units_per_s": RANDOM_UNIT_PROBE, "source": "profiles/r02/tlb_probe_128_256_byte_units.jsonl",
+                                              "lookups_per_s_this_gpu": round(n / (avg_kernel_ms * 1e-3), 1), "units_per_s_this_gpu": round(n / (avg_kernel_ms * 1e-3), 1),
+                                              "frac": round(n / (avg_kernel_ms * 1e-3) / RANDOM_UNIT_PROBE, 4)}}
+            if traffic:
+                # the kernels' own bytes: what the PMC passes of this very workload saw moving between L2 and HBM per step
+                # (64 B per bucket line -- both slots of a line are compared --, the query and id streams, the pass queues)
+                roofline["frac_hbm_traffic"] = round(traffic / (avg_kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+                roofline["hbm_traffic_bytes_per_lookup"] = round(traffic / n, 2)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cores = effective_cores()
             m = min(args.cpu_sample, n)
             t0 = time.perf_counter()
@@ -824,7 +872,7 @@ def main():
                    "single_thread_value": round(m / t1, 1),
                    "published_reference_ns_per_lookup": "738-768 ns (real S. enterica index, one 5.4 GHz core; BASELINE.md)"}
         extra = None
-        if world == 1 and not args.no_extra_mixes:
+        if args.full and world == 1 and not args.no_extra_mixes:
             # side measurements OUTSIDE the timed region: other query mixes on 10^8-query batches, ids of a sample checked
             extra = {}
             m = min(n, 100_000_000)
@@ -849,10 +897,10 @@ def main():
                                "fraction_found": round(float((o2 != -1).float().mean().item()), 4)}
                 del q2
         other_paths = None
-        if world == 1 and sharded is None and not args.no_other_paths and stats["sk_slots"]:
+        if args.full and world == 1 and sharded is None and not args.no_other_paths and stats["sk_slots"]:
             other_paths = measure_other_paths(args, index_path, local_rank, d, dq, W, bytes_per_lookup)
         from_file = None
-        if world == 1 and sharded is None and not args.no_file_query:
+        if args.full and world == 1 and sharded is None and not args.no_file_query:
             from sshash_amd.synthetic import make_reads_device
 
             reads = make_reads_device(d, local_rank, args.file_reads, 150, positive_fraction=0.9, seed=args.seed + 5).cpu()
@@ -863,7 +911,7 @@ def main():
         index_statistics = table_histogram = None
         from sshash_amd.repeats import load_recipe
 
-        if int(load_recipe(args.recipe)["k"]) == d.k():
+        if args.full and int(load_recipe(args.recipe)["k"]) == d.k():
             from sshash_amd.repeats import statistics_vs_target
 
             index_statistics = statistics_vs_target(d.bucket_stats(), args.recipe)
@@ -901,7 +949,7 @@ def main():
                        # what carries the exchange of a routed lookup: torch.distributed's all_to_all_single over the group's backend -- nccl
                        # (= RCCL over xGMI) whenever every rank has a GPU of its own; gloo only under the tests' one-device scaffolding
                        "exchange": (f"all_to_all_single over {backend}" + (" (TEST scaffolding: every rank on one device)" if one_device is not None else "")) if sharded is not None else None,
-                       "positive_fraction_found": round(found, 4), "device_index_bytes": d.device_bytes(local_rank),
+                       "positive_fraction_found": None if found is None else round(found, 4), "device_index_bytes": d.device_bytes(local_rank),
                        "device_bytes_per_kmer": round(d.device_bytes(local_rank) / d.num_kmers(), 2),
                        "device_stats": stats, "recipe": args.recipe, "repeat_scale": args.repeat_scale,
                        "index_statistics": index_statistics, "table_histogram": table_histogram},
@@ -909,7 +957,7 @@ def main():
             "per_rank": per_rank,
             "roofline": roofline,
             "cpu_baseline": cpu,
-            "cpu_baseline_note": None if cpu is not None or args.no_cpu_baseline else "the CPU path is timed by the N = 1 run only (rank 0, this box's host cores): see that run's line",
+            "cpu_baseline_note": None if cpu is not None or args.no_cpu_baseline or not args.full else "the CPU path is timed by the N = 1 run only (rank 0, this box's host cores): see that run's line",
             "other_mixes": extra,
             "other_paths": other_paths,
             "streaming_from_file": from_file,
@@ -918,7 +966,7 @@ def main():
         other_workloads = None  # (last: this process gives its GPU memory back first)
         # test scaffolding (tests/test_gpu_bench_harness.py): "bases,queries,reads" shrinks the children and lets a reduced parent have them
         reduced = os.environ.get("SSHASH_BENCH_TEST_OTHER_WORKLOADS")
-        if world == 1 and sharded is None and args.workload == "c3" and not args.no_other_workloads and (args.bases == WORKLOADS["c3"][0] or reduced):
+        if args.full and world == 1 and sharded is None and args.workload == "c3" and not args.no_other_workloads and (args.bases == WORKLOADS["c3"][0] or reduced):
             # BASELINE.json's other single-GPU configurations, each a run of this script of its own (index, replica, batch, oracle check,
             # roofline, cpu_baseline): C2 (configs[1]) and C4 (configs[3]: the k = 63 dictionary -- point lookups and its streaming query)
             d.close()
@@ -937,7 +985,7 @@ def main():
                 other_workloads[name] = run_other_workload(args, extra, env_extra)
                 log(f"other workload {name}: {other_workloads[name].get('value')} {other_workloads[name].get('unit')}")
         result["other_workloads"] = other_workloads
-        if world == 1 and sharded is None and not args.no_line_probe and isinstance(result.get("roofline"), dict) and "random_unit_bound" in result["roofline"]:
+        if args.full and world == 1 and sharded is None and not args.no_line_probe and isinstance(result.get("roofline"), dict) and "random_unit_bound" in result["roofline"]:
             log("random-line probe of this box ...")
             probe = random_line_probe()
             for line in [result] + [w for w in (other_workloads or {}).values() if isinstance(w, dict)]:

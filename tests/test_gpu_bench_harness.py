@@ -16,7 +16,7 @@ from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
-SMALL = ["--workload", "c2", "--bases", "30000000", "--queries", "4000000", "--steps", "3", "--warmup", "1", "--cpu-sample", "100000", "--file-reads", "200000"]
+SMALL = ["--workload", "c2", "--bases", "30000000", "--queries", "4000000", "--steps", "3", "--warmup", "1", "--cpu-sample", "100000", "--file-reads", "200000", "--full"]
 CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
             "data", "config", "roofline", "cpu_baseline")
 
@@ -26,7 +26,8 @@ LINE_LIMIT = 8192
 
 def run(args, env_extra, tmp_path, timeout=1200):
     """bench.py with `args`: (the stdout line, the full record). The line is the ONE line of stdout, below the limit, carries the
-    contract, and every number it repeats equals the full record's; stderr's tail names the headline."""
+    contract, and every number it repeats equals the full record's; stderr's tail names the headline. Without --full the line has
+    no roofline and no cpu_baseline."""
     env = dict(os.environ, SSHASH_BENCH_CACHE=str(tmp_path), **env_extra)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
@@ -43,7 +44,9 @@ def run(args, env_extra, tmp_path, timeout=1200):
         assert key in line, key
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data"):
         assert line[key] == full[key], key
-    for key in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
+    if "--full" not in args:
+        assert line["roofline"] is None and line["cpu_baseline"] is None
+    for key in ("bound", "achieved", "peak", "unit", "frac", "traffic") if "--full" in args else ():
         assert key in line["roofline"] and line["roofline"][key] == full["roofline"][key], key
     assert (line["cpu_baseline"] is None) == (full["cpu_baseline"] is None)
     if line["cpu_baseline"] is not None:
@@ -53,7 +56,7 @@ def run(args, env_extra, tmp_path, timeout=1200):
     assert "workload" in line["config"] and "model" not in line["config"]
     for heavy in ("index_statistics", "table_histogram", "device_stats"):
         assert heavy not in line["config"], heavy
-    assert "kernel_ms_steps" not in line["roofline"]
+    assert line["roofline"] is None or "kernel_ms_steps" not in line["roofline"]
     tail = p.stderr[-600:]
     assert "[bench] headline" in tail and f"{full['ms_per_step']} ms/step" in tail, tail  # whatever tail a log keeps carries the number
     return line, full
@@ -131,7 +134,7 @@ def test_eight_ranks_rehearsal(mode, tmp_path):
     divide by eight), the MAX over the ranks, the gather of the per-rank numbers, and for the routed modes the group size of the
     all-to-all. What it cannot show is RCCL itself: with a GPU per rank the same code takes `nccl` (asserted on the line's `exchange`)."""
     env = {"SSHASH_BENCH_TEST_ALL_RANKS_ON_DEVICE": "0"}
-    small = ["--workload", "c2", "--bases", "12000000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-line-probe", "--gpus", "8"]
+    small = ["--workload", "c2", "--bases", "12000000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-line-probe", "--gpus", "8", "--full"]
     if mode == "streaming":
         line, r = run(small + ["--streaming", "--reads", "400001", "--stream-oracle-reads", "2000"], env, tmp_path)
         assert r["n_gpus"] == 8 and len(r["per_rank"]) == 8 and [p["rank"] for p in r["per_rank"]] == list(range(8))
@@ -160,7 +163,7 @@ def test_eight_ranks_rehearsal(mode, tmp_path):
 def test_config_c4_line(tmp_path):
     """`bench.py --workload c4` (human k = 63, m = 25 stand-in) at reduced size: the two-word path behind the same line -- statistics
     against the published k = 63 build, the table-less paths, and the FASTQ query with its counters equal to the oracle's."""
-    args = ["--workload", "c4", "--bases", "30000000", "--queries", "2000000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--file-reads", "100000"]
+    args = ["--workload", "c4", "--bases", "30000000", "--queries", "2000000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--file-reads", "100000", "--full"]
     _, r = run(args, {}, tmp_path)
     assert r["config"]["k"] == 63 and r["config"]["m"] == 25 and r["dtype"] == "u64" and r["config"]["recipe"] == "human_k63"
     assert r["config"]["index_statistics"]["source"].startswith("benchmarks/results-10-11-25/k63/regular-build.log")
@@ -175,7 +178,7 @@ def test_config_c4_line(tmp_path):
 def test_streaming_mode_one_rank_and_two(tmp_path):
     """`bench.py --workload c4 --streaming [--gpus 2]` (BASELINE.json configs[3]) at reduced size: reads drawn on every rank's device,
     read-sharded, the six counters summed with one all_reduce; the line carries the contract, per-rank reports and the oracle check."""
-    base = ["--workload", "c4", "--bases", "30000000", "--streaming", "--reads", "400001", "--steps", "2", "--warmup", "1", "--stream-oracle-reads", "5000"]
+    base = ["--workload", "c4", "--bases", "30000000", "--streaming", "--reads", "400001", "--steps", "2", "--warmup", "1", "--stream-oracle-reads", "5000", "--full"]
     for n, extra, env_extra in ((1, [], {}), (2, ["--gpus", "2"], {"SSHASH_BENCH_TEST_ALL_RANKS_ON_DEVICE": "0"})):
         line, r = run(base + extra, env_extra, tmp_path)
         assert line["config"]["report"] == r["config"]["report"] and line["roofline"]["traffic"] == r["roofline"]["traffic"]
@@ -193,7 +196,7 @@ def test_streaming_mode_one_rank_and_two(tmp_path):
 def test_default_run_appends_the_other_baseline_configurations(tmp_path):
     """The driver's command measures C3 and, behind it, BASELINE.json's other single-GPU configurations as child runs of the same script
     (`other_workloads`: C2, C4, C4's streaming query, the k = 31 streaming query on high-hit reads), each with its own oracle check, roofline and cpu_baseline -- here at reduced size."""
-    args = ["--bases", "24000000", "--queries", "2000000", "--steps", "2", "--warmup", "1", "--cpu-sample", "100000", "--no-extra-mixes", "--no-other-paths", "--no-file-query"]
+    args = ["--bases", "24000000", "--queries", "2000000", "--steps", "2", "--warmup", "1", "--cpu-sample", "100000", "--no-extra-mixes", "--no-other-paths", "--no-file-query", "--full"]
     stdout_line, r = run(args, {"SSHASH_BENCH_TEST_OTHER_WORKLOADS": "24000000,2000000,200000"}, tmp_path, timeout=2400)
     others = r["other_workloads"]
     assert set(others) == {"c2", "c4", "c4_streaming", "c3_streaming_high_hit"} == set(stdout_line["other_workloads"])
@@ -215,3 +218,46 @@ def test_default_run_appends_the_other_baseline_configurations(tmp_path):
         box = line["roofline"]["random_unit_bound"]["this_box"]
         assert "error" not in box, box
         assert 2e10 < box["probe_units_per_s"] < 8e10 and box["frac"] > 0
+
+
+def test_plain_run_times_the_steps_only_and_dumps_its_outputs(tmp_path):
+    """`bench.py` without --full: the contract's numbers and no check or side measurement. --dump-outputs writes the ids of the last
+    timed step at the seeded sample positions (the batch is larger than the sample): equal in a run of another step count, equal to
+    the CPU oracle's ids of the same queries, gathered from both ranks at N = 2; and the six counters of a streaming step."""
+    import numpy as np
+
+    import bench
+    import sshash_amd
+    from oracle import oracle as O
+    from sshash_amd.synthetic import draw_queries_device
+
+    queries = bench.DUMP_SAMPLE + 1_000_000
+    small = ["--workload", "c2", "--bases", "30000000", "--queries", str(queries), "--warmup", "1"]
+    line, r = run(small + ["--steps", "3", "--dump-outputs", str(tmp_path / "a")], {}, tmp_path)
+    assert r["steps"] == 3 and abs(r["value"] - queries / r["ms_per_step"] * 1e3) / r["value"] < 0.02
+    for key in ("roofline", "cpu_baseline", "other_mixes", "other_paths", "streaming_from_file", "other_workloads"):
+        assert r[key] is None, key
+    assert r["config"]["index_statistics"] is None and r["config"]["ids_equal_oracle_on_queries"] is None
+    a = np.load(tmp_path / "a" / "kmer_id.npy")
+    assert a.dtype == np.float64 and a.shape == (bench.DUMP_SAMPLE,) and os.listdir(tmp_path / "a") == ["kmer_id.npy"]
+    run(small + ["--steps", "2", "--dump-outputs", str(tmp_path / "b")], {}, tmp_path)
+    assert np.array_equal(a, np.load(tmp_path / "b" / "kmer_id.npy"))
+
+    (index,) = [f for f in os.listdir(tmp_path) if f.endswith(".sshash")]
+    d = sshash_amd.Dictionary.load(str(tmp_path / index))
+    d.to_device(0)
+    dq = draw_queries_device(d, 0, queries, 0.5, seed=0x5555AAAA, negatives="random")
+    pos = bench.dump_positions(queries, 0x5555AAAA)
+    want = O.OracleIndex(str(tmp_path / index)).lookup_ids(dq.cpu().numpy().view(np.uint64)[pos])
+    assert np.array_equal(a, want.view(np.int64).astype(np.float64))
+    assert 0.45 < float((a >= 0).mean()) < 0.55
+    d.close()
+
+    run(small + ["--steps", "2", "--gpus", "2", "--dump-outputs", str(tmp_path / "c")], {"SSHASH_BENCH_TEST_ALL_RANKS_ON_DEVICE": "0"}, tmp_path)
+    c = np.load(tmp_path / "c" / "kmer_id.npy")
+    assert c.shape == (bench.DUMP_SAMPLE,) and 0.45 < float((c >= 0).mean()) < 0.55
+
+    streaming = ["--workload", "c2", "--bases", "30000000", "--streaming", "--reads", "200000", "--steps", "2", "--warmup", "1"]
+    _, s = run(streaming + ["--dump-outputs", str(tmp_path / "s")], {}, tmp_path)
+    assert s["roofline"] is None and s["config"]["counters_equal_oracle_on_reads"] is None
+    assert np.load(tmp_path / "s" / "report.npy").tolist() == [float(v) for v in s["config"]["report"].values()]

@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/../.."
 out=gpurun_out/${1:-r06_density_sweep}; mkdir -p $out
 export TMPDIR=/tmp SSHASH_BENCH_CACHE=/tmp
-S="--steps 6 --warmup 2 --no-cpu-baseline --no-extra-mixes --no-file-query --no-other-paths --no-other-workloads --no-line-probe --quiet-record"
+S="--full --steps 6 --warmup 2 --no-cpu-baseline --no-extra-mixes --no-file-query --no-other-paths --no-other-workloads --no-line-probe --quiet-record"
 for w in ${2:-c3}; do
 for point in "2.5 1.75" "2.0 1.5" "1.6 1.35" "1.4 1.25" "1.25 1.2"; do set -- $point
   [ $w = c4 ] && [ $1 = 2.5 ] && set -- 3.0 2.5     # (k <= 63: the default there)

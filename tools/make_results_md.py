@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""RESULTS.md's table from the full record of the driver's command (bench.py --full-record, default bench_full.json):
+"""RESULTS.md's table from the full record of the driver's command run with --full (bench.py --full --full-record, default bench_full.json):
 
     python tools/make_results_md.py profiles/r06/bench_driver_command_full.json [driver's BENCH_rNN.json]
 
