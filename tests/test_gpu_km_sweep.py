@@ -46,6 +46,20 @@ def test_point(k, m, canonical, tmp_path):
     # forward only: the reverse complements are misses unless the k-mer is in the input on that strand too
     fwd = d.lookup(queries, check_reverse_complement=False).kmer_id
     assert (fwd == case.oracle.lookup_packed(queries, False)["kmer_id"]).all()
+    # the same queries as ASCII: the packer builds one 32-bit word per 16 characters, and k = 33 leaves one character in the third
+    # word, k = 47 fifteen. Through the host entry point, and from a device buffer one byte past an aligned address (the tile's
+    # byte-wise staging); ids and every field equal the packed answers
+    import torch
+
+    from gpu_layer_worker import ALL_FIELDS, assert_fields, device_lookup, mixed_case, packed_to_ascii
+
+    text = mixed_case(packed_to_ascii(queries, k), k)
+    assert_fields(d.lookup(text, full=True), got, ALL_FIELDS, "ascii host")
+    assert (d.lookup(text).kmer_id == ids).all()
+    staged = torch.zeros(text.size + 1, dtype=torch.uint8, device="cuda:0")
+    staged[1:] = torch.from_numpy(text.reshape(-1)).to("cuda:0")
+    assert_fields(device_lookup(d, staged.data_ptr() + 1, 3 * n, ("kmer_id",), ascii_input=True), got, ("kmer_id",), "ascii device ids")
+    assert_fields(device_lookup(d, staged.data_ptr() + 1, 3 * n, ALL_FIELDS, ascii_input=True), got, ALL_FIELDS, "ascii device full")
     # the streaming query over reads cut out of the strings (substitutions, N's, both strands, ends of strings) and random
     # ones: the six counters and every per-k-mer result against the oracle's restated state machine
     from test_gpu_streaming import _as_dict, _synthetic_reads

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import sshash_amd
-from conftest import ROOT, SE_FASTA
+from conftest import ROOT, SE_FASTA, Case, skewed_sequences
 
 
 @pytest.mark.parametrize("case_name,S", [("case_skew_regular", 2), ("case_skew_canonical", 3)])
@@ -44,6 +44,76 @@ def test_shards_partition_the_dictionary(case_name, S, request, tmp_path):
     assert (found.sum(axis=0) >= (full != np.uint64(0xFFFFFFFFFFFFFFFF))).all()
     combined = np.where(found.any(axis=0), per_shard.min(axis=0), np.uint64(0xFFFFFFFFFFFFFFFF))
     assert (combined == full).all()
+
+
+SHARD_POINTS = [(31, 11, True, 3), (63, 17, False, 2), (63, 17, True, 2)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k,m,canonical,S", SHARD_POINTS, ids=[f"k{k}_{'canonical' if c else 'regular'}_S{S}" for k, m, c, S in SHARD_POINTS])
+def test_minimizer_shards_on_the_gpu(k, m, canonical, S, tmp_path):
+    """Every shard of a minimizer-sharded index is a replica without the super-k-mer table (it answers through the minimizer directory and
+    the MPHF): each one against its own oracle in every field, membership and the six streaming counters; together, the partition rule of
+    test_shards_partition_the_dictionary on the GPU's answers; route_device names the shard that answers each query."""
+    import torch
+
+    from oracle import oracle as O
+    from test_gpu_streaming import _as_dict, _synthetic_reads
+
+    case = Case(f"shards_k{k}_{int(canonical)}", skewed_sequences(k, m, seed=40 + k, canonical=canonical), k, m, canonical, str(tmp_path))
+    W, n = case.W, case.gt.num_kmers
+    every = case.gt.kmers(np.arange(n)).reshape(n, W)
+    rc = case.gt._revcomp(every.reshape(-1)).reshape(n, W)
+    mixed = every.copy()
+    mixed[::2] = rc[::2]
+    Q = np.concatenate([np.ascontiguousarray(mixed).reshape(-1), case.queries(n, n, seed=k)])
+    reads = _synthetic_reads(case, 300, seed=k, read_len=3 * k) + ["A" * 200, "ACGT" * 40]
+    whole = case.oracle.lookup_ids(Q)
+    shards, answers = [], []
+    for r in range(S):
+        d = sshash_amd.Dictionary.build(case.fasta, k=k, m=m, canonical=canonical, num_threads=2, num_shards=S, shard_id=r)
+        p = str(tmp_path / f"shard{r}.sshash")
+        d.save(p)
+        ora = O.OracleIndex(p)
+        d.to_device(0)
+        assert d.device_stats()["sk_absent_reason"] == "minimizer shard", d.device_stats()
+        got, want = d.lookup(Q, full=True), ora.lookup_packed(Q)
+        for f in ("kmer_id", "kmer_id_in_string", "kmer_offset", "string_id", "string_begin", "string_end", "minimizer_found"):
+            assert (getattr(got, f) == want[f]).all(), (r, f)
+        assert (got.kmer_orientation.astype(np.int64) == want["kmer_orientation"]).all(), r
+        assert (d.lookup(Q).kmer_id == want["kmer_id"]).all(), r
+        assert (d.is_member(Q) == (want["kmer_id"] != sshash_amd.INVALID_U64)).all(), r
+        assert _as_dict(d.streaming_query(reads)) == ora.streaming_query(reads), r
+        shards.append(d)
+        answers.append(got.kmer_id)
+    # together: a shard that finds a k-mer gives the whole dictionary's id; the shards' answers combined are the whole dictionary's
+    per_shard = np.stack(answers)
+    found = per_shard != sshash_amd.INVALID_U64
+    assert (per_shard[found] == np.broadcast_to(whole, per_shard.shape)[found]).all()
+    assert (np.where(found.any(axis=0), per_shard.min(axis=0), sshash_amd.INVALID_U64) == whole).all()
+    assert found[:, :n].any(axis=0).all()
+    # route_device: the owner of a forward query's minimizer answers it, the owner of the reverse complement's a reverse-complemented one
+    fwd, back = np.ascontiguousarray(every).reshape(-1), np.ascontiguousarray(rc).reshape(-1)
+    ids = np.arange(n, dtype=np.uint64)
+    for queries, owner_of in ((fwd, 0), (back, 1)):
+        dq = torch.from_numpy(queries.view(np.int64)).to("cuda:0")
+        owners = [torch.full((n,), -1, dtype=torch.int32, device="cuda:0") for _ in range(2)]
+        shards[0].route_device(0, dq.data_ptr(), n, S, owners[0].data_ptr(), owners[1].data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        o_f, o_r = (o.cpu().numpy() for o in owners)
+        assert ((o_f >= 0) & (o_f < S)).all() and ((o_r >= 0) & (o_r < S)).all()
+        if canonical:
+            assert (o_f == o_r).all()
+        by_shard = np.stack([s.lookup(queries).kmer_id for s in shards])
+        owner = (o_f, o_r)[owner_of]
+        assert (by_shard[owner, np.arange(n)] == ids).all(), ("forward", "reverse complement")[owner_of]
+    # n = 0 writes nothing
+    untouched = torch.full((4,), 77, dtype=torch.int32, device="cuda:0")
+    shards[0].route_device(0, dq.data_ptr(), 0, S, untouched.data_ptr(), untouched.data_ptr())
+    torch.cuda.synchronize()
+    assert (untouched.cpu().numpy() == 77).all()
+    for d in shards:
+        d.close()
 
 
 def test_bad_shard_arguments(case_skew_regular):
