@@ -184,6 +184,26 @@ sshash_status sshash_access_packed(const sshash_dict* d, const uint64_t* kmer_id
 sshash_status sshash_access_packed_device(const sshash_dict* d, int device, const uint64_t* kmer_ids, uint64_t n,
                                           uint64_t* out_words, void* hip_stream);
 
+/* ---- dictionary::begin / at_kmer_id / at_string_id (include/dictionary.hpp:84-121) and the iterator behind them
+ *      (include/spectrum_preserving_string_set.hpp:120-183), a whole id range per call:
+ *      out_words[(i - begin)*W ..) = the k-mer with id i, for i in [begin_kmer_id, end_kmer_id) -- the value sshash_access_packed
+ *      gives for i. at_string_id(s) is the range [string_offsets(s).begin - s*(k-1), string_offsets(s).end - (s+1)*(k-1)).
+ *      SSHASH_ERR_ARGUMENT when begin > end, end > num_kmers, or out_words is NULL and the range is not empty; begin == end writes
+ *      nothing. The device variant is asynchronous on hip_stream (device pointer; ids are 64-bit, a range is not limited to 2^32
+ *      ids); the host variant decodes the host index on the CPU (no GPU needed), sliding one base at a time inside every string. */
+sshash_status sshash_iterate_packed_device(const sshash_dict* d, int device, uint64_t begin_kmer_id, uint64_t end_kmer_id,
+                                           uint64_t* out_words, void* hip_stream);
+sshash_status sshash_iterate_packed(const sshash_dict* d, uint64_t begin_kmer_id, uint64_t end_kmer_id, uint64_t* out_words);
+
+/* The reference's `sshash check` (tools/sshash.cpp:20-36, test/check.hpp:7-75) on the replica of `device`: every k-mer of the
+ * dictionary, taken by the iterator, is looked up (check_reverse_complement = 1) forward and reverse-complemented, and is_member
+ * is asked. out = { [0] k-mers checked, [1] forward lookups not found, [2] forward lookups with another id, [3] reverse-complement
+ * lookups not found or with another id, [4] is_member false, [5] smallest failing id or UINT64_MAX, [6..8) 0 }. Runs 2^25 k-mers
+ * at a time with scratch of its own, freed before it returns. Synchronous: returns when the counts are on the host.
+ * SSHASH_ERR_ARGUMENT on a minimizer shard (num_shards > 1), which answers only the k-mers it owns; table-shard replicas answer
+ * every query and are checked. */
+sshash_status sshash_check_device(const sshash_dict* d, int device, uint64_t out[8]);
+
 /* ---- dictionary::weight(kmer_id): include/dictionary.hpp (weight), src/dictionary.cpp:96-100,
  *      include/weights.hpp:147-152. Batched; SSHASH_ERR_ARGUMENT when the dictionary stores no weights
  *      (the reference's checker refuses it the same way, test/check_from_file.hpp:234-237) or an id is

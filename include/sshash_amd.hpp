@@ -283,6 +283,62 @@ public:
         return to_report(s);
     }
 
+    /* dictionary::iterator -- include/dictionary.hpp:84-94: (kmer id, k-mer) pairs of an id range in id order. It decodes
+       ITERATOR_BUFFER k-mers at a time into a buffer of its own (sshash_iterate_packed) and hands them out one by one. */
+    static constexpr uint64_t ITERATOR_BUFFER = uint64_t(1) << 16;
+    class iterator {
+    public:
+        bool has_next() const { return m_next != m_end; }
+        /* (kmer-id, encoded kmer) */
+        std::pair<uint64_t, uint_kmer_t> next() {
+            if (m_pos == m_filled) refill();
+            uint_kmer_t x;
+            for (uint32_t q = 0; q < m_W; ++q) x.bits[q] = m_buf[m_pos * m_W + q];
+            ++m_pos;
+            return {m_next++, x};
+        }
+
+    private:
+        friend class dictionary;
+        iterator(sshash_dict const* h, uint32_t W, uint64_t begin, uint64_t end)
+            : m_h(h), m_W(W), m_next(begin), m_end(end) {}
+        void refill() {
+            if (m_next == m_end) throw std::out_of_range("iterator: next() past the end of its range");
+            const uint64_t n = std::min(ITERATOR_BUFFER, m_end - m_next);
+            m_buf.resize(n * m_W);
+            check(sshash_iterate_packed(m_h, m_next, m_next + n, m_buf.data()));
+            m_pos = 0;
+            m_filled = n;
+        }
+        sshash_dict const* m_h;
+        uint32_t m_W;
+        uint64_t m_next, m_end;  // id of the next k-mer handed out; one past the last
+        std::vector<uint64_t> m_buf;
+        uint64_t m_pos = 0, m_filled = 0;  // m_buf holds the k-mers of ids m_next - m_pos .. m_next - m_pos + m_filled
+    };
+
+    /* include/dictionary.hpp:96-104 */
+    iterator begin() const { return at_kmer_id(0); }
+    iterator at_kmer_id(uint64_t kmer_id) const {
+        if (kmer_id > num_kmers()) throw std::out_of_range("at_kmer_id: kmer_id out of range");
+        return iterator(m_h, words_per_kmer(), kmer_id, num_kmers());
+    }
+    /* include/dictionary.hpp:113-121 */
+    iterator at_string_id(uint64_t string_id) const {
+        auto [begin, end] = string_offsets(string_id);
+        const uint64_t begin_kmer_id = begin - string_id * (k() - 1);
+        return iterator(m_h, words_per_kmer(), begin_kmer_id, begin_kmer_id + (end - begin) - k() + 1);
+    }
+
+    /* no reference counterpart: the reference's `sshash check` (tools/sshash.cpp:20-36) on the replica of `device`, the
+       counts of sshash_check_device: {k-mers, forward not found, forward with another id, reverse complement wrong,
+       not is_member, smallest failing id or invalid_uint64, 0, 0} */
+    std::array<uint64_t, 8> check(int device) const {
+        std::array<uint64_t, 8> out{};
+        check(sshash_check_device(m_h, device, out.data()));
+        return out;
+    }
+
     sshash_dict* handle() const { return m_h; }
     uint32_t words_per_kmer() const { return m_info.words_per_kmer; }
 

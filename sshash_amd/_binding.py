@@ -178,6 +178,9 @@ def _load() -> C.CDLL:
         "sshash_route_bucket_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, C.c_int, P, P, P, P]),
         "sshash_route_bucket_by_key_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P, P, P]),
         "sshash_route_combine_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, P, P]),
+        "sshash_iterate_packed": (C.c_int, [P, C.c_uint64, C.c_uint64, P]),
+        "sshash_iterate_packed_device": (C.c_int, [P, C.c_int, C.c_uint64, C.c_uint64, P, P]),
+        "sshash_check_device": (C.c_int, [P, C.c_int, C.POINTER(C.c_uint64 * 8)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here == ABI symbol missing: fail loudly
@@ -196,7 +199,8 @@ C_ABI_SYMBOLS = (
     "sshash_access_packed_device sshash_weight sshash_weight_device "
     "sshash_streaming_query_from_file sshash_streaming_query sshash_streaming_query_device "
     "sshash_streaming_lookup sshash_streaming_lookup_device sshash_sharded_lookup_device sshash_sharded_lookup_rccl "
-    "sshash_route_packed_device sshash_route_bucket_device sshash_route_bucket_by_key_device sshash_route_combine_device"
+    "sshash_route_packed_device sshash_route_bucket_device sshash_route_bucket_by_key_device sshash_route_combine_device "
+    "sshash_iterate_packed sshash_iterate_packed_device sshash_check_device"
 ).split()
 
 
@@ -517,6 +521,38 @@ class Dictionary:
         out = np.empty(ids.size * self.words_per_kmer(), dtype=np.uint64)
         _check(_load().sshash_access_packed(self._h, ids.ctypes.data, ids.size, out.ctypes.data))
         return out
+
+    # ---- iteration: dictionary::begin / at_kmer_id / at_string_id (reference include/dictionary.hpp:84-121) -------------------
+    def kmers(self, begin: int = 0, end: Optional[int] = None) -> np.ndarray:
+        """The k-mers of the ids [begin, end) in id order (default: the whole dictionary), decoded on the host: flat uint64,
+        words_per_kmer() words per k-mer, like access_packed."""
+        end = self.num_kmers() if end is None else int(end)
+        begin = int(begin)
+        if begin < 0 or end < 0:
+            raise SSHashError(1, "iterate: ids are non-negative")
+        out = np.empty(max(end - begin, 0) * self.words_per_kmer(), dtype=np.uint64)
+        _check(_load().sshash_iterate_packed(self._h, begin, end, out.ctypes.data if out.size else None))
+        return out
+
+    def string_kmers(self, string_id: int) -> np.ndarray:
+        """dictionary::at_string_id: the k-mers of string `string_id`, through string_offsets."""
+        sid = int(string_id)
+        b, e = self.string_offsets([sid])
+        km1 = self.k() - 1
+        return self.kmers(int(b[0]) - sid * km1, int(e[0]) - (sid + 1) * km1)
+
+    def kmers_device(self, device: int, begin: int, end: int, d_out: int, stream: int = 0) -> None:
+        """The same on the GPU into the device buffer d_out ((end - begin) * words_per_kmer() uint64), asynchronous on `stream`."""
+        _check(_load().sshash_iterate_packed_device(self._h, int(device), int(begin), int(end), C.c_void_p(d_out),
+                                                    C.c_void_p(stream)))
+
+    def check(self, device: int = 0) -> dict:
+        """The reference's `sshash check` on the replica of `device`: every k-mer, taken by the iterator, looked up forward and
+        reverse-complemented and asked is_member. Counts of failures; first_failure is the smallest failing id or INVALID_U64."""
+        out = (C.c_uint64 * 8)()
+        _check(_load().sshash_check_device(self._h, int(device), C.byref(out)))
+        names = ("kmers", "forward_not_found", "forward_other_id", "reverse_complement_wrong", "not_member", "first_failure")
+        return {name: int(out[i]) for i, name in enumerate(names)}
 
     # ---- weights ---------------------------------------------------------------------------------
     def weight(self, kmer_ids: Iterable[int]) -> np.ndarray:

@@ -338,6 +338,31 @@ sshash_status sshash_access_packed_device(const sshash_dict* d, int device, cons
     return guarded([&] { d->eng->access_packed_device(device, kmer_ids, n, out_words, hip_stream); });
 }
 
+sshash_status sshash_iterate_packed(const sshash_dict* d, uint64_t begin_kmer_id, uint64_t end_kmer_id, uint64_t* out_words) {
+    if (!d || (!out_words && end_kmer_id > begin_kmer_id)) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (begin_kmer_id > end_kmer_id || end_kmer_id > d->idx->num_kmers)
+        return fail(SSHASH_ERR_ARGUMENT, "iterate: need begin <= end <= num_kmers");
+    return guarded([&] {
+        const uint32_t W = d->idx->words_per_kmer();
+        const uint64_t n = end_kmer_id - begin_kmer_id;
+        const uint32_t nt = std::max(1u, std::min(32u, std::thread::hardware_concurrency()));
+        detail::parallel_ranges(n, n > (uint64_t(1) << 16) ? nt : 1, [&](uint64_t b, uint64_t e, uint32_t) {
+            iterate_kmers_packed(*d->idx, begin_kmer_id + b, begin_kmer_id + e, out_words + b * W);
+        });
+    });
+}
+
+sshash_status sshash_iterate_packed_device(const sshash_dict* d, int device, uint64_t begin_kmer_id, uint64_t end_kmer_id,
+                                           uint64_t* out_words, void* hip_stream) {
+    if (!d || (!out_words && end_kmer_id > begin_kmer_id)) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] { d->eng->iterate_packed_device(device, begin_kmer_id, end_kmer_id, out_words, hip_stream); });
+}
+
+sshash_status sshash_check_device(const sshash_dict* d, int device, uint64_t out[8]) {
+    if (!d || !out) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] { d->eng->check_device(device, out); });
+}
+
 sshash_status sshash_streaming_query_from_file(const sshash_dict* d, const char* filename, int multiline,
                                                sshash_streaming_report* report) {
     if (!d || !filename || !report) return fail(SSHASH_ERR_ARGUMENT, "null argument");

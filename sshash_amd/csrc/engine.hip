@@ -1277,14 +1277,7 @@ access_kernel(const dict_view d, const uint64_t* __restrict__ ids, const uint64_
         for (int j = 0; j < W; ++j) out[i * W + j] = INVALID_U64;
         return;
     }
-    const uint64_t km1 = d.k - 1;
-    uint64_t lo = 0, hi = d.num_strings - 1;  // largest s with endpoints[s] - s*(k-1) <= id
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo + 1) / 2;
-        if (d.endpoints[mid] - mid * km1 <= id) lo = mid;
-        else hi = mid - 1;
-    }
-    const window_t<W> w = read_window<W>(d.granules, id + lo * km1, d.k);
+    const window_t<W> w = read_window<W>(d.granules, id + string_of_kmer_id(d, id) * (d.k - 1), d.k);
     for (int j = 0; j < W; ++j) out[i * W + j] = w.kmer.w[j];
 }
 
@@ -1327,6 +1320,202 @@ void engine::weight_device(int device, uint64_t const* d_ids, uint64_t n, uint64
     device_guard guard(device);
     hipLaunchKernelGGL(weight_kernel, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, hipStream_t(stream), rep->view, d_ids, n, d_out);
     HIP_CHECK(hipGetLastError());
+}
+
+/* ---- the dictionary's k-mer iterator on the device (dictionary::at_kmer_id / begin / at_string_id, include/dictionary.hpp:84-121,
+        spectrum_preserving_string_set::iterator, include/spectrum_preserving_string_set.hpp:120-183) for a whole id range at
+        once, and the reference's `sshash check` (tools/sshash.cpp:20-36, test/check.hpp:7-75) built on it ---- */
+
+/* ---- iterate: k-mers of the ids [begin, end) in id order -------------------------------------------------------------------
+   A block owns a contiguous run of tiles of IT_TILE consecutive ids; lane l decodes ids lo + r*IT_BLOCK + l, so a wave's stores
+   are 64 consecutive k-mers (512 or 1024 contiguous bytes) and neighbouring lanes read the same atoms / granules. Only the
+   block's first tile pays the binary search over the endpoints (string_of_kmer_id); from there the block walks the strings:
+   each tile stages the first k-mer ids of the strings it touches into LDS, IT_BLOCK at a time, until one lies past the tile.
+   Ids are strictly increasing across strings (a string holds at least one k-mer), so a tile touches at most IT_TILE + 1
+   strings: IT_STAGE entries always suffice. The block's next tile starts at the last staged string whose first id is <= its
+   first id. */
+
+constexpr uint32_t IT_BLOCK = 256;
+constexpr uint32_t IT_PER_LANE = 8;
+constexpr uint32_t IT_TILE = IT_BLOCK * IT_PER_LANE;                                         // 2048 ids
+constexpr uint32_t IT_STAGE = ((IT_TILE + 1 + IT_BLOCK - 1) / IT_BLOCK) * IT_BLOCK;          // 2304 entries, 18 KiB of LDS
+constexpr uint32_t IT_BLOCKS_PER_CU = 32;  // 8 resident (LDS) x 4 rounds: the last round's imbalance is a quarter of one
+
+/* largest j in [a, b] with first[j] <= id, given first[a] <= id */
+__device__ __forceinline__ uint32_t last_leq(uint64_t const* first, uint32_t a, uint32_t b, uint64_t id) {
+    while (a < b) {
+        const uint32_t mid = (a + b + 1) / 2;
+        if (first[mid] <= id) a = mid;
+        else b = mid - 1;
+    }
+    return a;
+}
+
+template <int W>
+__global__ void __launch_bounds__(IT_BLOCK)
+iterate_kernel(const dict_view d, const uint64_t begin, const uint64_t end, const uint64_t tiles_per_block,
+               uint64_t* __restrict__ out) {
+    __shared__ uint64_t first[IT_STAGE];  // first[j] = first k-mer id of string s0 + j (UINT64_MAX past the last string)
+    __shared__ uint64_t start_string;
+    const uint64_t num_tiles = (end - begin + IT_TILE - 1) / IT_TILE;
+    const uint64_t t_begin = uint64_t(blockIdx.x) * tiles_per_block;
+    if (t_begin >= num_tiles) return;
+    const uint64_t t_end = min(num_tiles, t_begin + tiles_per_block);
+    const uint64_t km1 = d.k - 1;
+
+    if (threadIdx.x == 0) start_string = string_of_kmer_id(d, begin + t_begin * IT_TILE);
+    __syncthreads();
+    uint64_t s0 = start_string;
+
+    for (uint64_t t = t_begin; t < t_end; ++t) {
+        const uint64_t lo = begin + t * IT_TILE;
+        const uint64_t hi = min(end, lo + IT_TILE);  // ids [lo, hi); first[0] <= lo
+        uint32_t staged = 0;
+        for (;;) {
+            const uint64_t s = s0 + staged + threadIdx.x;
+            first[staged + threadIdx.x] = s <= d.num_strings ? d.endpoints[s] - s * km1 : INVALID_U64;
+            __syncthreads();
+            staged += IT_BLOCK;
+            /* endpoints[num_strings] - num_strings*(k-1) == num_kmers >= hi: the loop ends by the first test at the latest after
+               IT_STAGE entries; the second is a guard. Both are uniform over the block. */
+            if (first[staged - 1] >= hi || staged == IT_STAGE) break;
+        }
+
+        uint32_t j = 0;
+        for (uint32_t r = 0; r < IT_PER_LANE; ++r) {
+            const uint64_t id = lo + r * IT_BLOCK + threadIdx.x;
+            if (id >= hi) break;
+            j = last_leq(first, j, staged - 1, id);  // ids of one lane increase: so does j
+            const window_t<W> w = read_window<W>(d.granules, id + (s0 + j) * km1, d.k);
+            uint64_t* o = out + (id - begin) * W;
+            for (int q = 0; q < W; ++q) o[q] = w.kmer.w[q];
+        }
+
+        const uint64_t next_s0 = s0 + last_leq(first, 0, staged - 1, hi);  // first[staged - 1] >= hi: it exists
+        __syncthreads();  // every lane is done with `first` before the next tile overwrites it
+        s0 = next_s0;
+    }
+}
+
+void engine::iterate_packed_device(int device, uint64_t begin, uint64_t end, uint64_t* d_out, void* stream) const {
+    device_replica const* rep = replica(device);
+    if (begin > end || end > rep->view.num_kmers)
+        throw error(error_kind::argument, "iterate: need begin <= end <= num_kmers");
+    if (begin == end) return;
+    device_guard guard(device);
+    int cus = 0;
+    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    const uint64_t num_tiles = (end - begin + IT_TILE - 1) / IT_TILE;
+    const uint64_t max_blocks = uint64_t(std::max(cus, 1)) * IT_BLOCKS_PER_CU;
+    const uint64_t tiles_per_block = (num_tiles + max_blocks - 1) / max_blocks;
+    const dim3 grid(uint32_t((num_tiles + tiles_per_block - 1) / tiles_per_block)), block(IT_BLOCK);
+    if (rep->view.k <= 31)
+        hipLaunchKernelGGL(iterate_kernel<1>, grid, block, 0, hipStream_t(stream), rep->view, begin, end, tiles_per_block, d_out);
+    else
+        hipLaunchKernelGGL(iterate_kernel<2>, grid, block, 0, hipStream_t(stream), rep->view, begin, end, tiles_per_block, d_out);
+    HIP_CHECK(hipGetLastError());
+}
+
+/* ---- check: every k-mer looked up forward and reverse-complemented, and asked is_member ---------------------------------- */
+
+enum : int { CHECK_KMERS = 0, CHECK_FWD_NOT_FOUND, CHECK_FWD_OTHER_ID, CHECK_RC_WRONG, CHECK_NOT_MEMBER, CHECK_FIRST_FAILURE };
+constexpr uint64_t CHECK_CHUNK = uint64_t(1) << 25;  // k-mers per round: scratch of 2^25 x (8W + 9) bytes
+
+template <int W>
+__global__ void __launch_bounds__(256) revcomp_kernel(uint64_t* __restrict__ kmers, const uint64_t n, const uint32_t k) {
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += uint64_t(gridDim.x) * blockDim.x) {
+        kmer_w<W> x;
+        for (int q = 0; q < W; ++q) x.w[q] = kmers[i * W + q];
+        x = kmer_revcomp<W>(x, k);
+        for (int q = 0; q < W; ++q) kmers[i * W + q] = x.w[q];
+    }
+}
+
+/* member == null: the reverse-complement pass (any id but first_id + i is a failure) */
+__global__ void __launch_bounds__(256)
+check_compare_kernel(const uint64_t* __restrict__ ids, const uint8_t* __restrict__ member, const uint64_t n, const uint64_t first_id,
+                     unsigned long long* __restrict__ counts) {
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += uint64_t(gridDim.x) * blockDim.x) {
+        const uint64_t want = first_id + i, got = ids[i];
+        bool failed;
+        if (member) {
+            const bool not_found = got == INVALID_U64, other = !not_found && got != want, not_member = member[i] == 0;
+            if (not_found) atomicAdd(&counts[CHECK_FWD_NOT_FOUND], 1ull);
+            if (other) atomicAdd(&counts[CHECK_FWD_OTHER_ID], 1ull);
+            if (not_member) atomicAdd(&counts[CHECK_NOT_MEMBER], 1ull);
+            failed = not_found || other || not_member;
+        } else {
+            failed = got != want;
+            if (failed) atomicAdd(&counts[CHECK_RC_WRONG], 1ull);
+        }
+        if (failed) atomicMin(&counts[CHECK_FIRST_FAILURE], (unsigned long long)want);
+    }
+}
+
+namespace {
+/* freed on every way out of check_device. The call runs on a stream of its own, so that it does not serialise with the other
+   work of the process on the device, as the null stream would; the lookup scratch the replica keyed by that stream
+   (device_replica::scratch_for) is handed back before the stream is destroyed. */
+struct check_scratch {
+    device_replica const* rep;
+    void* p[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipStream_t s = nullptr;
+    explicit check_scratch(device_replica const* r) : rep(r) {}
+    ~check_scratch() {
+        if (s) (void)hipStreamSynchronize(s);
+        for (void* q : p)
+            if (q) (void)hipFree(q);
+        if (s) {
+            rep->release_stream_scratch(s);
+            (void)hipStreamDestroy(s);
+        }
+    }
+};
+}  // namespace
+
+void engine::check_device(int device, uint64_t out[8]) const {
+    if (m_idx->num_shards > 1)
+        throw error(error_kind::argument, "check: a minimizer shard answers only the k-mers it owns (check the whole index)");
+    device_replica const* rep = replica(device);
+    device_guard guard(device);
+    const uint64_t n = rep->view.num_kmers;
+    const uint32_t W = rep->view.k <= 31 ? 1 : 2;
+    const uint64_t chunk = std::min(n, CHECK_CHUNK);
+    check_scratch x(rep);
+    HIP_CHECK(hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking));
+    HIP_CHECK(hipMalloc(&x.p[0], chunk * W * sizeof(uint64_t)));
+    HIP_CHECK(hipMalloc(&x.p[1], chunk * sizeof(uint64_t)));
+    HIP_CHECK(hipMalloc(&x.p[2], chunk));
+    HIP_CHECK(hipMalloc(&x.p[3], 8 * sizeof(uint64_t)));
+    uint64_t* d_kmers = static_cast<uint64_t*>(x.p[0]);
+    uint64_t* d_ids = static_cast<uint64_t*>(x.p[1]);
+    uint8_t* d_member = static_cast<uint8_t*>(x.p[2]);
+    unsigned long long* d_counts = static_cast<unsigned long long*>(x.p[3]);
+    HIP_CHECK(hipMemsetAsync(d_counts, 0, 8 * sizeof(uint64_t), x.s));
+    HIP_CHECK(hipMemsetAsync(d_counts + CHECK_FIRST_FAILURE, 0xFF, sizeof(uint64_t), x.s));
+
+    result_view ids{};
+    ids.kmer_id = d_ids;
+    for (uint64_t b = 0; b < n; b += chunk) {
+        const uint64_t m = std::min(chunk, n - b);
+        const dim3 grid(uint32_t(std::min<uint64_t>((m + 255) / 256, 16384))), block(256);
+        iterate_packed_device(device, b, b + m, d_kmers, x.s);
+        lookup_packed_device(device, d_kmers, m, true, out_mode::ids, ids, nullptr, x.s);
+        lookup_packed_device(device, d_kmers, m, true, out_mode::member, result_view{}, d_member, x.s);
+        hipLaunchKernelGGL(check_compare_kernel, grid, block, 0, x.s, d_ids, d_member, m, b, d_counts);
+        HIP_CHECK(hipGetLastError());
+        if (W == 1) hipLaunchKernelGGL(revcomp_kernel<1>, grid, block, 0, x.s, d_kmers, m, rep->view.k);
+        else hipLaunchKernelGGL(revcomp_kernel<2>, grid, block, 0, x.s, d_kmers, m, rep->view.k);
+        HIP_CHECK(hipGetLastError());
+        lookup_packed_device(device, d_kmers, m, true, out_mode::ids, ids, nullptr, x.s);
+        hipLaunchKernelGGL(check_compare_kernel, grid, block, 0, x.s, d_ids, nullptr, m, b, d_counts);
+        HIP_CHECK(hipGetLastError());
+    }
+    uint64_t h[8];
+    HIP_CHECK(hipMemcpyAsync(h, d_counts, sizeof(h), hipMemcpyDeviceToHost, x.s));
+    HIP_CHECK(hipStreamSynchronize(x.s));
+    h[CHECK_KMERS] = n;
+    for (int i = 0; i < 8; ++i) out[i] = h[i];
 }
 
 /* ---- host-buffer path -----------------------------------------------------------------------

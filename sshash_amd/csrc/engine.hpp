@@ -71,6 +71,12 @@ public:
        (all-ones for an id >= num_kmers). */
     void access_packed_device(int device, uint64_t const* d_ids, uint64_t n, uint64_t* d_out, void* stream) const;
 
+    /* the k-mers of the ids [begin, end) in id order (dictionary::at_kmer_id(begin) advanced to end), device buffer: n*W
+       packed words; throws unless begin <= end <= num_kmers (engine.hip) */
+    void iterate_packed_device(int device, uint64_t begin, uint64_t end, uint64_t* d_out, void* stream) const;
+    /* `sshash check` on the replica of `device` (engine.hip; sshash_check_device in include/sshash_amd.h). Synchronous. */
+    void check_device(int device, uint64_t out[8]) const;
+
     /* weight(kmer_id) for a batch of ids, device buffers (all-ones for an id >= num_kmers); throws when the
        dictionary stores no weights */
     void weight_device(int device, uint64_t const* d_ids, uint64_t n, uint64_t* d_out, void* stream) const;

@@ -585,7 +585,7 @@ uint64_t weight_of(host_index const& idx, uint64_t kmer_id) {
 
 /* ---- access ---------------------------------------------------------------------------- */
 
-static uint64_t id_to_offset(host_index const& idx, uint64_t kmer_id) {
+static uint64_t string_of_id(host_index const& idx, uint64_t kmer_id) {
     /* largest s with endpoints[s] - s*(k-1) <= kmer_id (include/offsets.hpp:41-65) */
     uint64_t lo = 0, hi = idx.num_strings - 1;
     const uint64_t km1 = idx.k - 1;
@@ -594,7 +594,11 @@ static uint64_t id_to_offset(host_index const& idx, uint64_t kmer_id) {
         if (idx.endpoints[mid] - mid * km1 <= kmer_id) lo = mid;
         else hi = mid - 1;
     }
-    return kmer_id + lo * km1;
+    return lo;
+}
+
+static uint64_t id_to_offset(host_index const& idx, uint64_t kmer_id) {
+    return kmer_id + string_of_id(idx, kmer_id) * (idx.k - 1);
 }
 
 void access_kmer_packed(host_index const& idx, uint64_t kmer_id, uint64_t* out) {
@@ -607,6 +611,33 @@ void access_kmer_packed(host_index const& idx, uint64_t kmer_id, uint64_t* out) 
         out[0] = x.w[0];
         out[1] = x.w[1];
     }
+}
+
+/* spectrum_preserving_string_set::iterator (include/spectrum_preserving_string_set.hpp:120-183): one search for the first id,
+   then a k-mer read whole at the start of every string and slid one base at a time inside it */
+template <int W>
+static void iterate_kmers(host_index const& idx, uint64_t begin, uint64_t end, uint64_t* out) {
+    uint64_t const* words = idx.strings.data();
+    const uint64_t km1 = idx.k - 1;
+    uint64_t id = begin;
+    for (uint64_t s = string_of_id(idx, begin); id < end; ++s) {
+        const uint64_t stop = std::min(end, idx.endpoints[s + 1] - (s + 1) * km1);  // one past the string's last id
+        uint64_t off = id + s * km1;
+        kmer_w<W> x = read_kmer<W>(words, off, idx.k);
+        for (;;) {
+            for (int q = 0; q < W; ++q) out[(id - begin) * W + q] = x.w[q];
+            if (++id == stop) break;
+            x = kmer_roll<W>(x, base_at(words, off + idx.k), idx.k);
+            ++off;
+        }
+    }
+}
+
+void iterate_kmers_packed(host_index const& idx, uint64_t begin, uint64_t end, uint64_t* out) {
+    if (begin > end || end > idx.num_kmers) throw error(error_kind::argument, "iterate: need begin <= end <= num_kmers");
+    if (begin == end) return;
+    if (idx.words_per_kmer() == 1) iterate_kmers<1>(idx, begin, end, out);
+    else iterate_kmers<2>(idx, begin, end, out);
 }
 
 void access_kmer(host_index const& idx, uint64_t kmer_id, char* out) {

@@ -108,6 +108,10 @@ void access_kmer(host_index const& idx, uint64_t kmer_id, char* out);
 /* Packed form: out[0..W) words. */
 void access_kmer_packed(host_index const& idx, uint64_t kmer_id, uint64_t* out);
 
+/* the k-mers of the ids [begin, end) in id order, out[(id - begin)*W ..): dictionary::at_kmer_id(begin) advanced to end
+   (include/dictionary.hpp:84-104); throws unless begin <= end <= num_kmers */
+void iterate_kmers_packed(host_index const& idx, uint64_t begin, uint64_t end, uint64_t* out);
+
 /* weight(kmer_id): include/weights.hpp:147-152 (dictionary::weight, src/dictionary.cpp:96-100) */
 uint64_t weight_of(host_index const& idx, uint64_t kmer_id);
 

@@ -91,6 +91,19 @@ __device__ __forceinline__ window_t<2> read_window<2>(void const* __restrict__ b
     return w;
 }
 
+/* offsets::id_to_offset (include/offsets.hpp:41-65) as a binary search over the endpoints: the string holding k-mer `id`
+   (< num_kmers), the largest s with endpoints[s] - s*(k-1) <= id; its k-mer starts at base id + s*(k-1) */
+__device__ __forceinline__ uint64_t string_of_kmer_id(dict_view const& d, uint64_t id) {
+    const uint64_t km1 = d.k - 1;
+    uint64_t lo = 0, hi = d.num_strings - 1;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (d.endpoints[mid] - mid * km1 <= id) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
 /* the m-mer (m <= 31) starting at base `off`, whatever the block layout */
 __device__ __forceinline__ uint64_t read_mmer(dict_view const& d, uint64_t off) {
     return d.k <= 31 ? read_window<1>(d.granules, off, d.m).kmer.w[0] : read_window<2>(d.granules, off, d.m).kmer.w[0];

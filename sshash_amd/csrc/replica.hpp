@@ -158,6 +158,16 @@ struct device_replica {
         return slot;
     }
 
+    /* Hand back the scratch of a stream that its owner is about to destroy (the work on it must be complete): a call that makes a
+       stream of its own for its duration (engine::check_device) leaves no block behind. */
+    void release_stream_scratch(void* stream) const {
+        std::lock_guard<std::mutex> lock(scratch_mutex);
+        auto it = scratch.find(stream);
+        if (it == scratch.end()) return;
+        it->second.release();
+        scratch.erase(it);
+    }
+
     /* Per-stream scratch of the streaming query (streaming.hip: the 2-bit packed copy of a call's reads and their validity bits).
        Round 5 took it from the pool above and gave it back at every call -- two stream-ordered allocations of ~0.4 GB each per call
        of 3 x 10^9 bases, on the host side of a step that the device then waits for (profiles/r06/). Kept per stream instead: calls
