@@ -85,9 +85,19 @@ result_view to_view(sshash_results const* r) {
     return v;
 }
 
-bool wants_full(sshash_results const* r) {
-    return r->kmer_id_in_string || r->kmer_offset || r->string_id || r->string_begin || r->string_end ||
-           r->kmer_orientation || r->minimizer_found;
+bool wants_full(sshash_results const* r) {  // any array besides kmer_id
+    bool any = false;
+    for_each_field([&](int f, auto* p, uint64_t) { any = any || (f > 0 && p); }, to_view(r));
+    return any;
+}
+
+void fill_report(sshash_streaming_report* report, streaming_report const& r) {
+    report->num_kmers = r.num_kmers;
+    report->num_positive_kmers = r.num_positive_kmers;
+    report->num_negative_kmers = r.num_negative_kmers;
+    report->num_invalid_kmers = r.num_invalid_kmers;
+    report->num_searches = r.num_searches;
+    report->num_extensions = r.num_extensions;
 }
 
 }  // namespace
@@ -379,12 +389,7 @@ sshash_status sshash_streaming_query_from_file(const sshash_dict* d, const char*
         if (!multiline && fastq_pieces::applicable(filename) && !test_hook_u64("sequential_reader", 0, 0, 1)) {
             streaming_report r;
             if (d->eng->streaming_query_fastq_pieces(filename, r)) {
-                report->num_kmers = r.num_kmers;
-                report->num_positive_kmers = r.num_positive_kmers;
-                report->num_negative_kmers = r.num_negative_kmers;
-                report->num_invalid_kmers = r.num_invalid_kmers;
-                report->num_searches = r.num_searches;
-                report->num_extensions = r.num_extensions;
+                fill_report(report, r);
                 return;
             }
         }
@@ -435,6 +440,7 @@ sshash_status sshash_streaming_query_from_file(const sshash_dict* d, const char*
         } join_reader{reader, mu, cv, abandon};
         double waited = 0, worked = 0;  // SSHASH_AMD_VERBOSE: where the wall clock of the file query went
         uint64_t batches = 0;
+        streaming_report total;
         auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         for (int at = 0;; at ^= 1) {
             const double t0 = now();
@@ -448,12 +454,7 @@ sshash_status sshash_streaming_query_from_file(const sshash_dict* d, const char*
             waited += t1 - t0;
             worked += now() - t1;
             ++batches;
-            report->num_kmers += r.num_kmers;
-            report->num_positive_kmers += r.num_positive_kmers;
-            report->num_negative_kmers += r.num_negative_kmers;
-            report->num_invalid_kmers += r.num_invalid_kmers;
-            report->num_searches += r.num_searches;
-            report->num_extensions += r.num_extensions;
+            fill_report(report, total += r);
             std::lock_guard<std::mutex> lock(mu);
             filled[at] = 0;
             cv.notify_all();
@@ -470,13 +471,7 @@ sshash_status sshash_streaming_query(const sshash_dict* d, const char* bases, co
     if (!d || !report || (num_reads && (!bases || !read_offsets))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
     std::memset(report, 0, sizeof(*report));
     return guarded([&] {
-        const streaming_report r = d->eng->streaming_query_host(bases, read_offsets, num_reads);
-        report->num_kmers = r.num_kmers;
-        report->num_positive_kmers = r.num_positive_kmers;
-        report->num_negative_kmers = r.num_negative_kmers;
-        report->num_invalid_kmers = r.num_invalid_kmers;
-        report->num_searches = r.num_searches;
-        report->num_extensions = r.num_extensions;
+        fill_report(report, d->eng->streaming_query_host(bases, read_offsets, num_reads));
     });
 }
 
@@ -485,15 +480,6 @@ sshash_status sshash_streaming_query_device(const sshash_dict* d, int device, co
                                             uint64_t* report, void* hip_stream) {
     if (!d || !report || (num_reads && (!bases || !read_offsets))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
     return guarded([&] { d->eng->streaming_query_device(device, bases, read_offsets, num_reads, total_bases, report, hip_stream); });
-}
-
-static void fill_report(sshash_streaming_report* report, streaming_report const& r) {
-    report->num_kmers = r.num_kmers;
-    report->num_positive_kmers = r.num_positive_kmers;
-    report->num_negative_kmers = r.num_negative_kmers;
-    report->num_invalid_kmers = r.num_invalid_kmers;
-    report->num_searches = r.num_searches;
-    report->num_extensions = r.num_extensions;
 }
 
 sshash_status sshash_streaming_lookup_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,

@@ -544,4 +544,26 @@ struct result_view {
     uint8_t* minimizer_found;
 };
 
+/* Host side: f(index, field of each view..., element width) for the eight fields, in sshash_results order. A view passed
+   as an lvalue lends f its fields by reference, so f may set them. */
+template <typename F, typename... Views>
+void for_each_field(F&& f, Views&&... v) {
+    f(0, v.kmer_id..., 8);
+    f(1, v.kmer_id_in_string..., 8);
+    f(2, v.kmer_offset..., 8);
+    f(3, v.string_id..., 8);
+    f(4, v.string_begin..., 8);
+    f(5, v.string_end..., 8);
+    f(6, v.kmer_orientation..., 1);
+    f(7, v.minimizer_found..., 1);
+}
+
+/* every non-null field moved `at` entries on */
+inline result_view advance(result_view v, uint64_t at) {
+    for_each_field([at](int, auto*& p, uint64_t) {
+        if (p) p += at;
+    }, v);
+    return v;
+}
+
 }  // namespace sshash_amd

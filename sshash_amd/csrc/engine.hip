@@ -311,13 +311,11 @@ void engine::to_device(int device, uint32_t table_shards, uint32_t table_shard_i
         v.cw_packed = 1;
     } else {
         const uint64_t n = idx.control_codewords.size;
-        uint64_t* packed = nullptr;
-        uint64_t* wide = nullptr;
-        const size_t packed_bytes = idx.control_codewords.words.size() * sizeof(uint64_t);
-        HIP_CHECK(hipMalloc(&packed, packed_bytes));
-        HIP_CHECK(hipMemcpy(packed, idx.control_codewords.words.data(), packed_bytes, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMalloc(&wide, std::max<uint64_t>(n, 1) * sizeof(uint64_t)));
-        rep->allocations.push_back(wide);
+        device_buffers tmp;
+        uint64_t* packed = tmp.alloc<uint64_t>(idx.control_codewords.words.size());
+        HIP_CHECK(hipMemcpy(packed, idx.control_codewords.words.data(), idx.control_codewords.words.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+        uint64_t* wide = tmp.alloc<uint64_t>(std::max<uint64_t>(n, 1));
+        tmp.keep(wide, *rep);
         rep->bytes += std::max<uint64_t>(n, 1) * sizeof(uint64_t);
         if (n) {
             check_single_launch(n, "upload (one lane per minimizer)");
@@ -325,7 +323,6 @@ void engine::to_device(int device, uint32_t table_shards, uint32_t table_shard_i
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipDeviceSynchronize());
         }
-        HIP_CHECK(hipFree(packed));
         v.codewords = wide;
     }
     /* minimizer directory (device_layout.hpp (4)) */
@@ -334,24 +331,20 @@ void engine::to_device(int device, uint32_t table_shards, uint32_t table_shard_i
         const uint64_t n = idx.control_codewords.size;
         const uint64_t nb = uint64_t(double(n) / DIR_LOAD) + 1;
         if (want && n && nb < (uint64_t(1) << 32) && v.cw_width <= DIR_CODE_BITS) {
-            uint64_t* buckets = nullptr;
-            uint32_t* claimed = nullptr;
-            unsigned long long* stats = nullptr;
-            HIP_CHECK(hipMalloc(&buckets, nb * 32));
-            HIP_CHECK(hipMalloc(&claimed, nb * 4));
-            HIP_CHECK(hipMalloc(&stats, 16));
+            device_buffers tmp;
+            uint64_t* buckets = tmp.alloc<uint64_t>(nb * 4);
+            uint32_t* claimed = tmp.alloc<uint32_t>(nb);
+            unsigned long long* stats = tmp.alloc<unsigned long long>(2);
             HIP_CHECK(hipMemset(buckets, 0, nb * 32));
             HIP_CHECK(hipMemset(claimed, 0, nb * 4));
             HIP_CHECK(hipMemset(stats, 0, 16));
-            rep->allocations.push_back(buckets);
+            tmp.keep(buckets, *rep);
             rep->bytes += nb * 32;
             hipLaunchKernelGGL(directory_insert_kernel, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, 0, v, n, buckets, claimed, uint32_t(nb));
             hipLaunchKernelGGL(directory_finalize_kernel, dim3(uint32_t((nb + 255) / 256)), dim3(256), 0, 0, buckets, claimed, uint32_t(nb), stats);
             HIP_CHECK(hipGetLastError());
             unsigned long long h_stats[2];
             HIP_CHECK(hipMemcpy(h_stats, stats, 16, hipMemcpyDeviceToHost));
-            HIP_CHECK(hipFree(stats));
-            HIP_CHECK(hipFree(claimed));
             rep->directory_overflowed = h_stats[0];
             rep->directory_entries = h_stats[1];
             v.directory.buckets = buckets;
@@ -806,18 +799,6 @@ deferred_lookup_kernel(const dict_view d, const skew_part_dev* __restrict__ skew
     }
 }
 
-static result_view advance(result_view v, uint64_t at) {
-    if (v.kmer_id) v.kmer_id += at;
-    if (v.kmer_id_in_string) v.kmer_id_in_string += at;
-    if (v.kmer_offset) v.kmer_offset += at;
-    if (v.string_id) v.string_id += at;
-    if (v.string_begin) v.string_begin += at;
-    if (v.string_end) v.string_end += at;
-    if (v.kmer_orientation) v.kmer_orientation += at;
-    if (v.minimizer_found) v.minimizer_found += at;
-    return v;
-}
-
 /* queries per launch sequence (first, resume, deferred): at most 2^27 (queue entries carry 27-bit indices); the tests cut a small batch
    into several (hooks.hpp) */
 static uint64_t launch_piece_queries() { return test_hook_u64("piece", uint64_t(1) << 27, 4096, uint64_t(1) << 27); }
@@ -999,14 +980,13 @@ void engine::neighbours_packed_device(int device, uint64_t const* d_kmers, uint6
     hipStream_t s = hipStream_t(stream);
     const uint32_t W = rep->view.k <= 31 ? 1 : 2;
     check_single_launch(8 * n, "kmer_neighbours");
-    uint64_t* expanded = nullptr;
-    expanded = static_cast<uint64_t*>(rep->stream_alloc(8 * n * W * sizeof(uint64_t), s));
+    device_buffers tmp(rep, s);
+    uint64_t* expanded = tmp.alloc<uint64_t>(8 * n * W);
     const dim3 grid(uint32_t((8 * n + 255) / 256)), block(256);
     if (W == 1) hipLaunchKernelGGL(expand_neighbours_kernel<1>, grid, block, 0, s, d_kmers, n, rep->view.k, expanded);
     else hipLaunchKernelGGL(expand_neighbours_kernel<2>, grid, block, 0, s, d_kmers, n, rep->view.k, expanded);
     HIP_CHECK(hipGetLastError());
     launch_any<false>(mode, rep, expanded, 8 * n, check_rc, d_out, nullptr, s);
-    HIP_CHECK(hipFreeAsync(expanded, s));
 }
 
 void engine::neighbours_packed_host(uint64_t const* h_kmers, uint64_t n, bool check_rc, out_mode mode,
@@ -1452,27 +1432,6 @@ check_compare_kernel(const uint64_t* __restrict__ ids, const uint8_t* __restrict
     }
 }
 
-namespace {
-/* freed on every way out of check_device. The call runs on a stream of its own, so that it does not serialise with the other
-   work of the process on the device, as the null stream would; the lookup scratch the replica keyed by that stream
-   (device_replica::scratch_for) is handed back before the stream is destroyed. */
-struct check_scratch {
-    device_replica const* rep;
-    void* p[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipStream_t s = nullptr;
-    explicit check_scratch(device_replica const* r) : rep(r) {}
-    ~check_scratch() {
-        if (s) (void)hipStreamSynchronize(s);
-        for (void* q : p)
-            if (q) (void)hipFree(q);
-        if (s) {
-            rep->release_stream_scratch(s);
-            (void)hipStreamDestroy(s);
-        }
-    }
-};
-}  // namespace
-
 void engine::check_device(int device, uint64_t out[8]) const {
     if (m_idx->num_shards > 1)
         throw error(error_kind::argument, "check: a minimizer shard answers only the k-mers it owns (check the whole index)");
@@ -1481,16 +1440,14 @@ void engine::check_device(int device, uint64_t out[8]) const {
     const uint64_t n = rep->view.num_kmers;
     const uint32_t W = rep->view.k <= 31 ? 1 : 2;
     const uint64_t chunk = std::min(n, CHECK_CHUNK);
-    check_scratch x(rep);
-    HIP_CHECK(hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking));
-    HIP_CHECK(hipMalloc(&x.p[0], chunk * W * sizeof(uint64_t)));
-    HIP_CHECK(hipMalloc(&x.p[1], chunk * sizeof(uint64_t)));
-    HIP_CHECK(hipMalloc(&x.p[2], chunk));
-    HIP_CHECK(hipMalloc(&x.p[3], 8 * sizeof(uint64_t)));
-    uint64_t* d_kmers = static_cast<uint64_t*>(x.p[0]);
-    uint64_t* d_ids = static_cast<uint64_t*>(x.p[1]);
-    uint8_t* d_member = static_cast<uint8_t*>(x.p[2]);
-    unsigned long long* d_counts = static_cast<unsigned long long*>(x.p[3]);
+    /* The call runs on a stream of its own, so that it does not serialise with the other work of the process on the device, as
+       the null stream would (declared after `tmp`: it is drained and handed back before the buffers are freed). */
+    device_buffers tmp;
+    const own_stream x(rep);
+    uint64_t* d_kmers = tmp.alloc<uint64_t>(chunk * W);
+    uint64_t* d_ids = tmp.alloc<uint64_t>(chunk);
+    uint8_t* d_member = tmp.alloc<uint8_t>(chunk);
+    unsigned long long* d_counts = tmp.alloc<unsigned long long>(8);
     HIP_CHECK(hipMemsetAsync(d_counts, 0, 8 * sizeof(uint64_t), x.s));
     HIP_CHECK(hipMemsetAsync(d_counts + CHECK_FIRST_FAILURE, 0xFF, sizeof(uint64_t), x.s));
 
@@ -1532,39 +1489,6 @@ constexpr uint32_t HOST_LANES_MAX = 8;
 
 uint64_t align256(uint64_t x) { return (x + 255) & ~uint64_t(255); }
 
-struct field_plan {  // where each output of a chunk lives inside the staging block
-    uint64_t in_bytes = 0, out_bytes = 0;
-    uint64_t at[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // sshash_results order; member shares slot 0
-    bool wanted[8] = {false, false, false, false, false, false, false, false};
-};
-
-field_plan plan_fields(out_mode mode, result_view const& h_out, uint64_t chunk, uint64_t bytes_per_query) {
-    field_plan p;
-    p.in_bytes = align256(chunk * bytes_per_query);
-    uint64_t at = 0;
-    auto add = [&](int f, bool wanted, uint64_t width) {
-        p.wanted[f] = wanted;
-        if (!wanted) return;
-        p.at[f] = at;
-        at += align256(chunk * width);
-    };
-    if (mode == out_mode::member) {
-        add(0, true, 1);
-    } else {
-        add(0, true, 8);
-        const bool full = mode == out_mode::full;
-        add(1, full && h_out.kmer_id_in_string, 8);
-        add(2, full && h_out.kmer_offset, 8);
-        add(3, full && h_out.string_id, 8);
-        add(4, full && h_out.string_begin, 8);
-        add(5, full && h_out.string_end, 8);
-        add(6, full && h_out.kmer_orientation, 1);
-        add(7, full && h_out.minimizer_found, 1);
-    }
-    p.out_bytes = at;
-    return p;
-}
-
 }  // namespace
 
 host_lane* device_replica::acquire_lane(size_t bytes) const {
@@ -1601,33 +1525,80 @@ void device_replica::release_lane(host_lane* lane) const {
     idle_lanes.push_back(lane);
 }
 
+std::vector<int> resident_devices(engine const& eng) {
+    std::vector<int> devs = eng.devices();
+    if (devs.empty()) throw error(error_kind::no_device, "dictionary is not resident on any device (call sshash_to_device first)");
+    return devs;
+}
+
+void run_lanes(engine const& eng, std::vector<int> const& devices, size_t bytes, std::function<void(size_t, int, host_lane&)> const& fn,
+               std::atomic<bool>* failed) {
+    std::vector<std::exception_ptr> errors(devices.size());
+    auto run_lane = [&](size_t li) {
+        try {
+            device_replica const* rep = eng.replica(devices[li]);
+            HIP_CHECK(hipSetDevice(devices[li]));
+            host_lane* lane = rep->acquire_lane(bytes);
+            try {
+                fn(li, devices[li], *lane);
+            } catch (...) {
+                rep->release_lane(lane);
+                throw;
+            }
+            rep->release_lane(lane);
+        } catch (...) {
+            errors[li] = std::current_exception();
+            if (failed) *failed = true;
+        }
+    };
+    int prev = 0;
+    HIP_CHECK(hipGetDevice(&prev));
+    if (devices.size() == 1) {
+        run_lane(0);  // (a small batch on one device: no thread at all)
+    } else {
+        std::vector<std::thread> workers;
+        for (size_t li = 0; li < devices.size(); ++li) workers.emplace_back(run_lane, li);
+        for (auto& w : workers) w.join();
+    }
+    (void)hipSetDevice(prev);
+    for (auto const& e : errors)
+        if (e) std::rethrow_exception(e);
+}
+
 template <bool ASCII>
-static void host_lookup(engine const& eng, std::vector<int> const& devs, void const* h_in, uint64_t bytes_per_query,
-                        uint64_t n, bool check_rc, out_mode mode, result_view const& h_out, uint8_t* h_member) {
+static void host_lookup(engine const& eng, void const* h_in, uint64_t bytes_per_query, uint64_t n, bool check_rc, out_mode mode,
+                        result_view const& h_out, uint8_t* h_member) {
     check_outputs(mode, h_out, h_member);
     if (n == 0) return;
-    if (devs.empty()) throw error(error_kind::no_device, "dictionary is not resident on any device (call sshash_to_device first)");
+    const std::vector<int> devs = resident_devices(eng);
     const uint64_t G = devs.size();
     const uint64_t chunk = std::min<uint64_t>(test_hook_u64("host_chunk", HOST_CHUNK, 1024, uint64_t(1) << 26), n);
     const uint64_t max_lanes = test_hook_u64("host_lanes", HOST_LANES_MAX, 1, 64);
-    const field_plan plan = plan_fields(mode, h_out, chunk, bytes_per_query);
     const uint64_t hw = std::max(1u, std::thread::hardware_concurrency());
+    /* the arrays the call fills: h_member, or kmer_id and -- in full mode -- every other one the caller passed */
+    uint8_t* const member = mode == out_mode::member ? h_member : nullptr;
+    result_view want{};
+    if (mode == out_mode::full) want = h_out;
+    else if (mode == out_mode::ids) want.kmer_id = h_out.kmer_id;
 
     struct share {  // one per device: its slice of the batch, handed out chunk by chunk
         uint64_t lo = 0, hi = 0;
         std::atomic<uint64_t> next{0};
     };
     std::vector<share> shares(G);
-    std::vector<std::pair<uint64_t, uint32_t>> lanes;  // (device index, lane index)
+    std::vector<int> lane_devs;
+    std::vector<uint64_t> lane_share;
     for (uint64_t g = 0; g < G; ++g) {
         shares[g].lo = n * g / G;
         shares[g].hi = n * (g + 1) / G;
         shares[g].next = shares[g].lo;
         const uint64_t chunks = (shares[g].hi - shares[g].lo + chunk - 1) / chunk;
-        const uint64_t want = std::min<uint64_t>({chunks, max_lanes, std::max<uint64_t>(1, hw / G)});
-        for (uint32_t l = 0; l < want; ++l) lanes.emplace_back(g, l);
+        const uint64_t want_lanes = std::min<uint64_t>({chunks, max_lanes, std::max<uint64_t>(1, hw / G)});
+        for (uint32_t l = 0; l < want_lanes; ++l) {
+            lane_devs.push_back(devs[g]);
+            lane_share.push_back(g);
+        }
     }
-    std::vector<std::exception_ptr> errors(lanes.size());
 
     /* Caller buffers that are page-locked already (hipHostMalloc / hipHostRegister; first and last byte checked) are
        copied from and to directly: the staging copies through this library's own pinned lanes are what bounds the
@@ -1644,13 +1615,8 @@ static void host_lookup(engine const& eng, std::vector<int> const& devs, void co
         }
         return true;
     };
-    bool in_place = pinned(h_in, n * bytes_per_query);
-    if (mode == out_mode::member) in_place = in_place && pinned(h_member, n);
-    else
-        in_place = in_place && pinned(h_out.kmer_id, n * 8) && (!plan.wanted[1] || pinned(h_out.kmer_id_in_string, n * 8)) &&
-                   (!plan.wanted[2] || pinned(h_out.kmer_offset, n * 8)) && (!plan.wanted[3] || pinned(h_out.string_id, n * 8)) &&
-                   (!plan.wanted[4] || pinned(h_out.string_begin, n * 8)) && (!plan.wanted[5] || pinned(h_out.string_end, n * 8)) &&
-                   (!plan.wanted[6] || pinned(h_out.kmer_orientation, n)) && (!plan.wanted[7] || pinned(h_out.minimizer_found, n));
+    bool in_place = pinned(h_in, n * bytes_per_query) && pinned(member, n);
+    for_each_field([&](int, auto* h, uint64_t width) { in_place = in_place && pinned(h, n * width); }, want);
 
     /* Page-locked caller arrays that the devices can address (hipHostMalloc'ed, or registered with hipHostRegisterMapped): the KERNELS read
        the queries and write the results where they lie -- no copy engine, no staging block, no chunk. A copy pipeline moves a chunk in,
@@ -1667,10 +1633,8 @@ static void host_lookup(engine const& eng, std::vector<int> const& devs, void co
         };
         std::vector<mapped_share> mapped(G);
         bool all_mapped = true;
-        int before = 0;
-        HIP_CHECK(hipGetDevice(&before));
         for (uint64_t g = 0; g < G && all_mapped; ++g) {
-            HIP_CHECK(hipSetDevice(devs[g]));
+            device_guard on(devs[g]);
             auto device_address = [&](auto* p) -> decltype(p) {
                 if (!p) return nullptr;
                 void* dptr = nullptr;
@@ -1684,157 +1648,90 @@ static void host_lookup(engine const& eng, std::vector<int> const& devs, void co
             const uint64_t lo = shares[g].lo;
             mapped_share& ms = mapped[g];
             if (char const* in = device_address(static_cast<char const*>(h_in))) ms.in = in + lo * bytes_per_query;
-            if (mode == out_mode::member) {
-                if (uint8_t* q = device_address(h_member)) ms.member = q + lo;
-            } else {
-                auto place = [&](auto* host, bool wanted) -> decltype(host) {
-                    if (!wanted) return nullptr;
-                    auto* q = device_address(host);
-                    return q ? q + lo : nullptr;
-                };
-                ms.out.kmer_id = place(h_out.kmer_id, true);
-                ms.out.kmer_id_in_string = place(h_out.kmer_id_in_string, plan.wanted[1]);
-                ms.out.kmer_offset = place(h_out.kmer_offset, plan.wanted[2]);
-                ms.out.string_id = place(h_out.string_id, plan.wanted[3]);
-                ms.out.string_begin = place(h_out.string_begin, plan.wanted[4]);
-                ms.out.string_end = place(h_out.string_end, plan.wanted[5]);
-                ms.out.kmer_orientation = place(h_out.kmer_orientation, plan.wanted[6]);
-                ms.out.minimizer_found = place(h_out.minimizer_found, plan.wanted[7]);
-            }
+            if (uint8_t* q = device_address(member)) ms.member = q + lo;
+            for_each_field([&](int, auto* h, auto*& d, uint64_t) {
+                if (auto* q = device_address(h)) d = q + lo;
+            }, want, ms.out);
         }
-        (void)hipSetDevice(before);
         if (all_mapped) {
-            std::vector<std::exception_ptr> failed(G);
-            auto run_device = [&](uint64_t g) {
-                try {
-                    const uint64_t m = shares[g].hi - shares[g].lo;
-                    if (m == 0) return;
-                    device_replica const* rep = eng.replica(devs[g]);
-                    HIP_CHECK(hipSetDevice(devs[g]));
-                    host_lane* lane = rep->acquire_lane(0);  // (for its stream)
-                    struct give_back {
-                        device_replica const* rep;
-                        host_lane* lane;
-                        ~give_back() { rep->release_lane(lane); }
-                    } guard{rep, lane};
-                    mapped_share const& ms = mapped[g];
-                    if (ASCII) eng.lookup_ascii_device(devs[g], static_cast<char const*>(ms.in), m, check_rc, mode, ms.out, ms.member, lane->stream);
-                    else eng.lookup_packed_device(devs[g], static_cast<uint64_t const*>(ms.in), m, check_rc, mode, ms.out, ms.member, lane->stream);
-                    HIP_CHECK(hipStreamSynchronize(lane->stream));
-                } catch (...) { failed[g] = std::current_exception(); }
-            };
-            if (G == 1) {
-                run_device(0);
-            } else {
-                std::vector<std::thread> workers;
-                for (uint64_t g = 0; g < G; ++g) workers.emplace_back(run_device, g);
-                for (auto& w : workers) w.join();
-            }
-            (void)hipSetDevice(before);
-            for (auto const& e : failed)
-                if (e) std::rethrow_exception(e);
+            std::vector<uint64_t> busy;  // the devices with a share of the batch: a lane each, for its stream
+            std::vector<int> busy_devs;
+            for (uint64_t g = 0; g < G; ++g)
+                if (shares[g].hi > shares[g].lo) {
+                    busy.push_back(g);
+                    busy_devs.push_back(devs[g]);
+                }
+            run_lanes(eng, busy_devs, 0, [&](size_t li, int device, host_lane& lane) {
+                const uint64_t g = busy[li], m = shares[g].hi - shares[g].lo;
+                mapped_share const& ms = mapped[g];
+                if (ASCII) eng.lookup_ascii_device(device, static_cast<char const*>(ms.in), m, check_rc, mode, ms.out, ms.member, lane.stream);
+                else eng.lookup_packed_device(device, static_cast<uint64_t const*>(ms.in), m, check_rc, mode, ms.out, ms.member, lane.stream);
+                HIP_CHECK(hipStreamSynchronize(lane.stream));
+            });
             return;
         }
     }
 
-    auto run_lane = [&](size_t li) {
-        try {
-            const uint64_t g = lanes[li].first;
-            device_replica const* rep = eng.replica(devs[g]);
-            HIP_CHECK(hipSetDevice(devs[g]));
-            host_lane* lane = rep->acquire_lane(plan.in_bytes + plan.out_bytes);
-            struct give_back {
-                device_replica const* rep;
-                host_lane* lane;
-                ~give_back() { rep->release_lane(lane); }
-            } guard{rep, lane};
-            hipStream_t s = lane->stream;
-            char* hp = static_cast<char*>(lane->pinned);
-            char* dp = static_cast<char*>(lane->device);
-            char* h_out_block = hp + plan.in_bytes;
-            char* d_out_block = dp + plan.in_bytes;
-            result_view d_out{};
-            uint8_t* d_member = nullptr;
-            if (mode == out_mode::member) d_member = reinterpret_cast<uint8_t*>(d_out_block + plan.at[0]);
-            else {
-                d_out.kmer_id = reinterpret_cast<uint64_t*>(d_out_block + plan.at[0]);
-                if (plan.wanted[1]) d_out.kmer_id_in_string = reinterpret_cast<uint64_t*>(d_out_block + plan.at[1]);
-                if (plan.wanted[2]) d_out.kmer_offset = reinterpret_cast<uint64_t*>(d_out_block + plan.at[2]);
-                if (plan.wanted[3]) d_out.string_id = reinterpret_cast<uint64_t*>(d_out_block + plan.at[3]);
-                if (plan.wanted[4]) d_out.string_begin = reinterpret_cast<uint64_t*>(d_out_block + plan.at[4]);
-                if (plan.wanted[5]) d_out.string_end = reinterpret_cast<uint64_t*>(d_out_block + plan.at[5]);
-                if (plan.wanted[6]) d_out.kmer_orientation = reinterpret_cast<int8_t*>(d_out_block + plan.at[6]);
-                if (plan.wanted[7]) d_out.minimizer_found = reinterpret_cast<uint8_t*>(d_out_block + plan.at[7]);
-            }
-            for (;;) {
-                const uint64_t at = shares[g].next.fetch_add(chunk);
-                if (at >= shares[g].hi) break;
-                const uint64_t m = std::min(chunk, shares[g].hi - at);
-                if (in_place) {
-                    HIP_CHECK(hipMemcpyAsync(dp, static_cast<char const*>(h_in) + at * bytes_per_query, m * bytes_per_query, hipMemcpyHostToDevice, s));
-                } else {
-                    std::memcpy(hp, static_cast<char const*>(h_in) + at * bytes_per_query, m * bytes_per_query);
-                    HIP_CHECK(hipMemcpyAsync(dp, hp, m * bytes_per_query, hipMemcpyHostToDevice, s));
-                }
-                if (ASCII) eng.lookup_ascii_device(devs[g], dp, m, check_rc, mode, d_out, d_member, s);
-                else eng.lookup_packed_device(devs[g], reinterpret_cast<uint64_t const*>(dp), m, check_rc, mode, d_out, d_member, s);
-                if (in_place) {
-                    auto back = [&](void* dst, int f, uint64_t width) {
-                        HIP_CHECK(hipMemcpyAsync(static_cast<char*>(dst) + at * width, d_out_block + plan.at[f], m * width, hipMemcpyDeviceToHost, s));
-                    };
-                    if (mode == out_mode::member) back(h_member, 0, 1);
-                    else {
-                        back(h_out.kmer_id, 0, 8);
-                        if (plan.wanted[1]) back(h_out.kmer_id_in_string, 1, 8);
-                        if (plan.wanted[2]) back(h_out.kmer_offset, 2, 8);
-                        if (plan.wanted[3]) back(h_out.string_id, 3, 8);
-                        if (plan.wanted[4]) back(h_out.string_begin, 4, 8);
-                        if (plan.wanted[5]) back(h_out.string_end, 5, 8);
-                        if (plan.wanted[6]) back(h_out.kmer_orientation, 6, 1);
-                        if (plan.wanted[7]) back(h_out.minimizer_found, 7, 1);
-                    }
-                    HIP_CHECK(hipStreamSynchronize(s));
-                    continue;
-                }
-                HIP_CHECK(hipMemcpyAsync(h_out_block, d_out_block, plan.out_bytes, hipMemcpyDeviceToHost, s));
-                HIP_CHECK(hipStreamSynchronize(s));
-                if (mode == out_mode::member) std::memcpy(h_member + at, h_out_block + plan.at[0], m);
-                else {
-                    std::memcpy(h_out.kmer_id + at, h_out_block + plan.at[0], m * 8);
-                    if (plan.wanted[1]) std::memcpy(h_out.kmer_id_in_string + at, h_out_block + plan.at[1], m * 8);
-                    if (plan.wanted[2]) std::memcpy(h_out.kmer_offset + at, h_out_block + plan.at[2], m * 8);
-                    if (plan.wanted[3]) std::memcpy(h_out.string_id + at, h_out_block + plan.at[3], m * 8);
-                    if (plan.wanted[4]) std::memcpy(h_out.string_begin + at, h_out_block + plan.at[4], m * 8);
-                    if (plan.wanted[5]) std::memcpy(h_out.string_end + at, h_out_block + plan.at[5], m * 8);
-                    if (plan.wanted[6]) std::memcpy(h_out.kmer_orientation + at, h_out_block + plan.at[6], m);
-                    if (plan.wanted[7]) std::memcpy(h_out.minimizer_found + at, h_out_block + plan.at[7], m);
-                }
-            }
-        } catch (...) { errors[li] = std::current_exception(); }
+    /* where a chunk's outputs lie in a lane's staging block (behind its queries): one behind the other, h_member alone at the front */
+    const uint64_t in_bytes = align256(chunk * bytes_per_query);
+    uint64_t out_bytes = member ? align256(chunk) : 0;
+    for_each_field([&](int, auto* h, uint64_t width) { out_bytes += h ? align256(chunk * width) : 0; }, want);
+    auto staged = [&](char* block) {
+        result_view v{};
+        for_each_field([&](int, auto* h, auto*& p, uint64_t width) {
+            if (!h) return;
+            p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(block);
+            block += align256(chunk * width);
+        }, want, v);
+        return v;
     };
-
-    int prev = 0;
-    HIP_CHECK(hipGetDevice(&prev));
-    if (lanes.size() == 1) {
-        run_lane(0);  // small batch on one device: no thread at all
-    } else {
-        std::vector<std::thread> workers;
-        for (size_t li = 0; li < lanes.size(); ++li) workers.emplace_back(run_lane, li);
-        for (auto& w : workers) w.join();
-    }
-    (void)hipSetDevice(prev);
-    for (auto const& e : errors)
-        if (e) std::rethrow_exception(e);
+    run_lanes(eng, lane_devs, in_bytes + out_bytes, [&](size_t li, int device, host_lane& lane) {
+        share& sh = shares[lane_share[li]];
+        hipStream_t s = lane.stream;
+        char* hp = static_cast<char*>(lane.pinned);
+        char* dp = static_cast<char*>(lane.device);
+        char* h_out_block = hp + in_bytes;
+        char* d_out_block = dp + in_bytes;
+        const result_view h_stage = staged(h_out_block), d_out = staged(d_out_block);
+        uint8_t* d_member = member ? reinterpret_cast<uint8_t*>(d_out_block) : nullptr;
+        for (;;) {
+            const uint64_t at = sh.next.fetch_add(chunk);
+            if (at >= sh.hi) break;
+            const uint64_t m = std::min(chunk, sh.hi - at);
+            if (in_place) {
+                HIP_CHECK(hipMemcpyAsync(dp, static_cast<char const*>(h_in) + at * bytes_per_query, m * bytes_per_query, hipMemcpyHostToDevice, s));
+            } else {
+                std::memcpy(hp, static_cast<char const*>(h_in) + at * bytes_per_query, m * bytes_per_query);
+                HIP_CHECK(hipMemcpyAsync(dp, hp, m * bytes_per_query, hipMemcpyHostToDevice, s));
+            }
+            if (ASCII) eng.lookup_ascii_device(device, dp, m, check_rc, mode, d_out, d_member, s);
+            else eng.lookup_packed_device(device, reinterpret_cast<uint64_t const*>(dp), m, check_rc, mode, d_out, d_member, s);
+            if (in_place) {
+                if (member) HIP_CHECK(hipMemcpyAsync(member + at, d_member, m, hipMemcpyDeviceToHost, s));
+                for_each_field([&](int, auto* h, auto* d, uint64_t width) {
+                    if (h) HIP_CHECK(hipMemcpyAsync(h + at, d, m * width, hipMemcpyDeviceToHost, s));
+                }, want, d_out);
+                HIP_CHECK(hipStreamSynchronize(s));
+                continue;
+            }
+            HIP_CHECK(hipMemcpyAsync(h_out_block, d_out_block, out_bytes, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            if (member) std::memcpy(member + at, h_out_block, m);
+            for_each_field([&](int, auto* h, auto* staged_h, uint64_t width) {
+                if (h) std::memcpy(h + at, staged_h, m * width);
+            }, want, h_stage);
+        }
+    });
 }
 
 void engine::lookup_packed_host(uint64_t const* h_kmers, uint64_t n, bool check_rc, out_mode mode,
                                 result_view const& h_out, uint8_t* h_member) const {
-    host_lookup<false>(*this, devices(), h_kmers, 8ull * m_idx->words_per_kmer(), n, check_rc, mode, h_out, h_member);
+    host_lookup<false>(*this, h_kmers, 8ull * m_idx->words_per_kmer(), n, check_rc, mode, h_out, h_member);
 }
 
 void engine::lookup_ascii_host(char const* h_kmers, uint64_t n, bool check_rc, out_mode mode, result_view const& h_out,
                                uint8_t* h_member) const {
-    host_lookup<true>(*this, devices(), h_kmers, m_idx->k, n, check_rc, mode, h_out, h_member);
+    host_lookup<true>(*this, h_kmers, m_idx->k, n, check_rc, mode, h_out, h_member);
 }
 
 }  // namespace sshash_amd

@@ -27,6 +27,17 @@ struct exchange_ops {
 struct streaming_report {  // streaming_query_report, include/util.hpp:21-36
     uint64_t num_kmers = 0, num_positive_kmers = 0, num_negative_kmers = 0, num_invalid_kmers = 0,
              num_searches = 0, num_extensions = 0;
+    /* the six counters as the device accumulates them (streaming_query_device: d_report), in this order */
+    static streaming_report from_device(uint64_t const words[6]) { return {words[0], words[1], words[2], words[3], words[4], words[5]}; }
+    streaming_report& operator+=(streaming_report const& o) {
+        num_kmers += o.num_kmers;
+        num_positive_kmers += o.num_positive_kmers;
+        num_negative_kmers += o.num_negative_kmers;
+        num_invalid_kmers += o.num_invalid_kmers;
+        num_searches += o.num_searches;
+        num_extensions += o.num_extensions;
+        return *this;
+    }
 };
 
 class engine {

@@ -1,6 +1,7 @@
 // replica.hpp -- one dictionary replica resident in the HBM of one device (internal header).
 #pragma once
 
+#include <algorithm>
 #include <atomic>
 
 #include <cstdio>
@@ -8,6 +9,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <mutex>
 #include <stdexcept>
 #include <string>
@@ -42,6 +44,75 @@ struct host_lane {
     void* pinned = nullptr;
     void* device = nullptr;
     size_t capacity = 0;
+};
+
+/* a device block kept for one stream (stream_cache): free_block() before it grows, release() when the stream gives it up */
+struct stream_block {
+    void* block = nullptr;
+    size_t bytes = 0;
+    void free_block() {
+        if (block) HIP_CHECK(hipFree(block));  // (synchronises: nothing in flight still uses it)
+        block = nullptr;
+        bytes = 0;
+    }
+    void release() {
+        if (block) (void)hipFree(block);
+        block = nullptr;
+        bytes = 0;
+    }
+};
+
+/* Device blocks keyed by stream. Work on one stream is ordered, so its block is reused without synchronisation; a block only
+   grows (hipFree of the old block synchronises implicitly). Once more than MAX_STREAMS streams or MAX_BYTES bytes would be
+   held, the least recently used blocks other than the one being grown go first. Slot: a stream_block, or one with more to
+   wait for before its block is freed, or more to release. */
+template <typename Slot, size_t MAX_STREAMS, size_t MAX_BYTES>
+class stream_cache {
+public:
+    /* the slot of `stream`, its block at least `bytes` (grown with 1/headroom to spare) */
+    Slot& get(void* stream, size_t bytes, size_t headroom) {
+        std::lock_guard<std::mutex> lock(m_mutex);
+        auto it = m_slots.try_emplace(stream).first;
+        it->second.last_use = ++m_clock;
+        Slot& slot = it->second.slot;
+        if (slot.bytes >= bytes) return slot;
+        slot.free_block();
+        const size_t want = bytes + bytes / headroom + 4096;
+        size_t held = want;
+        for (auto const& kv : m_slots) held += kv.second.slot.bytes;
+        while (m_slots.size() > 1 && (m_slots.size() > MAX_STREAMS || held > MAX_BYTES)) {
+            auto oldest = m_slots.end();
+            for (auto jt = m_slots.begin(); jt != m_slots.end(); ++jt)
+                if (jt != it && (oldest == m_slots.end() || jt->second.last_use < oldest->second.last_use)) oldest = jt;
+            held -= oldest->second.slot.bytes;
+            oldest->second.slot.release();
+            m_slots.erase(oldest);
+        }
+        HIP_CHECK(hipMalloc(&slot.block, want));
+        slot.bytes = want;
+        return slot;
+    }
+    void release(void* stream) {
+        std::lock_guard<std::mutex> lock(m_mutex);
+        auto it = m_slots.find(stream);
+        if (it == m_slots.end()) return;
+        it->second.slot.release();
+        m_slots.erase(it);
+    }
+    void clear() {
+        std::lock_guard<std::mutex> lock(m_mutex);
+        for (auto& kv : m_slots) kv.second.slot.release();
+        m_slots.clear();
+    }
+
+private:
+    struct entry {
+        Slot slot;
+        uint64_t last_use = 0;
+    };
+    std::mutex m_mutex;
+    std::unordered_map<void*, entry> m_slots;
+    uint64_t m_clock = 0;
 };
 
 struct device_replica {
@@ -89,22 +160,23 @@ struct device_replica {
         return p;
     }
 
-    /* Per-stream scratch for the resume and deferred queues of the multi-pass lookup (engine.hip). Work on one stream is
-       ordered, so a buffer keyed by the stream can be reused without synchronisation; it only grows
-       (hipFree of the old block synchronises implicitly). At most SCRATCH_STREAMS_MAX streams keep a block. */
-    /* held while one launch sequence (queue reset, first / resume / deferred pass) is enqueued: two host threads that share a
-       stream (the null stream, typically) must not interleave their sequences, which share that stream's scratch */
+    /* held while one launch sequence (queue reset, first / resume / deferred pass; the streaming runs) is enqueued: two host
+       threads that share a stream (the null stream, typically) must not interleave their sequences, which share that stream's
+       scratch below */
     mutable std::mutex launch_mutex;
-    mutable std::mutex scratch_mutex;
-    struct stream_scratch {
-        void* block = nullptr;
-        size_t bytes = 0;
-        uint64_t last_use = 0;
+    /* Per-stream scratch (stream_cache) for the resume and deferred queues of the multi-pass lookup (engine.hip). At most 16
+       streams keep a block: an application that makes a stream per request must not keep a gigabyte of queues per stream it
+       ever used. */
+    struct stream_scratch : stream_block {
         /* the tail passes (resume, deferred) of one launch piece run on `aux` while the caller's stream already runs the
            first pass of the next piece (engine.hip: launch): one auxiliary stream and two event pairs per caller stream */
         hipStream_t aux = nullptr;
         hipEvent_t first_done[2] = {nullptr, nullptr};
         hipEvent_t tail_done[2] = {nullptr, nullptr};
+        void free_block() {
+            if (aux) HIP_CHECK(hipStreamSynchronize(aux));  // a tail pass of an earlier call may still read the block
+            stream_block::free_block();
+        }
         void release() {
             if (aux) (void)hipStreamSynchronize(aux);
             for (int i = 0; i < 2; ++i) {
@@ -114,40 +186,18 @@ struct device_replica {
             }
             if (aux) (void)hipStreamDestroy(aux);
             aux = nullptr;
-            if (block) (void)hipFree(block);
-            block = nullptr;
-            bytes = 0;
+            stream_block::release();
         }
     };
-    mutable std::unordered_map<void*, stream_scratch> scratch;
-    mutable uint64_t scratch_clock = 0;
-    static constexpr size_t SCRATCH_STREAMS_MAX = 16;  // an application that makes a stream per request must not keep a
-                                                       // gigabyte of queues per stream it ever used: the
-                                                       // least recently used stream's block goes first
+    mutable stream_cache<stream_scratch, 16, ~size_t(0)> queue_scratch;
+    /* Per-stream scratch of the streaming query (streaming.hip: the 2-bit packed copy of a call's reads and their validity bits).
+       Round 5 took it from the pool above and gave it back at every call -- two stream-ordered allocations of ~0.4 GB each per call
+       of 3 x 10^9 bases, on the host side of a step that the device then waits for (profiles/r06/). Kept per stream instead, for
+       at most 64 streams (the file query runs up to 32 lanes, each on its own stream) and 8 GiB. */
+    mutable stream_cache<stream_block, 64, size_t(8) << 30> read_scratch;
+    /* (the caller holds launch_mutex: the slot, its aux stream and its events are used outside the cache's own lock) */
     stream_scratch& scratch_for(void* stream, size_t bytes, bool with_aux_stream) const {
-        std::lock_guard<std::mutex> lock(scratch_mutex);
-        auto it = scratch.find(stream);
-        if (it == scratch.end()) {
-            if (scratch.size() >= SCRATCH_STREAMS_MAX) {
-                auto oldest = scratch.begin();
-                for (auto jt = scratch.begin(); jt != scratch.end(); ++jt)
-                    if (jt->second.last_use < oldest->second.last_use) oldest = jt;
-                oldest->second.release();  // (synchronises: nothing in flight still uses it)
-                scratch.erase(oldest);
-            }
-            it = scratch.emplace(stream, stream_scratch{}).first;
-        }
-        stream_scratch& slot = it->second;
-        slot.last_use = ++scratch_clock;
-        if (slot.bytes < bytes) {
-            if (slot.aux) HIP_CHECK(hipStreamSynchronize(slot.aux));  // a tail pass of an earlier call may still read the old block
-            if (slot.block) HIP_CHECK(hipFree(slot.block));
-            slot.block = nullptr;
-            slot.bytes = 0;
-            const size_t want = bytes + bytes / 4 + 4096;
-            HIP_CHECK(hipMalloc(&slot.block, want));
-            slot.bytes = want;
-        }
+        stream_scratch& slot = queue_scratch.get(stream, bytes, 4);
         if (with_aux_stream && !slot.aux) {
             HIP_CHECK(hipStreamCreateWithFlags(&slot.aux, hipStreamNonBlocking));
             for (int i = 0; i < 2; ++i) {
@@ -157,57 +207,13 @@ struct device_replica {
         }
         return slot;
     }
+    void* read_scratch_for(void* stream, size_t bytes) const { return read_scratch.get(stream, bytes, 8).block; }
 
     /* Hand back the scratch of a stream that its owner is about to destroy (the work on it must be complete): a call that makes a
-       stream of its own for its duration (engine::check_device) leaves no block behind. */
+       stream of its own for its duration (own_stream) leaves no block behind. */
     void release_stream_scratch(void* stream) const {
-        std::lock_guard<std::mutex> lock(scratch_mutex);
-        auto it = scratch.find(stream);
-        if (it == scratch.end()) return;
-        it->second.release();
-        scratch.erase(it);
-    }
-
-    /* Per-stream scratch of the streaming query (streaming.hip: the 2-bit packed copy of a call's reads and their validity bits).
-       Round 5 took it from the pool above and gave it back at every call -- two stream-ordered allocations of ~0.4 GB each per call
-       of 3 x 10^9 bases, on the host side of a step that the device then waits for (profiles/r06/). Kept per stream instead: calls
-       on one stream are ordered, so the block is reused without synchronisation and only grows (hipFree of the old block
-       synchronises). An application that makes a stream per request does not keep a block per stream it ever used: the least
-       recently used ones go once more than READ_SCRATCH_STREAMS_MAX streams or READ_SCRATCH_BYTES_MAX bytes are held. */
-    struct read_scratch {
-        void* block = nullptr;
-        size_t bytes = 0;
-        uint64_t last_use = 0;
-    };
-    mutable std::unordered_map<void*, read_scratch> read_scratches;
-    static constexpr size_t READ_SCRATCH_STREAMS_MAX = 64;  // (the file query runs up to 32 lanes, each on its own stream)
-    static constexpr size_t READ_SCRATCH_BYTES_MAX = size_t(8) << 30;
-    void* read_scratch_for(void* stream, size_t bytes) const {
-        std::lock_guard<std::mutex> lock(scratch_mutex);
-        auto it = read_scratches.find(stream);
-        if (it == read_scratches.end()) it = read_scratches.emplace(stream, read_scratch{}).first;
-        read_scratch& slot = it->second;
-        slot.last_use = ++scratch_clock;
-        if (slot.bytes < bytes) {
-            if (slot.block) HIP_CHECK(hipFree(slot.block));  // (synchronises: nothing in flight still reads it)
-            slot.block = nullptr;
-            slot.bytes = 0;
-            const size_t want = bytes + bytes / 8 + 4096;
-            size_t held = want;
-            for (auto const& kv : read_scratches) held += kv.second.bytes;
-            while (read_scratches.size() > 1 && (read_scratches.size() > READ_SCRATCH_STREAMS_MAX || held > READ_SCRATCH_BYTES_MAX)) {
-                auto oldest = read_scratches.end();
-                for (auto jt = read_scratches.begin(); jt != read_scratches.end(); ++jt)
-                    if (jt != it && (oldest == read_scratches.end() || jt->second.last_use < oldest->second.last_use)) oldest = jt;
-                if (oldest == read_scratches.end()) break;
-                if (oldest->second.block) (void)hipFree(oldest->second.block);
-                held -= oldest->second.bytes;
-                read_scratches.erase(oldest);
-            }
-            HIP_CHECK(hipMalloc(&slot.block, want));
-            slot.bytes = want;
-        }
-        return slot.block;
+        queue_scratch.release(stream);
+        read_scratch.release(stream);
     }
 
     /* pooled lanes of the host-buffer path */
@@ -246,9 +252,8 @@ struct device_replica {
             (void)hipDeviceSynchronize();  // (stream-ordered frees of this pool must have run)
             (void)hipMemPoolDestroy(scratch_pool);
         }
-        for (auto& kv : scratch) kv.second.release();
-        for (auto& kv : read_scratches)
-            if (kv.second.block) (void)hipFree(kv.second.block);
+        queue_scratch.clear();
+        read_scratch.clear();
         for (host_lane* lane : idle_lanes) {
             if (lane->pinned) (void)hipHostFree(lane->pinned);
             if (lane->device) (void)hipFree(lane->device);
@@ -258,5 +263,80 @@ struct device_replica {
         (void)hipSetDevice(prev);
     }
 };
+
+/* A stream that a call makes for its own duration (engine::check_device, engine::streaming_lookup_host): on every way out it is
+   drained, the scratch the replica keyed by it is handed back and it is destroyed. */
+struct own_stream {
+    device_replica const* rep;
+    hipStream_t s = nullptr;
+    explicit own_stream(device_replica const* r) : rep(r) { HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+    own_stream(own_stream const&) = delete;
+    own_stream& operator=(own_stream const&) = delete;
+    ~own_stream() {
+        (void)hipStreamSynchronize(s);
+        rep->release_stream_scratch(s);
+        (void)hipStreamDestroy(s);
+    }
+};
+
+/* Device buffers freed on every way out of their scope: hipMalloc'ed and freed with hipFree, or -- given a replica and a stream --
+   stream-ordered out of the replica's pool and freed with hipFreeAsync on that stream. */
+class device_buffers {
+public:
+    device_buffers() = default;
+    device_buffers(device_replica const* rep, hipStream_t s) : m_rep(rep), m_stream(s) {}
+    device_buffers(device_buffers const&) = delete;
+    device_buffers& operator=(device_buffers const&) = delete;
+    ~device_buffers() {
+        for (void* p : m_owned) free_one(p);
+    }
+    template <typename T>
+    T* alloc(uint64_t n) {
+        const size_t bytes = std::max<uint64_t>(n * sizeof(T), 8);
+        void* p = nullptr;
+        if (m_rep) p = m_rep->stream_alloc(bytes, m_stream);
+        else HIP_CHECK(hipMalloc(&p, bytes));
+        m_owned.push_back(p);
+        return static_cast<T*>(p);
+    }
+    /* free one before the others */
+    void release(void const* p) {
+        for (void*& q : m_owned)
+            if (q == p) {
+                free_one(q);
+                q = nullptr;
+            }
+    }
+    /* hand a hipMalloc'ed buffer over to the replica, which frees it with the rest of its HBM */
+    void keep(void const* p, device_replica& rep) {
+        for (void*& q : m_owned)
+            if (q == p) {
+                rep.allocations.push_back(q);
+                q = nullptr;
+            }
+    }
+
+private:
+    void free_one(void* p) const {
+        if (!p) return;
+        if (m_rep) (void)hipFreeAsync(p, m_stream);
+        else (void)hipFree(p);
+    }
+    device_replica const* m_rep = nullptr;
+    hipStream_t m_stream = nullptr;
+    std::vector<void*> m_owned;
+};
+
+class engine;
+
+/* the devices holding a replica (engine::devices), or the error that there are none */
+std::vector<int> resident_devices(engine const& eng);
+
+/* Runs the lanes of a host-buffer entry point (engine.hip): lane i calls fn(i, devices[i], lane) with devices[i] current and a
+   pooled lane of that device's replica of at least `bytes` -- on the calling thread when there is one lane, else on a thread
+   each. Once every lane has finished, the caller's device is restored and the first exception (in lane order) rethrown;
+   `failed`, when given, is set as soon as a lane throws. */
+void run_lanes(engine const& eng, std::vector<int> const& devices, size_t bytes, std::function<void(size_t, int, host_lane&)> const& fn,
+               std::atomic<bool>* failed = nullptr);
 
 }  // namespace sshash_amd

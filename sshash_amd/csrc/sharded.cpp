@@ -19,21 +19,6 @@ namespace sshash_amd {
 
 namespace {
 
-struct stream_buffers {  // stream-ordered scratch out of the replica's own pool, released on every exit path
-    hipStream_t s;
-    device_replica const* rep;
-    std::vector<void*> owned;
-    template <typename T>
-    T* get(uint64_t n) {
-        void* p = rep->stream_alloc(std::max<uint64_t>(n, 1) * sizeof(T), s);
-        owned.push_back(p);
-        return static_cast<T*>(p);
-    }
-    ~stream_buffers() {
-        for (void* p : owned) (void)hipFreeAsync(p, s);
-    }
-};
-
 void call(int rc, char const* what) {
     if (rc != 0) throw error(error_kind::internal, std::string("sharded lookup: the ") + what + " exchange failed (" + std::to_string(rc) + ")");
 }
@@ -48,12 +33,12 @@ void engine::sharded_lookup_device(int device, uint32_t num_ranks, bool by_table
     device_guard guard(device);
     hipStream_t s = hipStream_t(stream);
     const uint32_t W = rep->view.k <= 31 ? 1 : 2, R = num_ranks;
-    stream_buffers buf{s, rep, {}};
+    device_buffers buf(rep, s);  // (stream-ordered)
 
     /* 1. route: messages per owner, then the messages themselves in per-owner regions (engine.hip: route_bucket_kernel) */
-    uint64_t* d_cursors = buf.get<uint64_t>(R);
+    uint64_t* d_cursors = buf.alloc<uint64_t>(R);
     HIP_CHECK(hipMemsetAsync(d_cursors, 0, R * sizeof(uint64_t), s));
-    uint32_t* d_owners = buf.get<uint32_t>(n);  // elected once, by the counting launch
+    uint32_t* d_owners = buf.alloc<uint32_t>(n);  // elected once, by the counting launch
     route_bucket_device(device, d_kmers, n, R, check_rc, by_table_key, d_cursors, nullptr, nullptr, s, d_owners);
     std::vector<uint64_t> send_counts(R), recv_counts(R), first(R);
     HIP_CHECK(hipMemcpyAsync(send_counts.data(), d_cursors, R * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
@@ -61,8 +46,8 @@ void engine::sharded_lookup_device(int device, uint32_t num_ranks, bool by_table
     std::exclusive_scan(send_counts.begin(), send_counts.end(), first.begin(), uint64_t(0));
     const uint64_t total = first.back() + send_counts.back();
     HIP_CHECK(hipMemcpyAsync(d_cursors, first.data(), R * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    uint64_t* d_send = buf.get<uint64_t>(total * W);
-    uint32_t* d_slots = buf.get<uint32_t>(total);
+    uint64_t* d_send = buf.alloc<uint64_t>(total * W);
+    uint32_t* d_slots = buf.alloc<uint32_t>(total);
     route_bucket_device(device, d_kmers, n, R, check_rc, by_table_key, d_cursors, d_send, d_slots, s, d_owners);
 
     /* 2. exchange: one packed k-mer per message. Every rank must elect table keys of the same length: the length steers which rank owns
@@ -89,17 +74,17 @@ void engine::sharded_lookup_device(int device, uint32_t num_ranks, bool by_table
                                                   " bases, this rank of " + std::to_string(my_key) + " (SSHASH_AMD_SK_M must be the same on every rank, and every rank must shard the same way)");
     }
     const uint64_t m = std::accumulate(recv_counts.begin(), recv_counts.end(), uint64_t(0));
-    uint64_t* d_recv = buf.get<uint64_t>(m * W);
+    uint64_t* d_recv = buf.alloc<uint64_t>(m * W);
     call(x.data(x.ctx, d_send, send_counts.data(), d_recv, recv_counts.data(), W * 8, stream), "k-mer");
 
     /* 3. the ordinary batched lookup on what arrived (a probe whose structures live elsewhere simply misses) */
-    uint64_t* d_ids = buf.get<uint64_t>(m);
+    uint64_t* d_ids = buf.alloc<uint64_t>(m);
     result_view ids{};
     ids.kmer_id = d_ids;
     if (m) lookup_packed_device(device, d_recv, m, check_rc, out_mode::ids, ids, nullptr, stream);
 
     /* 4. the ids travel back, aligned with the messages; 5. a reply that found its k-mer settles its query */
-    uint64_t* d_replies = buf.get<uint64_t>(total);
+    uint64_t* d_replies = buf.alloc<uint64_t>(total);
     call(x.data(x.ctx, d_ids, recv_counts.data(), d_replies, send_counts.data(), 8, stream), "id");
     const bool one_reply_per_query = total == n;  // table keys, canonical minimizers, no reverse complements: every query has ONE owner
     if (n && !one_reply_per_query) HIP_CHECK(hipMemsetAsync(d_out, 0xFF, n * sizeof(uint64_t), s));

@@ -337,33 +337,6 @@ sk_place_kernel(const dict_view d, const uint32_t choice, const uint64_t num_ite
     }
 }
 
-struct temp_buffers {  // freed on every exit path
-    std::vector<void*> owned;
-    template <typename T>
-    T* alloc(uint64_t n) {
-        void* p = nullptr;
-        HIP_CHECK(hipMalloc(&p, std::max<uint64_t>(n, 1) * sizeof(T)));
-        owned.push_back(p);
-        return static_cast<T*>(p);
-    }
-    void release(void* p) {
-        for (auto& q : owned)
-            if (q == p) {
-                (void)hipFree(q);
-                q = nullptr;
-            }
-    }
-    /* hand a buffer over to the replica */
-    void keep(void* p) {
-        for (auto& q : owned)
-            if (q == p) q = nullptr;
-    }
-    ~temp_buffers() {
-        for (void* p : owned)
-            if (p) (void)hipFree(p);
-    }
-};
-
 }  // namespace
 
 /* why a replica has no table (device_stats; sshash_device_stats out[11]): lookups then take the directory / MPHF path,
@@ -466,7 +439,7 @@ void build_sk_table(device_replica& rep, host_index const& idx, uint32_t table_s
         }
     };
 
-    temp_buffers tmp;
+    device_buffers tmp;
     uint32_t* counts = tmp.alloc<uint32_t>(num_waves);
     uint64_t* offsets = tmp.alloc<uint64_t>(num_waves + 1);
     const bool wide = idx.k > 31;
@@ -632,8 +605,7 @@ void build_sk_table(device_replica& rep, host_index const& idx, uint32_t table_s
     HIP_CHECK(hipMemcpy(h_stats, stats, 64, hipMemcpyDeviceToHost));
     HIP_CHECK(hipDeviceSynchronize());
 
-    tmp.keep(slots);
-    rep.allocations.push_back(slots);
+    tmp.keep(slots, rep);
     rep.bytes += table_bytes;
     {
         unsigned long long hist[2 * SK_HIST_BINS];

@@ -822,30 +822,16 @@ void engine::streaming_lookup_device(int device, char const* d_bases, uint64_t c
     dict_view const& d = rep->view;
     const uint32_t W = d.k <= 31 ? 1 : 2;
     const uint64_t chunk = std::min<uint64_t>(total_bases, uint64_t(1) << 27);
-    /* stream-ordered temporaries, given back on every exit path (an exception between allocation and release must not
-       leak them: ADVICE r2) */
-    struct temporaries {
-        hipStream_t s;
-        device_replica const* rep;
-        std::vector<void*> owned;
-        void* get(uint64_t bytes) {
-            void* p = rep->stream_alloc(std::max<uint64_t>(bytes, 8), s);
-            owned.push_back(p);
-            return p;
-        }
-        ~temporaries() {
-            for (void* p : owned) (void)hipFreeAsync(p, s);
-        }
-    } tmp{s, rep, {}};
+    device_buffers tmp(rep, s);  // (stream-ordered; an exception between allocation and release must not leak them: ADVICE r2)
     uint64_t* sid = d_out.string_id;
     int8_t* ori = d_out.kmer_orientation;
     uint64_t* ids = d_out.kmer_id;  // null: counters only (streaming_query_host over reads too long for one lane each)
-    if (!ids) ids = static_cast<uint64_t*>(tmp.get(total_bases * sizeof(uint64_t)));
-    uint8_t* flags = static_cast<uint8_t*>(tmp.get(total_bases));
-    uint64_t* kmers = static_cast<uint64_t*>(tmp.get(chunk * W * sizeof(uint64_t)));
-    uint64_t* tile_read = static_cast<uint64_t*>(tmp.get(((chunk + 255) / 256) * sizeof(uint64_t)));
-    if (!sid) sid = static_cast<uint64_t*>(tmp.get(total_bases * sizeof(uint64_t)));
-    if (!ori) ori = static_cast<int8_t*>(tmp.get(total_bases));
+    if (!ids) ids = tmp.alloc<uint64_t>(total_bases);
+    uint8_t* flags = tmp.alloc<uint8_t>(total_bases);
+    uint64_t* kmers = tmp.alloc<uint64_t>(chunk * W);
+    uint64_t* tile_read = tmp.alloc<uint64_t>((chunk + 255) / 256);
+    if (!sid) sid = tmp.alloc<uint64_t>(total_bases);
+    if (!ori) ori = tmp.alloc<int8_t>(total_bases);
     result_view all = d_out;
     all.kmer_id = ids;
     all.string_id = sid;
@@ -857,60 +843,38 @@ void engine::streaming_lookup_device(int device, char const* d_bases, uint64_t c
         if (W == 1) hipLaunchKernelGGL(stream_encode_kernel<1>, grid, block, 0, s, d_bases, d_read_offsets, tile_read, n_reads, total_bases, first, count, d.k, kmers, flags);
         else hipLaunchKernelGGL(stream_encode_kernel<2>, grid, block, 0, s, d_bases, d_read_offsets, tile_read, n_reads, total_bases, first, count, d.k, kmers, flags);
         HIP_CHECK(hipGetLastError());
-        result_view part = all;
-        part.kmer_id += first;
-        if (part.kmer_id_in_string) part.kmer_id_in_string += first;
-        if (part.kmer_offset) part.kmer_offset += first;
-        part.string_id += first;
-        if (part.string_begin) part.string_begin += first;
-        if (part.string_end) part.string_end += first;
-        part.kmer_orientation += first;
-        lookup_packed_masked_device(device, kmers, flags + first, count, true, out_mode::full, part, s);
+        lookup_packed_masked_device(device, kmers, flags + first, count, true, out_mode::full, advance(all, first), s);
     }
+    result_view out = d_out;  // (the caller's arrays, kmer_id or its stand-in)
+    out.kmer_id = ids;
     for (uint64_t first = 0; first < total_bases; first += uint64_t(1) << 30) {
         const uint64_t count = std::min<uint64_t>(uint64_t(1) << 30, total_bases - first);
-        result_view part = d_out;
-        part.kmer_id = ids + first;
-        if (part.kmer_id_in_string) part.kmer_id_in_string += first;
-        if (part.kmer_offset) part.kmer_offset += first;
-        if (part.string_id) part.string_id += first;
-        if (part.string_begin) part.string_begin += first;
-        if (part.string_end) part.string_end += first;
-        if (part.kmer_orientation) part.kmer_orientation += first;
-        hipLaunchKernelGGL(stream_classify_kernel, dim3(uint32_t(std::min<uint64_t>((count + 1023) / 1024, 2048))), dim3(256), 0, s, flags + first, count, part,
-                           sid + first, ori + first, d_report, first != 0);
+        hipLaunchKernelGGL(stream_classify_kernel, dim3(uint32_t(std::min<uint64_t>((count + 1023) / 1024, 2048))), dim3(256), 0, s, flags + first, count,
+                           advance(out, first), sid + first, ori + first, d_report, first != 0);
         HIP_CHECK(hipGetLastError());
     }
+}
+
+/* the six counters accumulated at d_report on the device, read back once the work on `s` is done */
+static streaming_report read_back(uint64_t const* d_report, hipStream_t s) {
+    uint64_t h[6];
+    HIP_CHECK(hipMemcpyAsync(h, d_report, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return streaming_report::from_device(h);
 }
 
 /* Host buffers: pieces of whole reads (at most ~64 MiB of bases each) go through one stream: H2D, the device pipeline
    above, D2H of the arrays the caller asked for. */
 streaming_report engine::streaming_lookup_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads,
                                                result_view const& h_out) const {
-    streaming_report total;
-    if (n_reads == 0) return total;
+    if (n_reads == 0) return {};
     if (!h_out.kmer_id) throw error(error_kind::argument, "kmer_id output pointer is null");
-    const std::vector<int> devs = devices();
-    if (devs.empty()) throw error(error_kind::no_device, "dictionary is not resident on any device (call sshash_to_device first)");
-    const int device = devs[0];
+    const int device = resident_devices(*this)[0];
     device_guard guard(device);
     const uint64_t piece_bases = uint64_t(64) << 20;
-    hipStream_t s = nullptr;
-    HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    struct buffers {
-        std::vector<void*> dev;
-        hipStream_t s;
-        ~buffers() {
-            for (void* p : dev) (void)hipFree(p);
-            (void)hipStreamDestroy(s);
-        }
-    } own{{}, s};
-    auto dmalloc = [&](uint64_t bytes) {
-        void* p = nullptr;
-        HIP_CHECK(hipMalloc(&p, std::max<uint64_t>(bytes, 8)));
-        own.dev.push_back(p);
-        return p;
-    };
+    device_buffers own;
+    const own_stream call(replica(device));  // (drained and its lookup scratch handed back before `own` frees the buffers)
+    hipStream_t s = call.s;
     uint64_t max_bases = 0, max_reads = 0;
     std::vector<uint64_t> cuts{0};
     for (uint64_t at = 0; at < n_reads;) {
@@ -921,19 +885,15 @@ streaming_report engine::streaming_lookup_host(char const* bases, uint64_t const
         cuts.push_back(end);
         at = end;
     }
-    char* d_bases = static_cast<char*>(dmalloc(max_bases + 8));
-    uint64_t* d_offsets = static_cast<uint64_t*>(dmalloc((max_reads + 1) * 8));
-    uint64_t* d_report = static_cast<uint64_t*>(dmalloc(6 * 8));
+    char* d_bases = own.alloc<char>(max_bases + 8);
+    uint64_t* d_offsets = own.alloc<uint64_t>(max_reads + 1);
+    uint64_t* d_report = own.alloc<uint64_t>(6);
     HIP_CHECK(hipMemsetAsync(d_report, 0, 48, s));
-    result_view d_out{};
-    d_out.kmer_id = static_cast<uint64_t*>(dmalloc(max_bases * 8));
-    if (h_out.kmer_id_in_string) d_out.kmer_id_in_string = static_cast<uint64_t*>(dmalloc(max_bases * 8));
-    if (h_out.kmer_offset) d_out.kmer_offset = static_cast<uint64_t*>(dmalloc(max_bases * 8));
-    if (h_out.string_id) d_out.string_id = static_cast<uint64_t*>(dmalloc(max_bases * 8));
-    if (h_out.string_begin) d_out.string_begin = static_cast<uint64_t*>(dmalloc(max_bases * 8));
-    if (h_out.string_end) d_out.string_end = static_cast<uint64_t*>(dmalloc(max_bases * 8));
-    if (h_out.kmer_orientation) d_out.kmer_orientation = static_cast<int8_t*>(dmalloc(max_bases));
     if (h_out.minimizer_found) throw error(error_kind::argument, "the streaming lookup does not report minimizer_found");
+    result_view d_out{};
+    for_each_field([&](int, auto* h, auto*& d, uint64_t) {
+        if (h) d = own.alloc<std::remove_reference_t<decltype(*d)>>(max_bases);
+    }, h_out, d_out);
     std::vector<uint64_t> rel(max_reads + 1);
     for (size_t piece = 0; piece + 1 < cuts.size(); ++piece) {
         const uint64_t first = cuts[piece], last = cuts[piece + 1];
@@ -944,39 +904,16 @@ streaming_report engine::streaming_lookup_host(char const* bases, uint64_t const
         HIP_CHECK(hipMemcpyAsync(d_bases, bases + b0, nb, hipMemcpyHostToDevice, s));
         /* places without a k-mer keep what the caller's arrays hold (sshash_amd.h: "left untouched"): EVERY requested
            device array is seeded with the caller's (only kmer_id was, the others came back as stale device memory) */
-        auto seed = [&](auto* h, auto* dptr, uint64_t width) {
-            if (h) HIP_CHECK(hipMemcpyAsync(dptr, h + b0, nb * width, hipMemcpyHostToDevice, s));
-        };
-        seed(h_out.kmer_id, d_out.kmer_id, 8);
-        seed(h_out.kmer_id_in_string, d_out.kmer_id_in_string, 8);
-        seed(h_out.kmer_offset, d_out.kmer_offset, 8);
-        seed(h_out.string_id, d_out.string_id, 8);
-        seed(h_out.string_begin, d_out.string_begin, 8);
-        seed(h_out.string_end, d_out.string_end, 8);
-        seed(h_out.kmer_orientation, d_out.kmer_orientation, 1);
+        for_each_field([&](int, auto* h, auto* d, uint64_t width) {
+            if (h) HIP_CHECK(hipMemcpyAsync(d, h + b0, nb * width, hipMemcpyHostToDevice, s));
+        }, h_out, d_out);
         streaming_lookup_device(device, d_bases, d_offsets, last - first, nb, d_out, d_report, s);
-        HIP_CHECK(hipMemcpyAsync(h_out.kmer_id + b0, d_out.kmer_id, nb * 8, hipMemcpyDeviceToHost, s));
-        auto back = [&](auto* h, auto* dptr, uint64_t width) {
-            if (h) HIP_CHECK(hipMemcpyAsync(h + b0, dptr, nb * width, hipMemcpyDeviceToHost, s));
-        };
-        back(h_out.kmer_id_in_string, d_out.kmer_id_in_string, 8);
-        back(h_out.kmer_offset, d_out.kmer_offset, 8);
-        back(h_out.string_id, d_out.string_id, 8);
-        back(h_out.string_begin, d_out.string_begin, 8);
-        back(h_out.string_end, d_out.string_end, 8);
-        back(h_out.kmer_orientation, d_out.kmer_orientation, 1);
+        for_each_field([&](int, auto* h, auto* d, uint64_t width) {
+            if (h) HIP_CHECK(hipMemcpyAsync(h + b0, d, nb * width, hipMemcpyDeviceToHost, s));
+        }, h_out, d_out);
         HIP_CHECK(hipStreamSynchronize(s));
     }
-    uint64_t h[6];
-    HIP_CHECK(hipMemcpyAsync(h, d_report, sizeof(h), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    total.num_kmers = h[0];
-    total.num_positive_kmers = h[1];
-    total.num_negative_kmers = h[2];
-    total.num_invalid_kmers = h[3];
-    total.num_searches = h[4];
-    total.num_extensions = h[5];
-    return total;
+    return read_back(d_report, s);
 }
 
 /* Host buffers: the reads are cut into pieces of at most ~32 MiB of bases; per replica up to eight lanes (the
@@ -985,10 +922,8 @@ streaming_report engine::streaming_lookup_host(char const* bases, uint64_t const
 constexpr uint64_t LONG_READ_BASES = uint64_t(1) << 16;
 
 streaming_report engine::streaming_query_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads) const {
-    streaming_report total;
-    if (n_reads == 0) return total;
-    const std::vector<int> devs = devices();
-    if (devs.empty()) throw error(error_kind::no_device, "dictionary is not resident on any device (call sshash_to_device first)");
+    if (n_reads == 0) return {};
+    const std::vector<int> devs = resident_devices(*this);
     const uint64_t G = devs.size();
     /* pieces: [first read, last read) with a bounded number of bases (a single longer read is its own piece) */
     const uint64_t piece_bases = uint64_t(32) << 20, piece_reads = uint64_t(1) << 20;
@@ -1011,76 +946,37 @@ streaming_report engine::streaming_query_host(char const* bases, uint64_t const*
     std::atomic<uint64_t> next{0};
     const uint64_t hw = std::max(1u, std::thread::hardware_concurrency());
     const uint64_t lanes_per_device = std::min<uint64_t>({(num_pieces + G - 1) / G, 8, std::max<uint64_t>(1, hw / G)});
-    const uint64_t num_lanes = lanes_per_device * G;
-    std::vector<std::exception_ptr> errors(num_lanes);
-    std::vector<streaming_report> partial(num_lanes);
-
-    auto run_lane = [&](uint64_t li) {
-        try {
-            const int device = devs[li % G];
-            device_replica const* rep = replica(device);
-            HIP_CHECK(hipSetDevice(device));
-            host_lane* lane = rep->acquire_lane(lane_bytes);
-            struct give_back {
-                device_replica const* rep;
-                host_lane* lane;
-                ~give_back() { rep->release_lane(lane); }
-            } guard{rep, lane};
-            hipStream_t s = lane->stream;
-            char* hp = static_cast<char*>(lane->pinned);
-            char* dp = static_cast<char*>(lane->device);
-            uint64_t* d_report = reinterpret_cast<uint64_t*>(dp + report_at);
-            HIP_CHECK(hipMemsetAsync(d_report, 0, 6 * sizeof(uint64_t), s));
-            for (;;) {
-                const uint64_t piece = next.fetch_add(1);
-                if (piece >= num_pieces) break;
-                const uint64_t first = cuts[piece], last = cuts[piece + 1];
-                const uint64_t nb = read_offsets[last] - read_offsets[first];
-                uint64_t* rel = reinterpret_cast<uint64_t*>(hp);
-                for (uint64_t i = first; i <= last; ++i) rel[i - first] = read_offsets[i] - read_offsets[first];
-                std::memcpy(hp + bases_at, bases + read_offsets[first], nb);
-                HIP_CHECK(hipMemcpyAsync(dp, hp, (last - first + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-                HIP_CHECK(hipMemcpyAsync(dp + bases_at, hp + bases_at, nb, hipMemcpyHostToDevice, s));
-                /* one lane walks one read: a read of megabases (a contig, a multiline FASTA record) would keep a single
-                   lane busy for minutes; such pieces go through the position-parallel pipeline, which gives the same counters */
-                bool long_read = false;
-                for (uint64_t i = first; i < last && !long_read; ++i) long_read = read_offsets[i + 1] - read_offsets[i] > LONG_READ_BASES;
-                if (long_read) streaming_lookup_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, result_view{}, d_report, s);
-                else streaming_query_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, d_report, s);
-                HIP_CHECK(hipStreamSynchronize(s));  // the pinned block is reused by the next piece
-            }
-            uint64_t h[6];
-            HIP_CHECK(hipMemcpyAsync(h, d_report, sizeof(h), hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            partial[li].num_kmers = h[0];
-            partial[li].num_positive_kmers = h[1];
-            partial[li].num_negative_kmers = h[2];
-            partial[li].num_invalid_kmers = h[3];
-            partial[li].num_searches = h[4];
-            partial[li].num_extensions = h[5];
-        } catch (...) { errors[li] = std::current_exception(); }
-    };
-
-    int prev = 0;
-    HIP_CHECK(hipGetDevice(&prev));
-    if (num_lanes == 1) {
-        run_lane(0);
-    } else {
-        std::vector<std::thread> workers;
-        for (uint64_t li = 0; li < num_lanes; ++li) workers.emplace_back(run_lane, li);
-        for (auto& w : workers) w.join();
-    }
-    (void)hipSetDevice(prev);
-    for (auto const& e : errors)
-        if (e) std::rethrow_exception(e);
-    for (auto const& p : partial) {
-        total.num_kmers += p.num_kmers;
-        total.num_positive_kmers += p.num_positive_kmers;
-        total.num_negative_kmers += p.num_negative_kmers;
-        total.num_invalid_kmers += p.num_invalid_kmers;
-        total.num_searches += p.num_searches;
-        total.num_extensions += p.num_extensions;
-    }
+    std::vector<int> lane_devs(lanes_per_device * G);
+    for (uint64_t li = 0; li < lane_devs.size(); ++li) lane_devs[li] = devs[li % G];
+    std::vector<streaming_report> partial(lane_devs.size());
+    run_lanes(*this, lane_devs, lane_bytes, [&](size_t li, int device, host_lane& lane) {
+        hipStream_t s = lane.stream;
+        char* hp = static_cast<char*>(lane.pinned);
+        char* dp = static_cast<char*>(lane.device);
+        uint64_t* d_report = reinterpret_cast<uint64_t*>(dp + report_at);
+        HIP_CHECK(hipMemsetAsync(d_report, 0, 6 * sizeof(uint64_t), s));
+        for (;;) {
+            const uint64_t piece = next.fetch_add(1);
+            if (piece >= num_pieces) break;
+            const uint64_t first = cuts[piece], last = cuts[piece + 1];
+            const uint64_t nb = read_offsets[last] - read_offsets[first];
+            uint64_t* rel = reinterpret_cast<uint64_t*>(hp);
+            for (uint64_t i = first; i <= last; ++i) rel[i - first] = read_offsets[i] - read_offsets[first];
+            std::memcpy(hp + bases_at, bases + read_offsets[first], nb);
+            HIP_CHECK(hipMemcpyAsync(dp, hp, (last - first + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipMemcpyAsync(dp + bases_at, hp + bases_at, nb, hipMemcpyHostToDevice, s));
+            /* one lane walks one read: a read of megabases (a contig, a multiline FASTA record) would keep a single
+               lane busy for minutes; such pieces go through the position-parallel pipeline, which gives the same counters */
+            bool long_read = false;
+            for (uint64_t i = first; i < last && !long_read; ++i) long_read = read_offsets[i + 1] - read_offsets[i] > LONG_READ_BASES;
+            if (long_read) streaming_lookup_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, result_view{}, d_report, s);
+            else streaming_query_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, d_report, s);
+            HIP_CHECK(hipStreamSynchronize(s));  // the pinned block is reused by the next piece
+        }
+        partial[li] = read_back(d_report, s);
+    });
+    streaming_report total;
+    for (auto const& p : partial) total += p;
     return total;
 }
 
@@ -1089,8 +985,7 @@ streaming_report engine::streaming_query_host(char const* bases, uint64_t const*
    work: lane = host thread + stream + pinned block + device block, as many lanes as usable CPUs, dealt round-robin to the
    resident replicas. */
 bool engine::streaming_query_fastq_pieces(std::string const& filename, streaming_report& total) const {
-    const std::vector<int> devs = devices();
-    if (devs.empty()) throw error(error_kind::no_device, "dictionary is not resident on any device (call sshash_to_device first)");
+    const std::vector<int> devs = resident_devices(*this);
     const uint64_t G = devs.size();
     uint64_t want_lanes = std::max<uint64_t>(G, std::min<uint64_t>(32, usable_cpus()));
     if (char const* e = std::getenv("SSHASH_AMD_READER_THREADS")) want_lanes = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
@@ -1110,77 +1005,41 @@ bool engine::streaming_query_fastq_pieces(std::string const& filename, streaming
     const uint64_t bases_at = (off_capacity * sizeof(uint64_t) + 255) & ~uint64_t(255);
     const uint64_t report_at = (bases_at + bases_capacity + 255) & ~uint64_t(255);
     const uint64_t lane_bytes = report_at + 6 * sizeof(uint64_t);
-    const uint64_t num_lanes = std::min(num_pieces, want_lanes);
+    std::vector<int> lane_devs(std::min(num_pieces, want_lanes));
+    for (uint64_t li = 0; li < lane_devs.size(); ++li) lane_devs[li] = devs[li % G];
 
     std::atomic<uint64_t> next{0};
-    std::atomic<bool> give_up{false};
+    std::atomic<bool> give_up{false};  // a lane threw, or a piece did not fit: the others take no more pieces
     std::vector<fastq_pieces::parsed> seen(num_pieces);
-    std::vector<std::exception_ptr> errors(num_lanes);
-    std::vector<streaming_report> partial(num_lanes);
-
-    auto run_lane = [&](uint64_t li) {
-        try {
-            const int device = devs[li % G];
-            device_replica const* rep = replica(device);
-            HIP_CHECK(hipSetDevice(device));
-            host_lane* lane = rep->acquire_lane(lane_bytes);
-            struct give_back {
-                device_replica const* rep;
-                host_lane* lane;
-                ~give_back() { rep->release_lane(lane); }
-            } guard{rep, lane};
-            hipStream_t s = lane->stream;
-            char* hp = static_cast<char*>(lane->pinned);
-            char* dp = static_cast<char*>(lane->device);
-            uint64_t* d_report = reinterpret_cast<uint64_t*>(dp + report_at);
-            HIP_CHECK(hipMemsetAsync(d_report, 0, 6 * sizeof(uint64_t), s));
-            std::vector<char> raw;
-            for (;;) {
-                const uint64_t piece = next.fetch_add(1);
-                if (piece >= num_pieces || give_up) break;
-                uint64_t* offsets = reinterpret_cast<uint64_t*>(hp);
-                const fastq_pieces::parsed got = file.parse(piece, k, hp + bases_at, bases_capacity, offsets, off_capacity, raw);
-                seen[piece] = got;
-                if (got.overflow) {
-                    give_up = true;
-                    break;
-                }
-                if (got.num_reads == 0) continue;
-                HIP_CHECK(hipMemcpyAsync(dp, hp, (got.num_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-                HIP_CHECK(hipMemcpyAsync(dp + bases_at, hp + bases_at, got.num_bases, hipMemcpyHostToDevice, s));
-                bool long_read = false;  // (as streaming_query_host: a read of megabases must not sit on one lane of a wave)
-                for (uint64_t i = 0; i < got.num_reads && !long_read; ++i) long_read = offsets[i + 1] - offsets[i] > LONG_READ_BASES;
-                if (long_read) streaming_lookup_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), got.num_reads, got.num_bases, result_view{}, d_report, s);
-                else streaming_query_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), got.num_reads, got.num_bases, d_report, s);
-                HIP_CHECK(hipStreamSynchronize(s));  // the pinned block is parsed into again
+    std::vector<streaming_report> partial(lane_devs.size());
+    run_lanes(*this, lane_devs, lane_bytes, [&](size_t li, int device, host_lane& lane) {
+        hipStream_t s = lane.stream;
+        char* hp = static_cast<char*>(lane.pinned);
+        char* dp = static_cast<char*>(lane.device);
+        uint64_t* d_report = reinterpret_cast<uint64_t*>(dp + report_at);
+        HIP_CHECK(hipMemsetAsync(d_report, 0, 6 * sizeof(uint64_t), s));
+        std::vector<char> raw;
+        for (;;) {
+            const uint64_t piece = next.fetch_add(1);
+            if (piece >= num_pieces || give_up) break;
+            uint64_t* offsets = reinterpret_cast<uint64_t*>(hp);
+            const fastq_pieces::parsed got = file.parse(piece, k, hp + bases_at, bases_capacity, offsets, off_capacity, raw);
+            seen[piece] = got;
+            if (got.overflow) {
+                give_up = true;
+                break;
             }
-            uint64_t h[6];
-            HIP_CHECK(hipMemcpyAsync(h, d_report, sizeof(h), hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            partial[li].num_kmers = h[0];
-            partial[li].num_positive_kmers = h[1];
-            partial[li].num_negative_kmers = h[2];
-            partial[li].num_invalid_kmers = h[3];
-            partial[li].num_searches = h[4];
-            partial[li].num_extensions = h[5];
-        } catch (...) {
-            errors[li] = std::current_exception();
-            give_up = true;
+            if (got.num_reads == 0) continue;
+            HIP_CHECK(hipMemcpyAsync(dp, hp, (got.num_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipMemcpyAsync(dp + bases_at, hp + bases_at, got.num_bases, hipMemcpyHostToDevice, s));
+            bool long_read = false;  // (as streaming_query_host: a read of megabases must not sit on one lane of a wave)
+            for (uint64_t i = 0; i < got.num_reads && !long_read; ++i) long_read = offsets[i + 1] - offsets[i] > LONG_READ_BASES;
+            if (long_read) streaming_lookup_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), got.num_reads, got.num_bases, result_view{}, d_report, s);
+            else streaming_query_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), got.num_reads, got.num_bases, d_report, s);
+            HIP_CHECK(hipStreamSynchronize(s));  // the pinned block is parsed into again
         }
-    };
-
-    int prev = 0;
-    HIP_CHECK(hipGetDevice(&prev));
-    if (num_lanes == 1) {
-        run_lane(0);
-    } else {
-        std::vector<std::thread> workers;
-        for (uint64_t li = 0; li < num_lanes; ++li) workers.emplace_back(run_lane, li);
-        for (auto& w : workers) w.join();
-    }
-    (void)hipSetDevice(prev);
-    for (auto const& e : errors)
-        if (e) std::rethrow_exception(e);
+        partial[li] = read_back(d_report, s);
+    }, &give_up);
     if (give_up) return false;
     /* every piece began where its predecessor stopped, the first at 0, the last stopped at the end of the file: the pieces
        together are the sequential reader's records (reads.hpp) */
@@ -1190,14 +1049,7 @@ bool engine::streaming_query_fastq_pieces(std::string const& filename, streaming
         expect = seen[i].next_record;
     }
     if (expect != file.file_bytes()) return false;
-    for (auto const& p : partial) {
-        total.num_kmers += p.num_kmers;
-        total.num_positive_kmers += p.num_positive_kmers;
-        total.num_negative_kmers += p.num_negative_kmers;
-        total.num_invalid_kmers += p.num_invalid_kmers;
-        total.num_searches += p.num_searches;
-        total.num_extensions += p.num_extensions;
-    }
+    for (auto const& p : partial) total += p;
     return true;
 }
 
