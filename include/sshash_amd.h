@@ -254,6 +254,35 @@ sshash_status sshash_streaming_query_device(const sshash_dict* d, int device, co
                                             const uint64_t* read_offsets, uint64_t num_reads, uint64_t total_bases,
                                             uint64_t* report, void* hip_stream);
 
+/* ---- the streaming query PER READ (no reference counterpart as a call; the reference's state machine is reset at every read,
+ *      src/query.cpp:78-108, so the report it would give for read r alone is well defined). Rows are sshash_streaming_report
+ *      structs, one per read, row r for read r of the call; the six counters of sshash_streaming_query over the same reads are the
+ *      column sums of the rows. A read shorter than k (an empty one included) has a row of six zeros. Same preconditions and status
+ *      codes as the calls above; per_read == NULL with num_reads > 0 is SSHASH_ERR_ARGUMENT, num_reads == 0 writes nothing. ---- */
+/* device buffers, asynchronous on hip_stream. per_read: num_reads rows, OVERWRITTEN (every row is written). report: 6 uint64
+ * counters, ACCUMULATED into as sshash_streaming_query_device does; may be NULL. total_bases as for sshash_streaming_query_device.
+ * Like that call it always takes the run kernel -- one lane walks one read, whatever its length: a caller holding reads of
+ * megabases cuts them itself or takes the host call below. */
+sshash_status sshash_streaming_query_per_read_device(const sshash_dict* d, int device, const char* bases,
+                                                     const uint64_t* read_offsets, uint64_t num_reads, uint64_t total_bases,
+                                                     sshash_streaming_report* per_read, uint64_t* report, void* hip_stream);
+/* host buffers; sharded over all resident replicas like sshash_streaming_query (a piece that holds a read above 2^16 bases goes
+ * through the position-parallel pipeline of sshash_streaming_lookup, which gives the same rows); report may be NULL */
+sshash_status sshash_streaming_query_per_read(const sshash_dict* d, const char* bases, const uint64_t* read_offsets,
+                                              uint64_t num_reads, sshash_streaming_report* per_read,
+                                              sshash_streaming_report* report);
+/* a query file: rows are handed over in batches, IN FILE ORDER, one call at a time (never concurrently): rows[0 .. n) belong to
+ * records first_read .. first_read + n of the file. There is a row for EVERY record of the file, those shorter than k included (six
+ * zeros), so that row i is record i: a FASTQ read, a single-line FASTA record (header line + one sequence line), or -- multiline -- a
+ * non-empty segment of a multiline FASTA (the lines up to an empty line or the end of the file, which is what the reader treats as one
+ * read). A non-zero return of `fn` stops the query: the call returns SSHASH_ERR_ARGUMENT, sshash_last_error() carries the value and
+ * `fn` is not called again. report may be NULL. Every kind of file, a plain FASTQ included, takes the sequential reader here (a
+ * reader thread ahead of the devices, as described for sshash_streaming_query_from_file): host memory stays bounded, and the call
+ * runs at that reader's pace. */
+typedef int (*sshash_per_read_fn)(void* ctx, uint64_t first_read, uint64_t n, const sshash_streaming_report* rows);
+sshash_status sshash_streaming_query_from_file_per_read(const sshash_dict* d, const char* filename, int multiline,
+                                                        sshash_per_read_fn fn, void* ctx, sshash_streaming_report* report);
+
 /* ---- streaming_query<Dict,canonical>::lookup for EVERY k-mer of every read (include/streaming_query.hpp:56-109),
  *      batched: what the reference returns k-mer by k-mer while it streams a read. Every non-NULL array of `out` has one
  *      entry per BASE of `bases` (total_bases = read_offsets[num_reads] entries): entry read_offsets[r] + j is the result

@@ -15,6 +15,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -260,6 +261,47 @@ public:
     streaming_query_report streaming_query_from_file(std::string const& filename, bool multiline) const {
         sshash_streaming_report s;
         check(sshash_streaming_query_from_file(m_h, filename.c_str(), multiline, &s));
+        return to_report(s);
+    }
+
+    /* The streaming query's report for every read on its own (sshash_streaming_query_per_read; no reference counterpart as a call:
+       the reference's state is reset at every read, src/query.cpp:78-108, so it is what the reference would report for that read
+       alone): rows[r] for read r = bases[read_offsets[r] .. read_offsets[r + 1]), six zeros for a read shorter than k. Returns the
+       batch's report, the column sums of the rows. */
+    streaming_query_report streaming_query_per_read(char const* bases, uint64_t const* read_offsets, uint64_t num_reads,
+                                                    std::vector<streaming_query_report>& rows) const {
+        std::vector<sshash_streaming_report> raw(num_reads);
+        sshash_streaming_report s;
+        check(sshash_streaming_query_per_read(m_h, bases, read_offsets, num_reads, raw.data(), &s));
+        rows.resize(num_reads);
+        for (uint64_t r = 0; r < num_reads; ++r) rows[r] = to_report(raw[r]);
+        return to_report(s);
+    }
+
+    /* device buffers, asynchronous on hip_stream (sshash_streaming_query_per_read_device): d_rows gets num_reads rows of six
+       uint64 (overwritten), d_report -- may be null -- six counters (accumulated into) */
+    void streaming_query_per_read_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t num_reads,
+                                         uint64_t total_bases, sshash_streaming_report* d_rows, uint64_t* d_report, void* hip_stream) const {
+        check(sshash_streaming_query_per_read_device(m_h, device, d_bases, d_read_offsets, num_reads, total_bases, d_rows, d_report, hip_stream));
+    }
+
+    /* a query file, one row per record, handed over in file order: fn(first_read, rows, n) for one batch after the other; a
+       non-zero return stops the query (std::runtime_error). Fn: int(uint64_t, streaming_query_report const*, uint64_t). */
+    template <typename Fn>
+    streaming_query_report streaming_query_from_file_per_read(std::string const& filename, bool multiline, Fn&& fn) const {
+        static_assert(sizeof(streaming_query_report) == sizeof(sshash_streaming_report), "the same six counters");
+        struct context {
+            std::remove_reference_t<Fn>* fn;
+        } ctx{&fn};
+        sshash_streaming_report s;
+        check(sshash_streaming_query_from_file_per_read(
+            m_h, filename.c_str(), multiline,
+            [](void* c, uint64_t first_read, uint64_t n, const sshash_streaming_report* rows) -> int {
+                std::vector<streaming_query_report> mine(n);
+                for (uint64_t i = 0; i < n; ++i) mine[i] = to_report(rows[i]);
+                return int((*static_cast<context*>(c)->fn)(first_read, static_cast<streaming_query_report const*>(mine.data()), n));
+            },
+            &ctx, &s));
         return to_report(s);
     }
 

@@ -5,7 +5,7 @@ import ctypes as C
 import os
 import sys
 from dataclasses import dataclass
-from typing import Iterable, Optional, Sequence, Union
+from typing import Callable, Iterable, Optional, Sequence, Union
 
 import numpy as np
 
@@ -97,6 +97,10 @@ class _Report(C.Structure):
 _lib: Optional[C.CDLL] = None
 
 
+# sshash_per_read_fn: (ctx, first_read, n, rows) -> 0 to go on
+_PerReadFn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p)
+
+
 def _preload_hip_runtime() -> None:
     """One HIP runtime per process. PyTorch-ROCm wheels bundle their own libamdhip64.so (same SONAME
     as the system one); if libsshash_amd.so pulled in /opt/rocm's copy first, a later `import torch`
@@ -174,6 +178,9 @@ def _load() -> C.CDLL:
         "sshash_streaming_query_from_file": (C.c_int, [P, C.c_char_p, C.c_int, C.POINTER(_Report)]),
         "sshash_streaming_query": (C.c_int, [P, P, P, C.c_uint64, C.POINTER(_Report)]),
         "sshash_streaming_query_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, P]),
+        "sshash_streaming_query_per_read_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, P, P]),
+        "sshash_streaming_query_per_read": (C.c_int, [P, P, P, C.c_uint64, P, C.POINTER(_Report)]),
+        "sshash_streaming_query_from_file_per_read": (C.c_int, [P, C.c_char_p, C.c_int, _PerReadFn, P, C.POINTER(_Report)]),
         "sshash_route_packed_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P, P]),
         "sshash_route_bucket_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, C.c_int, P, P, P, P]),
         "sshash_route_bucket_by_key_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P, P, P]),
@@ -198,6 +205,7 @@ C_ABI_SYMBOLS = (
     "sshash_is_member_packed_device sshash_is_member_packed sshash_is_member_ascii sshash_access sshash_access_packed "
     "sshash_access_packed_device sshash_weight sshash_weight_device "
     "sshash_streaming_query_from_file sshash_streaming_query sshash_streaming_query_device "
+    "sshash_streaming_query_per_read sshash_streaming_query_per_read_device sshash_streaming_query_from_file_per_read "
     "sshash_streaming_lookup sshash_streaming_lookup_device sshash_sharded_lookup_device sshash_sharded_lookup_rccl "
     "sshash_route_packed_device sshash_route_bucket_device sshash_route_bucket_by_key_device sshash_route_combine_device "
     "sshash_iterate_packed sshash_iterate_packed_device sshash_check_device"
@@ -634,10 +642,34 @@ class Dictionary:
         return StreamingQueryReport(r.num_kmers, r.num_positive_kmers, r.num_negative_kmers, r.num_invalid_kmers,
                                     r.num_searches, r.num_extensions)
 
-    def streaming_query_from_file(self, filename: str, multiline: bool = False) -> StreamingQueryReport:
-        """dictionary::streaming_query_from_file (reference include/dictionary.hpp:81-82, src/query.cpp:118-175)."""
+    def streaming_query_from_file(self, filename: str, multiline: bool = False,
+                                  per_read: Optional[Callable[[int, np.ndarray], Optional[int]]] = None) -> StreamingQueryReport:
+        """dictionary::streaming_query_from_file (reference include/dictionary.hpp:81-82, src/query.cpp:118-175).
+
+        per_read: called as per_read(first_read, rows) for one batch of the file after the other, in file order; rows is an (n, 6)
+        uint64 array (the columns of StreamingQueryReport), row i for record first_read + i of the file -- every record has a row,
+        those shorter than k included. A return value other than None / 0 stops the query (SSHashError, status 1); an exception
+        raised by the callable stops it too and is raised again here."""
         r = _Report()
-        _check(_load().sshash_streaming_query_from_file(self._h, os.fsencode(filename), 1 if multiline else 0, C.byref(r)))
+        if per_read is None:
+            _check(_load().sshash_streaming_query_from_file(self._h, os.fsencode(filename), 1 if multiline else 0, C.byref(r)))
+            return self._report(r)
+        raised = []
+
+        def hand_over(_ctx, first_read, n, rows):
+            try:
+                block = np.ctypeslib.as_array(C.cast(rows, C.POINTER(C.c_uint64)), shape=(int(n), 6)).copy()
+                stop = per_read(int(first_read), block)
+                return int(stop) if stop else 0
+            except BaseException as e:  # (must not travel through the C frames)
+                raised.append(e)
+                return -1
+
+        fn = _PerReadFn(hand_over)
+        status = _load().sshash_streaming_query_from_file_per_read(self._h, os.fsencode(filename), 1 if multiline else 0, fn, None, C.byref(r))
+        if raised:
+            raise raised[0]
+        _check(status)
         return self._report(r)
 
     def streaming_query(self, reads: Sequence[Union[str, bytes]]) -> StreamingQueryReport:
@@ -650,6 +682,29 @@ class Dictionary:
         r = _Report()
         _check(_load().sshash_streaming_query(self._h, bases.ctypes.data, offsets.ctypes.data, len(chunks), C.byref(r)))
         return self._report(r)
+
+    def streaming_query_per_read(self, reads: Sequence[Union[str, bytes]]):
+        """The streaming query's report for every read on its own -> (rows, StreamingQueryReport): rows is an (n, 6) uint64 array,
+        row r = (num_kmers, num_positive_kmers, num_negative_kmers, num_invalid_kmers, num_searches, num_extensions) of read r (six
+        zeros for a read shorter than k); the report is the batch's, the column sums of the rows."""
+        chunks = [s.encode("ascii", "replace") if isinstance(s, str) else bytes(s) for s in reads]
+        offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
+        if chunks:
+            offsets[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
+        bases = np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8)
+        rows = np.zeros((len(chunks), 6), dtype=np.uint64)
+        r = _Report()
+        _check(_load().sshash_streaming_query_per_read(self._h, bases.ctypes.data, offsets.ctypes.data, len(chunks),
+                                                       rows.ctypes.data if len(chunks) else None, C.byref(r)))
+        return rows, self._report(r)
+
+    def streaming_query_per_read_device(self, device: int, d_bases: int, d_read_offsets: int, num_reads: int, d_rows: int,
+                                        d_report: int = 0, stream: int = 0, total_bases: int = 0) -> None:
+        """Device buffers: d_rows receives num_reads rows of six uint64 (overwritten), d_report (0: none) six counters (accumulated
+        into). `total_bases` as for streaming_query_device."""
+        _check(_load().sshash_streaming_query_per_read_device(self._h, int(device), C.c_void_p(d_bases), C.c_void_p(d_read_offsets),
+                                                              int(num_reads), int(total_bases), C.c_void_p(d_rows),
+                                                              C.c_void_p(d_report), C.c_void_p(stream)))
 
     def streaming_lookup(self, reads: Sequence[Union[str, bytes]], full: bool = False):
         """streaming_query::lookup for every k-mer of every read (reference include/streaming_query.hpp:56-109), batched.

@@ -100,6 +100,80 @@ void fill_report(sshash_streaming_report* report, streaming_report const& r) {
     report->num_extensions = r.num_extensions;
 }
 
+/* The sequential reader of a query file, a batch ahead of whoever uses the batches: `per_batch(read_batch const&)` is called for one
+   batch after the other, in file order, on the calling thread. */
+template <typename Fn>
+void for_each_batch(read_stream& in, Fn&& per_batch) {
+    /* The file goes through in batches of ~256 MiB of bases (a FASTQ of hundreds of gigabytes must not be
+       materialised): a reader thread decompresses batch i+1 while the devices work on batch i. */
+    uint64_t batch_bases = uint64_t(256) << 20;
+    batch_bases = test_hook_u64("query_batch_bases", batch_bases, 1, ~uint64_t(0));  // (tests: batch seams inside a small file)
+    read_batch slot[2];
+    std::mutex mu;
+    std::condition_variable cv;
+    int filled[2] = {0, 0};  // 0 = free, 1 = holds a batch, 2 = end of file
+    std::exception_ptr reader_error;
+    bool abandon = false;
+    std::thread reader([&] {
+        try {
+            for (int at = 0;; at ^= 1) {
+                {
+                    std::unique_lock<std::mutex> lock(mu);
+                    cv.wait(lock, [&] { return filled[at] == 0 || abandon; });
+                    if (abandon) return;
+                }
+                const bool more = in.next(slot[at], batch_bases);
+                std::lock_guard<std::mutex> lock(mu);
+                filled[at] = more ? 1 : 2;
+                cv.notify_all();
+                if (!more) return;
+            }
+        } catch (...) {
+            std::lock_guard<std::mutex> lock(mu);
+            reader_error = std::current_exception();
+            filled[0] = filled[1] = 2;
+            cv.notify_all();
+        }
+    });
+    struct joiner {
+        std::thread& t;
+        std::mutex& mu;
+        std::condition_variable& cv;
+        bool& abandon;
+        ~joiner() {
+            {
+                std::lock_guard<std::mutex> lock(mu);
+                abandon = true;
+            }
+            cv.notify_all();
+            t.join();
+        }
+    } join_reader{reader, mu, cv, abandon};
+    double waited = 0, worked = 0;  // SSHASH_AMD_VERBOSE: where the wall clock of the file query went
+    uint64_t batches = 0;
+    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    for (int at = 0;; at ^= 1) {
+        const double t0 = now();
+        {
+            std::unique_lock<std::mutex> lock(mu);
+            cv.wait(lock, [&] { return filled[at] != 0; });
+            if (filled[at] == 2) break;
+        }
+        const double t1 = now();
+        per_batch(slot[at]);
+        waited += t1 - t0;
+        worked += now() - t1;
+        ++batches;
+        std::lock_guard<std::mutex> lock(mu);
+        filled[at] = 0;
+        cv.notify_all();
+    }
+    if (std::getenv("SSHASH_AMD_VERBOSE"))
+        fprintf(stderr, "[sshash_amd] file query: %llu batches; waiting for the reader %.3f s, devices at work %.3f s\n",
+                (unsigned long long)batches, waited, worked);
+    if (reader_error) std::rethrow_exception(reader_error);
+}
+
 }  // namespace
 
 extern "C" {
@@ -393,76 +467,37 @@ sshash_status sshash_streaming_query_from_file(const sshash_dict* d, const char*
                 return;
             }
         }
-        /* The file goes through in batches of ~256 MiB of bases (a FASTQ of hundreds of gigabytes must not be
-           materialised): a reader thread decompresses batch i+1 while the devices work on batch i. */
-        uint64_t batch_bases = uint64_t(256) << 20;
-        batch_bases = test_hook_u64("query_batch_bases", batch_bases, 1, ~uint64_t(0));  // (tests: batch seams inside a small file)
-        read_batch slot[2];
-        std::mutex mu;
-        std::condition_variable cv;
-        int filled[2] = {0, 0};  // 0 = free, 1 = holds a batch, 2 = end of file
-        std::exception_ptr reader_error;
-        bool abandon = false;
-        std::thread reader([&] {
-            try {
-                for (int at = 0;; at ^= 1) {
-                    {
-                        std::unique_lock<std::mutex> lock(mu);
-                        cv.wait(lock, [&] { return filled[at] == 0 || abandon; });
-                        if (abandon) return;
-                    }
-                    const bool more = in.next(slot[at], batch_bases);
-                    std::lock_guard<std::mutex> lock(mu);
-                    filled[at] = more ? 1 : 2;
-                    cv.notify_all();
-                    if (!more) return;
-                }
-            } catch (...) {
-                std::lock_guard<std::mutex> lock(mu);
-                reader_error = std::current_exception();
-                filled[0] = filled[1] = 2;
-                cv.notify_all();
-            }
-        });
-        struct joiner {
-            std::thread& t;
-            std::mutex& mu;
-            std::condition_variable& cv;
-            bool& abandon;
-            ~joiner() {
-                {
-                    std::lock_guard<std::mutex> lock(mu);
-                    abandon = true;
-                }
-                cv.notify_all();
-                t.join();
-            }
-        } join_reader{reader, mu, cv, abandon};
-        double waited = 0, worked = 0;  // SSHASH_AMD_VERBOSE: where the wall clock of the file query went
-        uint64_t batches = 0;
         streaming_report total;
-        auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-        for (int at = 0;; at ^= 1) {
-            const double t0 = now();
-            {
-                std::unique_lock<std::mutex> lock(mu);
-                cv.wait(lock, [&] { return filled[at] != 0; });
-                if (filled[at] == 2) break;
-            }
-            const double t1 = now();
-            const streaming_report r = d->eng->streaming_query_host(slot[at].bases.data(), slot[at].offsets.data(), slot[at].num_reads());
-            waited += t1 - t0;
-            worked += now() - t1;
-            ++batches;
-            fill_report(report, total += r);
-            std::lock_guard<std::mutex> lock(mu);
-            filled[at] = 0;
-            cv.notify_all();
+        for_each_batch(in, [&](read_batch const& batch) {
+            fill_report(report, total += d->eng->streaming_query_host(batch.bases.data(), batch.offsets.data(), batch.num_reads()));
+        });
+    });
+}
+
+sshash_status sshash_streaming_query_from_file_per_read(const sshash_dict* d, const char* filename, int multiline,
+                                                        sshash_per_read_fn fn, void* ctx, sshash_streaming_report* report) {
+    if (!d || !filename || !fn) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (report) std::memset(report, 0, sizeof(*report));
+    return guarded([&] {
+        read_stream in(filename, multiline != 0, d->idx->k, true);  // (every record of the file: row i is record i)
+        if (!in.supported()) {
+            fprintf(stderr, "unsupported query file format\n");
+            return;
         }
-        if (std::getenv("SSHASH_AMD_VERBOSE"))
-            fprintf(stderr, "[sshash_amd] file query: %llu batches; waiting for the reader %.3f s, devices at work %.3f s\n",
-                    (unsigned long long)batches, waited, worked);
-        if (reader_error) std::rethrow_exception(reader_error);
+        static_assert(sizeof(sshash_streaming_report) == 6 * sizeof(uint64_t), "a row is six words");
+        streaming_report total;
+        uint64_t first_read = 0;
+        std::vector<sshash_streaming_report> rows;
+        for_each_batch(in, [&](read_batch const& batch) {
+            const uint64_t n = batch.num_reads();
+            if (n == 0) return;
+            rows.resize(n);
+            total += d->eng->streaming_query_per_read_host(batch.bases.data(), batch.offsets.data(), n, reinterpret_cast<uint64_t*>(rows.data()));
+            if (report) fill_report(report, total);
+            const int stop = fn(ctx, first_read, n, rows.data());
+            if (stop) throw error(error_kind::argument, "the per-read callback returned " + std::to_string(stop));
+            first_read += n;
+        });
     });
 }
 
@@ -480,6 +515,26 @@ sshash_status sshash_streaming_query_device(const sshash_dict* d, int device, co
                                             uint64_t* report, void* hip_stream) {
     if (!d || !report || (num_reads && (!bases || !read_offsets))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
     return guarded([&] { d->eng->streaming_query_device(device, bases, read_offsets, num_reads, total_bases, report, hip_stream); });
+}
+
+sshash_status sshash_streaming_query_per_read_device(const sshash_dict* d, int device, const char* bases,
+                                                     const uint64_t* read_offsets, uint64_t num_reads, uint64_t total_bases,
+                                                     sshash_streaming_report* per_read, uint64_t* report, void* hip_stream) {
+    if (!d || (num_reads && (!bases || !read_offsets || !per_read))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] {
+        d->eng->streaming_query_per_read_device(device, bases, read_offsets, num_reads, total_bases, reinterpret_cast<uint64_t*>(per_read), report, hip_stream);
+    });
+}
+
+sshash_status sshash_streaming_query_per_read(const sshash_dict* d, const char* bases, const uint64_t* read_offsets,
+                                              uint64_t num_reads, sshash_streaming_report* per_read,
+                                              sshash_streaming_report* report) {
+    if (!d || (num_reads && (!bases || !read_offsets || !per_read))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (report) std::memset(report, 0, sizeof(*report));
+    return guarded([&] {
+        const streaming_report r = d->eng->streaming_query_per_read_host(bases, read_offsets, num_reads, reinterpret_cast<uint64_t*>(per_read));
+        if (report) fill_report(report, r);
+    });
 }
 
 sshash_status sshash_streaming_lookup_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,

@@ -118,6 +118,10 @@ public:
     /* Batched streaming query over `n_reads` reads stored back to back in `bases`
        (read r = bases[read_offsets[r] .. read_offsets[r+1])). Host buffers. */
     streaming_report streaming_query_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads) const;
+    /* The same with one report PER READ: `rows` (host, n_reads x 6 words in the order of the device report, row r for read r; null:
+       the totals only) is overwritten; returns the totals. A piece that holds a read above 2^16 bases takes the position-parallel
+       pipeline, the others the run kernel; both give the same rows. */
+    streaming_report streaming_query_per_read_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* rows) const;
     /* An uncompressed FASTQ file, read and parsed by the lanes themselves (reads.hpp: fastq_pieces): every lane takes pieces of
        the file from a shared counter, parses a piece straight into its pinned block, uploads it and runs the streaming
        kernels -- no single reader thread, no intermediate batch. Returns false when the file turned out not to be four lines
@@ -126,13 +130,18 @@ public:
     /* Device buffers, asynchronous; `d_report` receives 6 u64 counters (accumulated). */
     void streaming_query_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
                                 uint64_t total_bases, uint64_t* d_report, void* stream) const;
+    /* Device buffers, asynchronous, always the run kernel; `d_rows` (n_reads x 6 words) is overwritten, every row of it; `d_report`
+       (nullable) is accumulated into. */
+    void streaming_query_per_read_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
+                                         uint64_t total_bases, uint64_t* d_rows, uint64_t* d_report, void* stream) const;
 
     /* Per-k-mer results of the streaming query (streaming_query::lookup for every k-mer of every read,
        include/streaming_query.hpp:56-109): entry read_offsets[r] + j of every non-null array of `d_out` = the k-mer
        starting at base j of read r; places where no k-mer starts are left untouched. `d_report` (nullable): the six
        counters, accumulated. Device buffers, asynchronous. */
     void streaming_lookup_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
-                                 uint64_t total_bases, result_view const& d_out, uint64_t* d_report, void* stream) const;
+                                 uint64_t total_bases, result_view const& d_out, uint64_t* d_report, void* stream,
+                                 uint64_t* d_rows = nullptr /* one report per read, n_reads x 6 words, ADDED to */) const;
     streaming_report streaming_lookup_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads,
                                            result_view const& h_out) const;
 

@@ -238,7 +238,7 @@ struct line_reader {
     }
 };
 
-void push_read(read_batch& out, char const* s, size_t n, uint32_t k) {
+void push_read(read_batch& out, char const* s, size_t n, uint32_t k) {  // (k = 0: every record)
     if (n < k) return;
     out.bases.insert(out.bases.end(), s, s + n);
     out.offsets.push_back(out.bases.size());
@@ -249,13 +249,13 @@ void push_read(read_batch& out, char const* s, size_t n, uint32_t k) {
 struct read_stream::impl {
     line_reader in;
     enum { FASTQ, FASTA, FASTA_MULTILINE } format;
-    uint32_t k;
+    uint32_t k;  // reads below this length are dropped (0 with every_record)
     bool done = false;
     std::string segment;
     impl(std::string const& filename, int fmt, uint32_t k_) : in(filename), format(decltype(format)(fmt)), k(k_) {}
 };
 
-read_stream::read_stream(std::string const& filename, bool multiline, uint32_t k) {
+read_stream::read_stream(std::string const& filename, bool multiline, uint32_t k, bool every_record) {
     const bool fasta = ends_with(filename, ".fa") || ends_with(filename, ".fasta") || ends_with(filename, ".fa.gz") ||
                        ends_with(filename, ".fasta.gz");
     const bool fastq = ends_with(filename, ".fq") || ends_with(filename, ".fastq") || ends_with(filename, ".fq.gz") ||
@@ -265,7 +265,7 @@ read_stream::read_stream(std::string const& filename, bool multiline, uint32_t k
         line_reader probe(filename);
         return;
     }
-    m = std::make_unique<impl>(filename, fastq ? impl::FASTQ : multiline ? impl::FASTA_MULTILINE : impl::FASTA, k);
+    m = std::make_unique<impl>(filename, fastq ? impl::FASTQ : multiline ? impl::FASTA_MULTILINE : impl::FASTA, every_record ? 0 : k);
 }
 
 read_stream::~read_stream() = default;
@@ -278,7 +278,8 @@ bool read_stream::next(read_batch& out, uint64_t max_bases) {
     if (max_bases < (uint64_t(1) << 32)) out.bases.reserve(size_t(max_bases) + (size_t(1) << 16));
     char const* p = nullptr;
     size_t n = 0;
-    while (out.bases.size() < max_bases) {
+    /* (every record: a file of records without bases would never fill a batch by its bases; 2^22 records end one as well) */
+    while (out.bases.size() < max_bases && (r.k || out.offsets.size() <= (size_t(1) << 22))) {
         if (r.format == impl::FASTQ) {
             if (!r.in.skip() || !r.in.next(p, n)) { r.done = true; break; }  // header, bases
             push_read(out, p, n, r.k);
@@ -288,14 +289,15 @@ bool read_stream::next(read_batch& out, uint64_t max_bases) {
             if (!r.in.skip() || !r.in.next(p, n)) { r.done = true; break; }
             push_read(out, p, n, r.k);
         } else {
+            /* (every record: an empty segment -- two empty lines in a row, the end of the file behind one -- is no record) */
             if (!r.in.next(p, n)) {
-                push_read(out, r.segment.data(), r.segment.size(), r.k);
+                if (r.k || !r.segment.empty()) push_read(out, r.segment.data(), r.segment.size(), r.k);
                 r.segment.clear();
                 r.done = true;
                 break;
             }
             if (n == 0) {
-                push_read(out, r.segment.data(), r.segment.size(), r.k);
+                if (r.k || !r.segment.empty()) push_read(out, r.segment.data(), r.segment.size(), r.k);
                 r.segment.clear();
             } else {
                 r.segment.append(p, n);

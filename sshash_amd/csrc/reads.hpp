@@ -9,7 +9,8 @@
 // Format is chosen by file extension (.fa/.fasta/.fq/.fastq, optionally .gz)  :131-171. A .gz is read through zlib (one
 // thread: a deflate stream does not split); a BGZF file (bgzip: gzip members with their size in the header -- any gzip reader,
 // the reference's included, reads it as a .gz) is recognised by its first header and inflated member by member on all cores.
-// Reads shorter than k are dropped here (they contribute no k-mer: :63,:92).
+// Reads shorter than k are dropped here (they contribute no k-mer: :63,:92) -- unless the caller asks for every record
+// (read_stream's `every_record`: the per-read query reports on record i of the file in row i, so no record may go missing).
 #pragma once
 
 #include <cstdint>
@@ -29,7 +30,9 @@ struct read_batch {
    `max_bases` or beyond): a query file of hundreds of gigabytes never sits in host memory as a whole. */
 class read_stream {
 public:
-    read_stream(std::string const& filename, bool multiline, uint32_t k);  // throws when the file cannot be opened
+    /* every_record: reads shorter than k are handed out as well (an empty sequence line included; a multiline FASTA segment is a
+       record when it holds anything at all), in file order with the others */
+    read_stream(std::string const& filename, bool multiline, uint32_t k, bool every_record = false);  // throws when the file cannot be opened
     ~read_stream();
     bool supported() const { return bool(m); }  // false: the extension is not a supported format
     /* false once the file is exhausted and `out` holds nothing */

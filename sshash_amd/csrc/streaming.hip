@@ -10,8 +10,8 @@
 // remaining == 0. The negative short-cut (:150-157) becomes "the k-mers behind a miss that elect the
 // same table key, and cannot be in that key's slot either, are negative too" -- the same k-mers are
 // negative either way, so the counters are unchanged.
-// Output: the six counters of streaming_query_report (include/util.hpp:21-36); per-k-mer results:
-// the position-parallel pipeline further down.
+// Output: the six counters of streaming_query_report (include/util.hpp:21-36), for the batch or -- the kernel's PER_READ form -- for every
+// read on its own; per-k-mer results: the position-parallel pipeline further down.
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
 
@@ -248,13 +248,43 @@ __device__ __forceinline__ uint64_t extend_run(dict_view const& d, const uint64_
     return run;
 }
 
+/* (the per-read form of the kernel below) the lane's counters into its read's row: stored, or -- `partial`: the row already holds a part
+   of the read's counts -- added to what went there before; the counters start again at zero */
+__device__ __forceinline__ void row_flush(uint64_t* __restrict__ row, bool partial, uint32_t& c_invalid, uint32_t& c_negative, uint32_t& c_searches,
+                                          uint32_t& c_extensions) {
+    const uint64_t s = c_searches, e = c_extensions;
+    if (partial) {
+        row[1] += s + e;
+        row[2] += c_negative;
+        row[3] += c_invalid;
+        row[4] += s;
+        row[5] += e;
+    } else {
+        row[1] = s + e;
+        row[2] = c_negative;
+        row[3] = c_invalid;
+        row[4] = s;
+        row[5] = e;
+    }
+    c_invalid = c_negative = c_searches = c_extensions = 0;
+}
+
 /* (five waves a SIMD: 96 registers. Round 5's steps there, same-box: k <= 31 four -> five waves 110 -> 126 G k-mers/s; k <= 63, once 32-bit
    counters and a run measurement without early loads had made room, 138 -> 147 with 20 bytes of scratch. Compiled for six: 14 / 31 % slower,
    profiles/r05/streaming_run_kernel_waves_per_simd_ab.txt.) */
 #ifndef SSHASH_STREAM_WAVES
 #define SSHASH_STREAM_WAVES 5
 #endif
-template <int W, bool CANON, bool SK>
+/* PER_READ: one streaming_query_report PER READ instead of one for the batch -- `report` is then the array of ROWS, six words a read
+   in the order of the batch's report (num_kmers, positive, negative, invalid, searches, extensions), row r for read r. The lane that
+   takes read r owns row r until it takes its next read, and every counter it bumps in between belongs to that read: the row is
+   written by that lane alone, with plain stores, no atomics. num_kmers is stored at the hand-out, the other five when the read is
+   done (the lane's 32-bit counters are then exactly the read's). The two ways a count leaves the lane's counters early -- the move-out
+   every `move_out_every` turns, and a run or a stretch of invalid k-mers of 2^15 and more -- put it into the row early instead, and
+   mark the row (ROW_PARTIAL): what follows is ADDED to such a row (a load, an add, a store -- a dependent round trip that the common
+   read never pays). A read shorter than k gets its six zeros at the hand-out and is never anybody's. No batch totals here: they are
+   the column sums of the rows (stream_rows_sum_kernel). */
+template <int W, bool CANON, bool SK, bool PER_READ>
 __global__ void __launch_bounds__(256, SSHASH_STREAM_WAVES)
 streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, const uint64_t* __restrict__ packed,
                      const uint64_t* __restrict__ okay, const uint64_t* __restrict__ offsets, const uint64_t n_reads,
@@ -268,7 +298,9 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
     const uint32_t k = d.k;
     const uint32_t lane = threadIdx.x & 63u;
     unsigned long long* const wave_moved_out = moved_out[threadIdx.x >> 6];
-    if (lane < 5) wave_moved_out[lane] = 0;
+    if constexpr (!PER_READ) {
+        if (lane < 5) wave_moved_out[lane] = 0;
+    }
     /* this wave's share of the reads, handed out in order to whichever lane is done with its read */
     const uint64_t wave = uint64_t(blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);
     uint64_t next = wave * reads_per_wave, last = next + reads_per_wave;
@@ -300,6 +332,11 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
     uint64_t on = 0, on_a = 0;
     uint32_t where = 0;
     uint32_t turns = 0;
+    /* (PER_READ) the read this lane is on, counted from the wave's first -- one register: a wave's share is far below 2^31 reads --, and
+       whether its row already holds a part of its counts */
+    constexpr uint32_t ROW_NONE = ~0u, ROW_PARTIAL = 1u << 31;
+    uint32_t my_row = ROW_NONE;
+    uint64_t* const wave_rows = report + wave * reads_per_wave * 6;  // (PER_READ) the row of the wave's first read
 #ifdef SSHASH_STREAM_STATS
     /* (a debug build, tools/jobs/r06_stream_stats.sh: what the lanes of a wave do per turn -- wave-level sums in scalar registers, out
        through report[6 ..]; the caller's report has 16 entries then) */
@@ -315,14 +352,21 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
 #endif
         if (++turns >= move_out_every) {  // (scalar; a turn adds less than 2^15 to a lane's counter -- a longer run of extensions or of invalid k-mers goes to the wave's 64-bit totals at once --, so 2^16 turns stay below 2^31)
             turns = 0;
-            const uint64_t i = wave_sum(c_invalid), n = wave_sum(c_negative), f = wave_sum(c_searches), e = wave_sum(c_extensions);
-            if (lane == 0) {
-                wave_moved_out[0] += i;
-                wave_moved_out[1] += n;
-                wave_moved_out[2] += f;
-                wave_moved_out[3] += e;
+            if constexpr (PER_READ) {
+                if (my_row != ROW_NONE) {
+                    row_flush(wave_rows + uint64_t(my_row & ~ROW_PARTIAL) * 6, (my_row & ROW_PARTIAL) != 0, c_invalid, c_negative, c_searches, c_extensions);
+                    my_row |= ROW_PARTIAL;
+                }
+            } else {
+                const uint64_t i = wave_sum(c_invalid), n = wave_sum(c_negative), f = wave_sum(c_searches), e = wave_sum(c_extensions);
+                if (lane == 0) {
+                    wave_moved_out[0] += i;
+                    wave_moved_out[1] += n;
+                    wave_moved_out[2] += f;
+                    wave_moved_out[3] += e;
+                }
+                c_invalid = c_negative = c_searches = c_extensions = 0;
             }
-            c_invalid = c_negative = c_searches = c_extensions = 0;
         }
         /* -- the run behind the hit of the turn before, THEN this turn's seed (round 6): the lane measures its run and goes straight on to
               whatever lies behind it in the same turn -- the negative over the substitution that ended the run, as a rule; the NEXT READ when
@@ -335,8 +379,19 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
         if (pending) {
             const uint64_t b = cur + k - 1, valid_end = inv < rd_end ? inv : rd_end;
             const uint64_t run = extend_run<W>(d, packed, off, ori, b, valid_end - b, run_step_load<W>(d, packed, off, ori > 0, b, 0));
-            if (run >> 15) atomicAdd(wave_moved_out + 3, (unsigned long long)run);  // (past what the lane's 32-bit counter may take in one turn: 2^16 turns lie between two move-outs)
-            else c_extensions += uint32_t(run);
+            if (run >> 15) {  // (past what the lane's 32-bit counter may take in one turn: 2^16 turns lie between two move-outs)
+                if constexpr (PER_READ) {  // (into the row at once, behind what the lane has counted for it so far)
+                    uint64_t* const row = wave_rows + uint64_t(my_row & ~ROW_PARTIAL) * 6;
+                    row_flush(row, (my_row & ROW_PARTIAL) != 0, c_invalid, c_negative, c_searches, c_extensions);
+                    my_row |= ROW_PARTIAL;
+                    row[1] += run;
+                    row[5] += run;
+                } else {
+                    atomicAdd(wave_moved_out + 3, (unsigned long long)run);
+                }
+            } else {
+                c_extensions += uint32_t(run);
+            }
             cur += run;
             if (run) where &= ~WALK_HEAVY_FIELDS;  // (the k-mer behind a run elects a key of its own)
         }
@@ -344,13 +399,30 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
         /* -- the reads: whoever has none left takes the next of the wave's share -- */
         const bool want = !walking && cur + k > rd_end;
         const uint64_t wants = __ballot(want);
+        if constexpr (PER_READ) {
+            if (want && my_row != ROW_NONE) {  // (not walking, no k-mer left, the run behind the last hit measured above: the read is done)
+                row_flush(wave_rows + uint64_t(my_row & ~ROW_PARTIAL) * 6, (my_row & ROW_PARTIAL) != 0, c_invalid, c_negative, c_searches, c_extensions);
+                my_row = ROW_NONE;
+            }
+        }
         if (wants != 0 && next < last) {
             const uint64_t rank = uint64_t(__popcll(wants & ((uint64_t(1) << lane) - 1)));
             if (want && rank < last - next) {
                 const uint64_t r = next + rank;
                 cur = offsets[r];
                 rd_end = offsets[r + 1];
-                if (rd_end - cur >= k) atomicAdd(wave_moved_out + 4, (unsigned long long)(rd_end - cur - k + 1));
+                if constexpr (PER_READ) {
+                    uint64_t* const row = report + r * 6;
+                    const uint64_t kmers = rd_end - cur >= k ? rd_end - cur - k + 1 : 0;
+                    row[0] = kmers;
+                    if (kmers) {
+                        my_row = uint32_t(r - wave * reads_per_wave);
+                    } else {  // (nothing will ever be counted for it: the whole row now)
+                        row[1] = row[2] = row[3] = row[4] = row[5] = 0;
+                    }
+                } else {
+                    if (rd_end - cur >= k) atomicAdd(wave_moved_out + 4, (unsigned long long)(rd_end - cur - k + 1));
+                }
                 inv = first_invalid_base(okay, cur, rd_end);
                 neg_unknown_mini = false;
                 where = 0;
@@ -372,8 +444,18 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
             const uint64_t over = last_over_it - cur + 1;
             /* (a turn may add 2^15 - 1 to a lane's 32-bit counter and no more -- 2^16 turns lie between two move-outs --; this loop
                can cross a whole read in one turn, so what it adds is bounded by the loop's own sum, kept here) */
-            if ((over + c_invalid_turn) >> 15) atomicAdd(wave_moved_out + 0, (unsigned long long)over);
-            else c_invalid_turn += uint32_t(over);
+            if ((over + c_invalid_turn) >> 15) {
+                if constexpr (PER_READ) {
+                    uint64_t* const row = wave_rows + uint64_t(my_row & ~ROW_PARTIAL) * 6;
+                    row_flush(row, (my_row & ROW_PARTIAL) != 0, c_invalid, c_negative, c_searches, c_extensions);
+                    my_row |= ROW_PARTIAL;
+                    row[3] += over;
+                } else {
+                    atomicAdd(wave_moved_out + 0, (unsigned long long)over);
+                }
+            } else {
+                c_invalid_turn += uint32_t(over);
+            }
             cur = nv;
             inv = first_invalid_base(okay, nv, rd_end);
             neg_unknown_mini = false;
@@ -561,20 +643,40 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
     }
 #ifdef SSHASH_STREAM_STATS
     const unsigned long long st_neg_kept = wave_sum(st_kept_lane);
-    if (lane == 0) {
+    if (lane == 0 && !PER_READ) {  // (the statistics are the six-counter kernel's: `report` is rows otherwise)
         unsigned long long* st = reinterpret_cast<unsigned long long*>(report) + 6;
         atomicAdd(st + 0, st_turns); atomicAdd(st + 1, st_fresh); atomicAdd(st + 2, st_walk); atomicAdd(st + 3, st_ext); atomicAdd(st + 4, st_slot1);
         atomicAdd(st + 5, st_inv); atomicAdd(st + 6, st_idle); atomicAdd(st + 7, st_full); atomicAdd(st + 8, st_neg_kept); atomicAdd(st + 9, st_short);
     }
 #endif
-    const bool first = lane == 0;  // (what the wave moved out is added once)
-    block_report(first ? wave_moved_out[4] : 0, uint64_t(c_invalid) + (first ? wave_moved_out[0] : 0), uint64_t(c_negative) + (first ? wave_moved_out[1] : 0),
-                 uint64_t(c_searches) + (first ? wave_moved_out[2] : 0), uint64_t(c_extensions) + (first ? wave_moved_out[3] : 0), report);
+    if constexpr (PER_READ) {
+        if (my_row != ROW_NONE) row_flush(wave_rows + uint64_t(my_row & ~ROW_PARTIAL) * 6, (my_row & ROW_PARTIAL) != 0, c_invalid, c_negative, c_searches, c_extensions);  // (no lane gets here with a read: whoever is not live has handed its row in above)
+    } else {
+        const bool first = lane == 0;  // (what the wave moved out is added once)
+        block_report(first ? wave_moved_out[4] : 0, uint64_t(c_invalid) + (first ? wave_moved_out[0] : 0), uint64_t(c_negative) + (first ? wave_moved_out[1] : 0),
+                     uint64_t(c_searches) + (first ? wave_moved_out[2] : 0), uint64_t(c_extensions) + (first ? wave_moved_out[3] : 0), report);
+    }
+}
+
+/* the batch's six counters out of the rows of its reads: column sums, accumulated into `report` (one set of atomics a workgroup) */
+__global__ void __launch_bounds__(256)
+stream_rows_sum_kernel(const uint64_t* __restrict__ rows, const uint64_t n_reads, uint64_t* __restrict__ report) {
+    uint64_t c_kmers = 0, c_invalid = 0, c_negative = 0, c_searches = 0, c_extensions = 0;
+    const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
+    for (uint64_t r = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; r < n_reads; r += stride) {
+        const uint64_t* row = rows + 6 * r;
+        c_kmers += row[0];
+        c_negative += row[2];
+        c_invalid += row[3];
+        c_searches += row[4];
+        c_extensions += row[5];
+    }
+    block_report(c_kmers, c_invalid, c_negative, c_searches, c_extensions, report);
 }
 
 template <int W, bool CANON>
 void launch_streaming_runs(device_replica const* rep, dict_view const& d, char const* bases, uint64_t const* offsets, uint64_t n_reads,
-                           uint64_t total_bases, uint64_t* report, hipStream_t s) {
+                           uint64_t total_bases, uint64_t* report, hipStream_t s, uint64_t* rows = nullptr /* per read: n_reads x 6 words; `report` may then be null */) {
     /* two bits and a validity bit a base, in words of 32 and 64 bases; three words of slack behind the last base (a seed and a
        run read up to two words past their first) */
     const uint64_t packed_bytes = ((total_bases + 31) / 32 + 3) * 8, okay_bytes = ((total_bases + 63) / 64 + 2) * 8;
@@ -597,8 +699,20 @@ void launch_streaming_runs(device_replica const* rep, dict_view const& d, char c
     const uint64_t reads_per_wave = (n_reads + waves - 1) / waves;
     const dim3 grid(uint32_t(waves / 4)), block(256);
     const uint32_t move_out_every = uint32_t(test_hook_u64("stream_move_out_every", uint64_t(1) << 16, 1, uint64_t(1) << 16));
-    if (d.sk.enabled) hipLaunchKernelGGL((streaming_run_kernel<W, CANON, true>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, report);
-    else hipLaunchKernelGGL((streaming_run_kernel<W, CANON, false>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, report);
+    if (rows) {
+        if (reads_per_wave >> 31) throw error(error_kind::argument, "too many reads for one call");  // (a lane keeps its read's index in its wave's share in 31 bits)
+        if (d.sk.enabled) hipLaunchKernelGGL((streaming_run_kernel<W, CANON, true, true>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, rows);
+        else hipLaunchKernelGGL((streaming_run_kernel<W, CANON, false, true>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, rows);
+        HIP_CHECK(hipGetLastError());
+        if (report) {
+            const uint32_t blocks = uint32_t(std::min<uint64_t>((n_reads + 255) / 256, 1024));
+            hipLaunchKernelGGL(stream_rows_sum_kernel, dim3(blocks), dim3(256), 0, s, rows, n_reads, report);
+            HIP_CHECK(hipGetLastError());
+        }
+        return;
+    }
+    if (d.sk.enabled) hipLaunchKernelGGL((streaming_run_kernel<W, CANON, true, false>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, report);
+    else hipLaunchKernelGGL((streaming_run_kernel<W, CANON, false, false>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, report);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -623,6 +737,31 @@ void engine::streaming_query_device(int device, char const* d_bases, uint64_t co
     else if (!wide && d.canonical) launch_streaming_runs<1, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s);
     else if (wide && !d.canonical) launch_streaming_runs<2, false>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s);
     else launch_streaming_runs<2, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s);
+}
+
+/* One report per read, by the run kernel whatever the reads' lengths (a caller with device buffers has cut its batch itself, as with
+   streaming_query_device). Every row is written: also when no base is there to look at. */
+void engine::streaming_query_per_read_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
+                                             uint64_t total_bases, uint64_t* d_rows, uint64_t* d_report, void* stream) const {
+    device_replica const* rep = replica(device);
+    if (n_reads == 0) return;
+    if (!d_rows) throw error(error_kind::argument, "per-read output pointer is null");
+    device_guard guard(device);
+    dict_view const& d = rep->view;
+    hipStream_t s = hipStream_t(stream);
+    const bool wide = d.k > 31;
+    if (total_bases == 0) {
+        HIP_CHECK(hipMemcpyAsync(&total_bases, d_read_offsets + n_reads, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (total_bases == 0) {  // empty reads only: their rows are zero
+            HIP_CHECK(hipMemsetAsync(d_rows, 0, n_reads * 6 * sizeof(uint64_t), s));
+            return;
+        }
+    }
+    if (!wide && !d.canonical) launch_streaming_runs<1, false>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, d_rows);
+    else if (!wide && d.canonical) launch_streaming_runs<1, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, d_rows);
+    else if (wide && !d.canonical) launch_streaming_runs<2, false>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, d_rows);
+    else launch_streaming_runs<2, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, d_rows);
 }
 
 /* ---- per-k-mer results: the streaming query as a position-parallel pipeline -----------------------------------
@@ -811,10 +950,64 @@ stream_classify_kernel(const uint8_t* __restrict__ flags, const uint64_t total_b
     block_report(c_kmer, c_invalid, c_negative, c_search, c_extension, report);
 }
 
+/* The classification once more, into one report PER READ: one lane per place; rows[6 r ..] += what the k-mers of read r add to the six
+   counters (the rows are zeroed by the caller). A read of a megabase is a million lanes on one row, so the lanes of a wave first sum
+   over their runs of equal read: a run begins at the wave's first k-mer and at every k-mer that is the first of its read (a k-mer
+   belongs to the read of the k-mer before it unless it is marked SQ_FIRST; places without a k-mer add nothing and need no read), what
+   a k-mer adds to a counter is one bit, so a run's sum is a ballot, masked by the run's lanes and counted, and the run's first lane --
+   the only one to look its read up in the offsets -- adds the sums that are not zero: at most one atomic per wave, read and counter. */
+__global__ void __launch_bounds__(256)
+stream_classify_rows_kernel(const uint8_t* __restrict__ flags, const uint64_t total_bases, const uint64_t* __restrict__ kmer_id,
+                            const uint64_t* __restrict__ string_id, const int8_t* __restrict__ orientation,
+                            const uint64_t* __restrict__ offsets, const uint64_t n_reads, uint64_t* __restrict__ rows) {
+    const uint64_t p = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint8_t f = p < total_bases ? flags[p] : uint8_t(0);
+    const bool has = (f & (SQ_VALID | SQ_INVALID)) != 0, invalid = (f & SQ_INVALID) != 0;
+    bool negative = false, search = false, extension = false;
+    if (!invalid && (f & SQ_VALID)) {
+        const uint64_t id = kmer_id[p];
+        if (id == INVALID_U64) {
+            negative = true;
+        } else {
+            if (!(f & SQ_FIRST) && p > 0 && (flags[p - 1] & SQ_VALID)) {  // (as stream_classify_kernel)
+                const uint64_t before = kmer_id[p - 1];
+                extension = before != INVALID_U64 && string_id[p - 1] == string_id[p] && id == before + uint64_t(int64_t(orientation[p - 1]));
+            }
+            search = !extension;
+        }
+    }
+    const uint64_t have = __ballot(has);
+    if (have == 0) return;  // (uniform)
+    const uint64_t below = (uint64_t(1) << lane) - 1;
+    const bool head = has && ((f & SQ_FIRST) || (have & below) == 0);
+    const uint64_t heads = __ballot(head);
+    const uint64_t m_invalid = __ballot(invalid), m_negative = __ballot(negative), m_search = __ballot(search), m_extension = __ballot(extension);
+    if (!head) return;
+    const uint64_t above = (heads >> lane) >> 1;  // the heads behind this lane
+    const uint32_t end = above ? lane + 1 + uint32_t(__builtin_ctzll(above)) : 64u;
+    const uint64_t mine = (end == 64 ? ~uint64_t(0) : (uint64_t(1) << end) - 1) & ~below;  // the lanes of my run
+    uint64_t lo = 0, hi = n_reads - 1;  // my read: the largest r with offsets[r] <= p
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (offsets[mid] <= p) lo = mid;
+        else hi = mid - 1;
+    }
+    unsigned long long* const row = reinterpret_cast<unsigned long long*>(rows + 6 * lo);
+    const unsigned long long n_kmers = __popcll(have & mine), n_invalid = __popcll(m_invalid & mine), n_negative = __popcll(m_negative & mine),
+                             n_search = __popcll(m_search & mine), n_extension = __popcll(m_extension & mine);
+    atomicAdd(row + 0, n_kmers);
+    if (n_search + n_extension) atomicAdd(row + 1, n_search + n_extension);
+    if (n_negative) atomicAdd(row + 2, n_negative);
+    if (n_invalid) atomicAdd(row + 3, n_invalid);
+    if (n_search) atomicAdd(row + 4, n_search);
+    if (n_extension) atomicAdd(row + 5, n_extension);
+}
+
 void engine::streaming_lookup_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
-                                     uint64_t total_bases, result_view const& d_out, uint64_t* d_report, void* stream) const {
+                                     uint64_t total_bases, result_view const& d_out, uint64_t* d_report, void* stream, uint64_t* d_rows) const {
     device_replica const* rep = replica(device);
-    if (!d_out.kmer_id && !d_report) throw error(error_kind::argument, "neither a kmer_id array nor a report to fill");
+    if (!d_out.kmer_id && !d_report && !d_rows) throw error(error_kind::argument, "neither a kmer_id array nor a report to fill");
     if (d_out.minimizer_found) throw error(error_kind::argument, "the streaming lookup does not report minimizer_found");
     if (n_reads == 0 || total_bases == 0) return;
     device_guard guard(device);
@@ -851,6 +1044,11 @@ void engine::streaming_lookup_device(int device, char const* d_bases, uint64_t c
         const uint64_t count = std::min<uint64_t>(uint64_t(1) << 30, total_bases - first);
         hipLaunchKernelGGL(stream_classify_kernel, dim3(uint32_t(std::min<uint64_t>((count + 1023) / 1024, 2048))), dim3(256), 0, s, flags + first, count,
                            advance(out, first), sid + first, ori + first, d_report, first != 0);
+        HIP_CHECK(hipGetLastError());
+    }
+    if (d_rows) {
+        hipLaunchKernelGGL(stream_classify_rows_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, flags, total_bases, ids, sid, ori,
+                           d_read_offsets, n_reads, d_rows);
         HIP_CHECK(hipGetLastError());
     }
 }
@@ -922,11 +1120,18 @@ streaming_report engine::streaming_lookup_host(char const* bases, uint64_t const
 constexpr uint64_t LONG_READ_BASES = uint64_t(1) << 16;
 
 streaming_report engine::streaming_query_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads) const {
+    return streaming_query_per_read_host(bases, read_offsets, n_reads, nullptr);
+}
+
+/* The same pieces and lanes; with `rows` (n_reads x 6 words, host) a lane's device block also holds a row for every read of the largest
+   piece, and a piece's rows come back into the caller's array at the piece's first read. */
+streaming_report engine::streaming_query_per_read_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* rows) const {
     if (n_reads == 0) return {};
     const std::vector<int> devs = resident_devices(*this);
     const uint64_t G = devs.size();
     /* pieces: [first read, last read) with a bounded number of bases (a single longer read is its own piece) */
-    const uint64_t piece_bases = uint64_t(32) << 20, piece_reads = uint64_t(1) << 20;
+    const uint64_t piece_bases = uint64_t(32) << 20;
+    const uint64_t piece_reads = test_hook_u64("stream_piece_reads", uint64_t(1) << 20, 1, uint64_t(1) << 20);  // (tests: seams between pieces inside a small batch)
     std::vector<uint64_t> cuts{0};
     uint64_t max_bases = 0, max_reads = 0;
     for (uint64_t at = 0; at < n_reads;) {
@@ -941,7 +1146,8 @@ streaming_report engine::streaming_query_host(char const* bases, uint64_t const*
     const uint64_t off_bytes = (max_reads + 1) * sizeof(uint64_t);
     const uint64_t bases_at = (off_bytes + 255) & ~uint64_t(255);
     const uint64_t report_at = (bases_at + max_bases + 255) & ~uint64_t(255);
-    const uint64_t lane_bytes = report_at + 6 * sizeof(uint64_t);
+    const uint64_t rows_at = (report_at + 6 * sizeof(uint64_t) + 255) & ~uint64_t(255);
+    const uint64_t lane_bytes = rows ? rows_at + max_reads * 6 * sizeof(uint64_t) : report_at + 6 * sizeof(uint64_t);
 
     std::atomic<uint64_t> next{0};
     const uint64_t hw = std::max(1u, std::thread::hardware_concurrency());
@@ -969,9 +1175,20 @@ streaming_report engine::streaming_query_host(char const* bases, uint64_t const*
                lane busy for minutes; such pieces go through the position-parallel pipeline, which gives the same counters */
             bool long_read = false;
             for (uint64_t i = first; i < last && !long_read; ++i) long_read = read_offsets[i + 1] - read_offsets[i] > LONG_READ_BASES;
-            if (long_read) streaming_lookup_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, result_view{}, d_report, s);
-            else streaming_query_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, d_report, s);
+            if (rows) {
+                uint64_t* d_rows = reinterpret_cast<uint64_t*>(dp + rows_at);
+                const uint64_t row_bytes = (last - first) * 6 * sizeof(uint64_t);
+                if (long_read || nb == 0) HIP_CHECK(hipMemsetAsync(d_rows, 0, row_bytes, s));  // (the classify pass adds to its rows; no bases: no kernel at all)
+                if (long_read) streaming_lookup_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, result_view{}, d_report, s, d_rows);
+                else if (nb) streaming_query_per_read_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, d_rows, d_report, s);
+                HIP_CHECK(hipMemcpyAsync(hp + rows_at, d_rows, row_bytes, hipMemcpyDeviceToHost, s));  // (through the lane's pinned block: the caller's array is pageable)
+            } else if (long_read) {
+                streaming_lookup_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, result_view{}, d_report, s);
+            } else {
+                streaming_query_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, d_report, s);
+            }
             HIP_CHECK(hipStreamSynchronize(s));  // the pinned block is reused by the next piece
+            if (rows) std::memcpy(rows + 6 * first, hp + rows_at, (last - first) * 6 * sizeof(uint64_t));
         }
         partial[li] = read_back(d_report, s);
     });
