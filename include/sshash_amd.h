@@ -283,6 +283,50 @@ typedef int (*sshash_per_read_fn)(void* ctx, uint64_t first_read, uint64_t n, co
 sshash_status sshash_streaming_query_from_file_per_read(const sshash_dict* d, const char* filename, int multiline,
                                                         sshash_per_read_fn fn, void* ctx, sshash_streaming_report* report);
 
+/* ---- WHERE a read hits: the maximal runs of the streaming query (no reference counterpart as a call; it is the reference's state
+ *      machine, include/streaming_query.hpp:56-109, written down). Every positive k-mer of a read is a search or an extension; a RUN
+ *      is one search together with the extensions that follow it directly. Equivalently, on the per-k-mer results of the read: a
+ *      positive k-mer continues the run of the k-mer before it iff that k-mer is positive, lies in the same string and
+ *      kmer_id == previous kmer_id + previous orientation; otherwise it starts a run. Invalid and negative k-mers belong to no run.
+ *      So, per read, the number of runs is num_searches and the sum of the runs' lengths num_positive_kmers of the read's row of
+ *      sshash_streaming_query_per_read, and the runs give back the result of every positive k-mer exactly:
+ *      k-mer j of a run (j = 0 .. n-1) starts at base read_pos + j of the read and has kmer_id +/- j, kmer_id_in_string +/- j
+ *      (+ forward, - backward), the run's string_id and orientation -- the streaming_query::lookup results of those k-mers.
+ *      Output layout: CSR. run_offsets[num_reads + 1], run_offsets[0] = 0; the runs of read r are records run_offsets[r] ..
+ *      run_offsets[r+1], in increasing read_pos. The layout is canonical: two calls over the same reads give byte-identical
+ *      run_offsets and records. A read shorter than k, an empty read and a read without a hit have an empty range.
+ *      Preconditions and status codes as the per-read calls: a null dictionary / bases / read_offsets / run_offsets with
+ *      num_reads > 0, or runs == NULL with runs_capacity > 0, is SSHASH_ERR_ARGUMENT before anything runs; num_reads == 0 succeeds
+ *      and writes run_offsets[0] = 0 if run_offsets is not NULL. ---- */
+typedef struct sshash_streaming_run {
+    uint64_t kmer_id;            /* lookup_result::kmer_id of the run's FIRST k-mer in read order */
+    uint64_t string_id;          /* the string all k-mers of the run lie in */
+    uint64_t kmer_id_in_string;  /* lookup_result::kmer_id_in_string of that first k-mer */
+    uint32_t read_pos;           /* base of the read (0-based, relative to the read's start) where that k-mer starts */
+    uint32_t num_kmers;          /* bits 0..30: k-mers in the run (>= 1); bit 31: set = orientation backward (-1) */
+} sshash_streaming_run;
+#define SSHASH_RUN_BACKWARD 0x80000000u
+/* device buffers, asynchronous on hip_stream. run_offsets: num_reads + 1 words, OVERWRITTEN, always complete and exact whatever the
+ * capacity. runs: room for runs_capacity records; record i is written iff i < runs_capacity, nothing at or beyond
+ * runs + runs_capacity is touched; runs == NULL with runs_capacity == 0 is the counting call. The caller sees whether everything
+ * fitted from run_offsets[num_reads] <= runs_capacity (no status for it: the call only enqueues). report: 6 uint64 counters,
+ * ACCUMULATED into as sshash_streaming_query_device does; may be NULL. total_bases as for sshash_streaming_query_device.
+ * PRECONDITION: every read is shorter than 2^31 bases -- read_pos and the length in num_kmers are 31 bits wide, and this call, which
+ * only enqueues, does not look at the reads' lengths (the host call below does and refuses); a longer read gets wrapped fields. Always the
+ * run kernel, as sshash_streaming_query_per_read_device: a counting launch (the runs of every read), a prefix sum, and -- with
+ * runs_capacity > 0 -- a second launch that writes the records; scratch beyond that of sshash_streaming_query_device: 8 bytes per
+ * 4096 reads. */
+sshash_status sshash_streaming_runs_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
+                                           uint64_t num_reads, uint64_t total_bases, uint64_t* run_offsets,
+                                           sshash_streaming_run* runs, uint64_t runs_capacity, uint64_t* report, void* hip_stream);
+/* host buffers, sharded over all resident replicas like sshash_streaming_query_per_read (a piece that holds a read above 2^16 bases
+ * goes through the position-parallel pipeline of sshash_streaming_lookup and a compaction behind it, which give the same
+ * records); same capacity rule; report may be NULL. A read of 2^31 bases or more is SSHASH_ERR_ARGUMENT (read_pos / num_kmers could
+ * not hold it). */
+sshash_status sshash_streaming_runs(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
+                                    uint64_t* run_offsets, sshash_streaming_run* runs, uint64_t runs_capacity,
+                                    sshash_streaming_report* report);
+
 /* ---- streaming_query<Dict,canonical>::lookup for EVERY k-mer of every read (include/streaming_query.hpp:56-109),
  *      batched: what the reference returns k-mer by k-mer while it streams a read. Every non-NULL array of `out` has one
  *      entry per BASE of `bases` (total_bases = read_offsets[num_reads] entries): entry read_offsets[r] + j is the result

@@ -285,6 +285,28 @@ public:
         check(sshash_streaming_query_per_read_device(m_h, device, d_bases, d_read_offsets, num_reads, total_bases, d_rows, d_report, hip_stream));
     }
 
+    /* WHERE the reads hit: the maximal runs of the streaming query (sshash_streaming_runs; the record and the rule are in
+       include/sshash_amd.h). run_offsets gets num_reads + 1 entries, runs the records of read r at run_offsets[r] .. run_offsets[r + 1],
+       in increasing read_pos. Two calls: the counting one sizes `runs`. Returns the batch's report. */
+    streaming_query_report streaming_runs(char const* bases, uint64_t const* read_offsets, uint64_t num_reads,
+                                          std::vector<uint64_t>& run_offsets, std::vector<sshash_streaming_run>& runs) const {
+        run_offsets.assign(num_reads + 1, 0);
+        sshash_streaming_report s;
+        check(sshash_streaming_runs(m_h, bases, read_offsets, num_reads, run_offsets.data(), nullptr, 0, &s));
+        runs.resize(run_offsets[num_reads]);
+        if (!runs.empty()) check(sshash_streaming_runs(m_h, bases, read_offsets, num_reads, run_offsets.data(), runs.data(), runs.size(), &s));
+        return to_report(s);
+    }
+
+    /* device buffers, asynchronous on hip_stream (sshash_streaming_runs_device): d_run_offsets gets num_reads + 1 uint64 (overwritten),
+       d_runs the records below runs_capacity (null with capacity 0: the counting call), d_report -- may be null -- six counters
+       (accumulated into) */
+    void streaming_runs_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t num_reads, uint64_t total_bases,
+                               uint64_t* d_run_offsets, sshash_streaming_run* d_runs, uint64_t runs_capacity, uint64_t* d_report,
+                               void* hip_stream) const {
+        check(sshash_streaming_runs_device(m_h, device, d_bases, d_read_offsets, num_reads, total_bases, d_run_offsets, d_runs, runs_capacity, d_report, hip_stream));
+    }
+
     /* a query file, one row per record, handed over in file order: fn(first_read, rows, n) for one batch after the other; a
        non-zero return stops the query (std::runtime_error). Fn: int(uint64_t, streaming_query_report const*, uint64_t). */
     template <typename Fn>

@@ -12,22 +12,28 @@ Method names and argument meaning follow ``sshash::dictionary`` (reference
 """
 from ._binding import (  # noqa: F401
     INVALID_U64,
+    RUN_BACKWARD,
+    RUN_DTYPE,
     Dictionary,
     LookupResult,
     SSHashError,
     StreamingQueryReport,
     device_count,
     encode_kmers,
+    expand_runs,
     library_path,
 )
 
 __all__ = [
     "INVALID_U64",
+    "RUN_BACKWARD",
+    "RUN_DTYPE",
     "Dictionary",
     "LookupResult",
     "SSHashError",
     "StreamingQueryReport",
     "device_count",
     "encode_kmers",
+    "expand_runs",
     "library_path",
 ]

@@ -94,6 +94,16 @@ class _Report(C.Structure):
     ]
 
 
+# sshash_streaming_run (include/sshash_amd.h): one maximal run of a read -- a search and the extensions behind it
+RUN_DTYPE = np.dtype([("kmer_id", "<u8"), ("string_id", "<u8"), ("kmer_id_in_string", "<u8"), ("read_pos", "<u4"), ("num_kmers", "<u4")])
+RUN_BACKWARD = 0x80000000  # bit 31 of num_kmers: orientation -1
+
+
+class _Run(C.Structure):  # (the same record for ctypes: its size and offsets are checked against RUN_DTYPE by the tests)
+    _fields_ = [("kmer_id", C.c_uint64), ("string_id", C.c_uint64), ("kmer_id_in_string", C.c_uint64), ("read_pos", C.c_uint32),
+                ("num_kmers", C.c_uint32)]
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -181,6 +191,8 @@ def _load() -> C.CDLL:
         "sshash_streaming_query_per_read_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, P, P]),
         "sshash_streaming_query_per_read": (C.c_int, [P, P, P, C.c_uint64, P, C.POINTER(_Report)]),
         "sshash_streaming_query_from_file_per_read": (C.c_int, [P, C.c_char_p, C.c_int, _PerReadFn, P, C.POINTER(_Report)]),
+        "sshash_streaming_runs_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, P, C.c_uint64, P, P]),
+        "sshash_streaming_runs": (C.c_int, [P, P, P, C.c_uint64, P, P, C.c_uint64, C.POINTER(_Report)]),
         "sshash_route_packed_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P, P]),
         "sshash_route_bucket_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, C.c_int, P, P, P, P]),
         "sshash_route_bucket_by_key_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P, P, P]),
@@ -206,6 +218,7 @@ C_ABI_SYMBOLS = (
     "sshash_access_packed_device sshash_weight sshash_weight_device "
     "sshash_streaming_query_from_file sshash_streaming_query sshash_streaming_query_device "
     "sshash_streaming_query_per_read sshash_streaming_query_per_read_device sshash_streaming_query_from_file_per_read "
+    "sshash_streaming_runs sshash_streaming_runs_device "
     "sshash_streaming_lookup sshash_streaming_lookup_device sshash_sharded_lookup_device sshash_sharded_lookup_rccl "
     "sshash_route_packed_device sshash_route_bucket_device sshash_route_bucket_by_key_device sshash_route_combine_device "
     "sshash_iterate_packed sshash_iterate_packed_device sshash_check_device"
@@ -706,6 +719,37 @@ class Dictionary:
                                                               int(num_reads), int(total_bases), C.c_void_p(d_rows),
                                                               C.c_void_p(d_report), C.c_void_p(stream)))
 
+    def streaming_runs(self, reads: Sequence[Union[str, bytes]]):
+        """WHERE the reads hit -> (run_offsets, runs, StreamingQueryReport): the maximal runs of the streaming query (a run = a search and
+        the extensions behind it; sshash_streaming_runs in include/sshash_amd.h). run_offsets: len(reads) + 1 uint64, CSR; runs: a
+        RUN_DTYPE array, the records of read r at runs[run_offsets[r]:run_offsets[r + 1]] in increasing read_pos. expand_runs() gives
+        the per-k-mer results back."""
+        chunks = [s.encode("ascii", "replace") if isinstance(s, str) else bytes(s) for s in reads]
+        offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
+        if chunks:
+            offsets[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
+        bases = np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8)
+        run_offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
+        capacity = 2 * len(chunks) + 64  # a first guess; run_offsets says whether it was enough
+        while True:
+            runs = np.zeros(capacity, dtype=RUN_DTYPE)
+            r = _Report()
+            _check(_load().sshash_streaming_runs(self._h, bases.ctypes.data, offsets.ctypes.data, len(chunks), run_offsets.ctypes.data,
+                                                 runs.ctypes.data, capacity, C.byref(r)))
+            total = int(run_offsets[-1])
+            if total <= capacity:
+                return run_offsets, runs[:total], self._report(r)
+            capacity = total
+
+    def streaming_runs_device(self, device: int, d_bases: int, d_read_offsets: int, num_reads: int, d_run_offsets: int, d_runs: int,
+                              runs_capacity: int, d_report: int = 0, stream: int = 0, total_bases: int = 0) -> None:
+        """Device buffers: d_run_offsets receives num_reads + 1 uint64 (overwritten, exact whatever the capacity), d_runs the records
+        below runs_capacity (0 with capacity 0: the counting call), d_report (0: none) six counters (accumulated into).
+        `total_bases` as for streaming_query_device."""
+        _check(_load().sshash_streaming_runs_device(self._h, int(device), C.c_void_p(d_bases), C.c_void_p(d_read_offsets), int(num_reads),
+                                                    int(total_bases), C.c_void_p(d_run_offsets), C.c_void_p(d_runs), int(runs_capacity),
+                                                    C.c_void_p(d_report), C.c_void_p(stream)))
+
     def streaming_lookup(self, reads: Sequence[Union[str, bytes]], full: bool = False):
         """streaming_query::lookup for every k-mer of every read (reference include/streaming_query.hpp:56-109), batched.
         -> (list of LookupResult, one per read, len(read) - k + 1 entries each; StreamingQueryReport)."""
@@ -748,3 +792,35 @@ class Dictionary:
         eight bytes back and waits for the stream first)."""
         _check(_load().sshash_streaming_query_device(self._h, int(device), C.c_void_p(d_bases), C.c_void_p(d_read_offsets),
                                                      int(num_reads), int(total_bases), C.c_void_p(d_report), C.c_void_p(stream)))
+
+
+def expand_runs(run_offsets, runs, read_lengths, k: int):
+    """The inverse of Dictionary.streaming_runs: one LookupResult per read with len(read) - k + 1 entries each of kmer_id, string_id,
+    kmer_id_in_string and kmer_orientation -- what streaming_lookup(reads, full=True) returns in those fields for every POSITIVE k-mer;
+    k-mers outside every run are INVALID_U64 / +1. (That +1 is NOT always streaming_lookup's: for a negative k-mer the lookup reports the
+    strand of its last probe, -1 in a regular dictionary, which no run carries.) k-mer j of a run starts at base read_pos + j and has kmer_id +/- j and kmer_id_in_string +/- j (+ forward, -
+    backward), the run's string_id and orientation."""
+    run_offsets = np.asarray(run_offsets, dtype=np.uint64)
+    runs = np.asarray(runs, dtype=RUN_DTYPE)
+    if len(run_offsets) != len(read_lengths) + 1:
+        raise ValueError("run_offsets has len(read_lengths) + 1 entries")
+    out = []
+    for r, length in enumerate(read_lengths):
+        n = max(0, int(length) - int(k) + 1)
+        ids = np.full(n, INVALID_U64, dtype=np.uint64)
+        sid = np.full(n, INVALID_U64, dtype=np.uint64)
+        in_string = np.full(n, INVALID_U64, dtype=np.uint64)
+        ori = np.ones(n, dtype=np.int8)
+        for rec in runs[int(run_offsets[r]):int(run_offsets[r + 1])]:
+            count = int(rec["num_kmers"]) & 0x7FFFFFFF
+            at = int(rec["read_pos"])
+            if count == 0 or at + count > n:
+                raise ValueError(f"read {r}: a run of {count} k-mers at base {at} does not fit {n} k-mers")
+            backward = (int(rec["num_kmers"]) & RUN_BACKWARD) != 0
+            step = np.arange(count, dtype=np.uint64)
+            ids[at:at + count] = rec["kmer_id"] - step if backward else rec["kmer_id"] + step
+            in_string[at:at + count] = rec["kmer_id_in_string"] - step if backward else rec["kmer_id_in_string"] + step
+            sid[at:at + count] = rec["string_id"]
+            ori[at:at + count] = -1 if backward else 1
+        out.append(LookupResult(kmer_id=ids, kmer_id_in_string=in_string, kmer_orientation=ori, string_id=sid))
+    return out

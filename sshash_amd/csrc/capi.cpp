@@ -537,6 +537,28 @@ sshash_status sshash_streaming_query_per_read(const sshash_dict* d, const char* 
     });
 }
 
+static_assert(sizeof(sshash_streaming_run) == 32, "a run record is 32 bytes: two 16-byte stores on the device");
+
+sshash_status sshash_streaming_runs_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
+                                           uint64_t num_reads, uint64_t total_bases, uint64_t* run_offsets,
+                                           sshash_streaming_run* runs, uint64_t runs_capacity, uint64_t* report, void* hip_stream) {
+    if (!d || (num_reads && (!bases || !read_offsets || !run_offsets)) || (!runs && runs_capacity)) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] {
+        d->eng->streaming_runs_device(device, bases, read_offsets, num_reads, total_bases, run_offsets, runs, runs_capacity, report, hip_stream);
+    });
+}
+
+sshash_status sshash_streaming_runs(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
+                                    uint64_t* run_offsets, sshash_streaming_run* runs, uint64_t runs_capacity,
+                                    sshash_streaming_report* report) {
+    if (!d || (num_reads && (!bases || !read_offsets || !run_offsets)) || (!runs && runs_capacity)) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (report) std::memset(report, 0, sizeof(*report));
+    return guarded([&] {
+        const streaming_report r = d->eng->streaming_runs_host(bases, read_offsets, num_reads, run_offsets, runs, runs_capacity);
+        if (report) fill_report(report, r);
+    });
+}
+
 sshash_status sshash_streaming_lookup_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
                                              uint64_t num_reads, uint64_t total_bases, const sshash_results* out, uint64_t* report,
                                              void* hip_stream) {

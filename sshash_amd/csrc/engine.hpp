@@ -40,6 +40,14 @@ struct streaming_report {  // streaming_query_report, include/util.hpp:21-36
     }
 };
 
+/* where the runs of a streaming call go (streaming.hip), device pointers: run_offsets -- n_reads + 1 words, CSR --, the records
+   (sshash_streaming_run, include/sshash_amd.h) and how many of them there is room for */
+struct run_sink {
+    uint64_t* run_offsets;
+    void* records;
+    uint64_t capacity;
+};
+
 class engine {
 public:
     explicit engine(std::shared_ptr<host_index> idx);
@@ -135,13 +143,26 @@ public:
     void streaming_query_per_read_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
                                          uint64_t total_bases, uint64_t* d_rows, uint64_t* d_report, void* stream) const;
 
+    /* The maximal runs of every read (sshash_streaming_runs[_device] in include/sshash_amd.h): a run is a search and the extensions
+       behind it. Device buffers, asynchronous, always the run kernel: count -> scan -> write; `d_run_offsets` (n_reads + 1 words) is
+       overwritten, record i is written iff i < runs_capacity, `d_report` (nullable) is accumulated into. Every read below 2^31
+       bases (a record's read_pos and length are 31 bits wide; the host call checks, this one does not). */
+    void streaming_runs_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
+                               uint64_t* d_run_offsets, void* d_runs, uint64_t runs_capacity, uint64_t* d_report, void* stream) const;
+    /* Host buffers, over all resident replicas; a piece that holds a read above 2^16 bases takes the position-parallel pipeline and a
+       compaction behind it, which give the same records. Throws at a read of 2^31 bases or more. Returns the totals. */
+    streaming_report streaming_runs_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* run_offsets, void* runs,
+                                         uint64_t runs_capacity) const;
+
     /* Per-k-mer results of the streaming query (streaming_query::lookup for every k-mer of every read,
        include/streaming_query.hpp:56-109): entry read_offsets[r] + j of every non-null array of `d_out` = the k-mer
        starting at base j of read r; places where no k-mer starts are left untouched. `d_report` (nullable): the six
        counters, accumulated. Device buffers, asynchronous. */
     void streaming_lookup_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
                                  uint64_t total_bases, result_view const& d_out, uint64_t* d_report, void* stream,
-                                 uint64_t* d_rows = nullptr /* one report per read, n_reads x 6 words, ADDED to */) const;
+                                 uint64_t* d_rows = nullptr /* one report per read, n_reads x 6 words, ADDED to */,
+                                 run_sink const* d_runs = nullptr /* the reads' runs, compacted out of the per-k-mer results: run_offsets overwritten,
+                                                                      records below its capacity written */) const;
     streaming_report streaming_lookup_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads,
                                            result_view const& h_out) const;
 
@@ -157,6 +178,11 @@ public:
     device_replica const* replica(int device) const;
 
 private:
+    /* the passes of streaming_runs_device (streaming.hip): `count` -- d_run_offsets from the reads, `d_report` accumulated into --,
+       `write` -- the records, for a d_run_offsets that holds the offsets of these very reads (streaming_runs_host counts, sizes a
+       piece's records from the count and writes) */
+    void streaming_runs_passes(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
+                               run_sink const& sink, uint64_t* d_report, void* stream, bool count, bool write) const;
     std::shared_ptr<host_index> m_idx;
     /* to_device may run while other host threads query: readers share, the upload's final push_back is exclusive */
     mutable std::shared_mutex m_replicas_mutex;

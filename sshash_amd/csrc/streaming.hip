@@ -11,7 +11,8 @@
 // same table key, and cannot be in that key's slot either, are negative too" -- the same k-mers are
 // negative either way, so the counters are unchanged.
 // Output: the six counters of streaming_query_report (include/util.hpp:21-36), for the batch or -- the kernel's PER_READ form -- for every
-// read on its own; per-k-mer results: the position-parallel pipeline further down.
+// read on its own, or -- its run forms -- one record per run (a search and the extensions behind it: where the read hits) in CSR layout;
+// per-k-mer results: the position-parallel pipeline further down.
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
 
@@ -284,11 +285,37 @@ __device__ __forceinline__ void row_flush(uint64_t* __restrict__ row, bool parti
    mark the row (ROW_PARTIAL): what follows is ADDED to such a row (a load, an add, a store -- a dependent round trip that the common
    read never pays). A read shorter than k gets its six zeros at the hand-out and is never anybody's. No batch totals here: they are
    the column sums of the rows (stream_rows_sum_kernel). */
-template <int W, bool CANON, bool SK, bool PER_READ>
+/* MODE (what leaves the kernel besides, or instead of, the batch's six counters):
+     STREAM_TOTALS       the six counters of the batch;
+     STREAM_ROWS         PER_READ, above;
+     STREAM_RUN_COUNTS   the six counters of the batch as STREAM_TOTALS, and for every read the number of its RUNS -- a run is a search
+                         and the extensions behind it, so a read has as many as it has searches -- at sink.run_offsets[r] (one plain
+                         store when the read is done: a count per read that never leaves the lane early, in a register of its own);
+     STREAM_RUN_RECORDS  one sshash_streaming_run per run (include/sshash_amd.h), no counters: the lane that takes read r starts its
+                         cursor at sink.run_offsets[r] -- the counts of a STREAM_RUN_COUNTS launch over the same reads, scanned -- and
+                         stores the record of every hit where its run has been measured (top of the turn after the hit; a hit that
+                         nothing can follow: where it is found), two 16-byte stores, nothing at or beyond sink.capacity and nothing at
+                         or beyond run_offsets[r + 1]. The hit's string travels across the turn in one more register. */
+enum : int { STREAM_TOTALS = 0, STREAM_ROWS = 1, STREAM_RUN_COUNTS = 2, STREAM_RUN_RECORDS = 3 };
+
+/* the record of the run of `n` k-mers whose first (in read order) starts at base `at` of the packed reads and lies at offset `off` of
+   the strings, in string `sid`: to place `cursor` of the records, unless that is past what the read or the caller has room for */
+__device__ __forceinline__ void run_record_store(dict_view const& d, run_sink const& sink, const uint64_t* __restrict__ offsets, uint64_t r,
+                                                 uint64_t cursor, uint64_t at, uint64_t off, uint32_t sid, int ori, uint64_t n) {
+    if (cursor >= sink.capacity || cursor >= sink.run_offsets[r + 1]) return;
+    const uint64_t kmer_id = off - uint64_t(sid) * (d.k - 1), in_string = off - d.endpoints[sid];  // (store_result, lookup_device.hpp)
+    const uint32_t read_pos = uint32_t(at - offsets[r]), length = uint32_t(n) | (ori > 0 ? 0u : 0x80000000u);
+    uint4* const rec = static_cast<uint4*>(sink.records) + 2 * cursor;
+    rec[0] = make_uint4(uint32_t(kmer_id), uint32_t(kmer_id >> 32), sid, 0u);
+    rec[1] = make_uint4(uint32_t(in_string), uint32_t(in_string >> 32), read_pos, length);
+}
+
+template <int W, bool CANON, bool SK, int MODE>
 __global__ void __launch_bounds__(256, SSHASH_STREAM_WAVES)
 streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, const uint64_t* __restrict__ packed,
                      const uint64_t* __restrict__ okay, const uint64_t* __restrict__ offsets, const uint64_t n_reads,
-                     const uint64_t reads_per_wave, const uint32_t move_out_every, uint64_t* __restrict__ report) {
+                     const uint64_t reads_per_wave, const uint32_t move_out_every, uint64_t* __restrict__ report, const run_sink sink) {
+    constexpr bool PER_READ = MODE == STREAM_ROWS, COUNT_RUNS = MODE == STREAM_RUN_COUNTS, RECORDS = MODE == STREAM_RUN_RECORDS;
     __shared__ uint4 stage[SK ? 4 * 256 : 1];  // a wave's 64 bucket lines on their way from the quads that fetch them to the lanes that own them
     uint4* const wave_stage = stage + (SK ? (threadIdx.x >> 6) * 256 : 0);
     /* the counters are 32 bits wide in the lanes (six registers fewer than five 64-bit ones: with them the k <= 63 kernel fits five waves a
@@ -298,7 +325,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
     const uint32_t k = d.k;
     const uint32_t lane = threadIdx.x & 63u;
     unsigned long long* const wave_moved_out = moved_out[threadIdx.x >> 6];
-    if constexpr (!PER_READ) {
+    if constexpr (!PER_READ && !RECORDS) {
         if (lane < 5) wave_moved_out[lane] = 0;
     }
     /* this wave's share of the reads, handed out in order to whichever lane is done with its read */
@@ -336,6 +363,10 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
        whether its row already holds a part of its counts */
     constexpr uint32_t ROW_NONE = ~0u, ROW_PARTIAL = 1u << 31;
     uint32_t my_row = ROW_NONE;
+    /* (the run forms) the runs of the lane's read so far; where its next record goes; the string of the hit whose run is to be measured */
+    uint32_t n_runs = 0, hit_sid = 0;
+    uint64_t cursor = 0;
+    const uint64_t wave_first = wave * reads_per_wave;
     uint64_t* const wave_rows = report + wave * reads_per_wave * 6;  // (PER_READ) the row of the wave's first read
 #ifdef SSHASH_STREAM_STATS
     /* (a debug build, tools/jobs/r06_stream_stats.sh: what the lanes of a wave do per turn -- wave-level sums in scalar registers, out
@@ -357,7 +388,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                     row_flush(wave_rows + uint64_t(my_row & ~ROW_PARTIAL) * 6, (my_row & ROW_PARTIAL) != 0, c_invalid, c_negative, c_searches, c_extensions);
                     my_row |= ROW_PARTIAL;
                 }
-            } else {
+            } else if constexpr (!RECORDS) {
                 const uint64_t i = wave_sum(c_invalid), n = wave_sum(c_negative), f = wave_sum(c_searches), e = wave_sum(c_extensions);
                 if (lane == 0) {
                     wave_moved_out[0] += i;
@@ -379,7 +410,10 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
         if (pending) {
             const uint64_t b = cur + k - 1, valid_end = inv < rd_end ? inv : rd_end;
             const uint64_t run = extend_run<W>(d, packed, off, ori, b, valid_end - b, run_step_load<W>(d, packed, off, ori > 0, b, 0));
-            if (run >> 15) {  // (past what the lane's 32-bit counter may take in one turn: 2^16 turns lie between two move-outs)
+            if constexpr (RECORDS) {  // (the hit lies a base before cur)
+                run_record_store(d, sink, offsets, wave_first + my_row, cursor, cur - 1, off, hit_sid, ori, run + 1);
+                ++cursor;
+            } else if (run >> 15) {  // (past what the lane's 32-bit counter may take in one turn: 2^16 turns lie between two move-outs)
                 if constexpr (PER_READ) {  // (into the row at once, behind what the lane has counted for it so far)
                     uint64_t* const row = wave_rows + uint64_t(my_row & ~ROW_PARTIAL) * 6;
                     row_flush(row, (my_row & ROW_PARTIAL) != 0, c_invalid, c_negative, c_searches, c_extensions);
@@ -405,6 +439,13 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                 my_row = ROW_NONE;
             }
         }
+        if constexpr (COUNT_RUNS) {
+            if (want && my_row != ROW_NONE) {  // (the read is done, as above: its count)
+                sink.run_offsets[wave_first + my_row] = n_runs;
+                n_runs = 0;
+                my_row = ROW_NONE;
+            }
+        }
         if (wants != 0 && next < last) {
             const uint64_t rank = uint64_t(__popcll(wants & ((uint64_t(1) << lane) - 1)));
             if (want && rank < last - next) {
@@ -420,6 +461,16 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                     } else {  // (nothing will ever be counted for it: the whole row now)
                         row[1] = row[2] = row[3] = row[4] = row[5] = 0;
                     }
+                } else if constexpr (COUNT_RUNS) {
+                    if (rd_end - cur >= k) {
+                        atomicAdd(wave_moved_out + 4, (unsigned long long)(rd_end - cur - k + 1));
+                        my_row = uint32_t(r - wave_first);
+                    } else {  // (no k-mer, no run)
+                        sink.run_offsets[r] = 0;
+                    }
+                } else if constexpr (RECORDS) {
+                    my_row = uint32_t(r - wave_first);
+                    cursor = sink.run_offsets[r];
                 } else {
                     if (rd_end - cur >= k) atomicAdd(wave_moved_out + 4, (unsigned long long)(rd_end - cur - k + 1));
                 }
@@ -450,7 +501,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                     row_flush(row, (my_row & ROW_PARTIAL) != 0, c_invalid, c_negative, c_searches, c_extensions);
                     my_row |= ROW_PARTIAL;
                     row[3] += over;
-                } else {
+                } else if constexpr (!RECORDS) {
                     atomicAdd(wave_moved_out + 0, (unsigned long long)over);
                 }
             } else {
@@ -590,6 +641,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                     found = r.outcome == FAST_HIT;
                     off = r.kmer_offset;
                     ori = r.orientation;
+                    if constexpr (RECORDS) hit_sid = r.string_id;
                     const bool stands = !found && !(where & WALK_VISITED);
                     if (stands || (where & WALK_HEAVY_PENDING)) {
                         /* a miss that stands for the k-mers behind this one: those that elect the same key occurrence (sk_key_persists)
@@ -627,6 +679,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                 found = h.found;
                 off = h.kmer_offset;
                 ori = h.orientation;
+                if constexpr (RECORDS) hit_sid = h.string_id;
                 neg_unknown_mini = !SK && !h.found && !h.minimizer_found;
             }
         }
@@ -635,6 +688,13 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                 ++c_searches;
                 neg_unknown_mini = false;
                 pending = cur + 1 + k <= valid_end;  // (otherwise nothing can extend it)
+                if constexpr (COUNT_RUNS) ++n_runs;
+                if constexpr (RECORDS) {
+                    if (!pending) {  // a run of one
+                        run_record_store(d, sink, offsets, wave_first + my_row, cursor, cur, off, hit_sid, ori, 1);
+                        ++cursor;
+                    }
+                }
             } else {
                 ++c_negative;
             }
@@ -643,7 +703,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
     }
 #ifdef SSHASH_STREAM_STATS
     const unsigned long long st_neg_kept = wave_sum(st_kept_lane);
-    if (lane == 0 && !PER_READ) {  // (the statistics are the six-counter kernel's: `report` is rows otherwise)
+    if (lane == 0 && MODE == STREAM_TOTALS) {  // (the statistics are the six-counter kernel's: `report` is rows otherwise)
         unsigned long long* st = reinterpret_cast<unsigned long long*>(report) + 6;
         atomicAdd(st + 0, st_turns); atomicAdd(st + 1, st_fresh); atomicAdd(st + 2, st_walk); atomicAdd(st + 3, st_ext); atomicAdd(st + 4, st_slot1);
         atomicAdd(st + 5, st_inv); atomicAdd(st + 6, st_idle); atomicAdd(st + 7, st_full); atomicAdd(st + 8, st_neg_kept); atomicAdd(st + 9, st_short);
@@ -651,7 +711,10 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
 #endif
     if constexpr (PER_READ) {
         if (my_row != ROW_NONE) row_flush(wave_rows + uint64_t(my_row & ~ROW_PARTIAL) * 6, (my_row & ROW_PARTIAL) != 0, c_invalid, c_negative, c_searches, c_extensions);  // (no lane gets here with a read: whoever is not live has handed its row in above)
-    } else {
+    } else if constexpr (!RECORDS) {
+        if constexpr (COUNT_RUNS) {
+            if (my_row != ROW_NONE) sink.run_offsets[wave_first + my_row] = n_runs;  // (as the rows: nobody gets here with a read)
+        }
         const bool first = lane == 0;  // (what the wave moved out is added once)
         block_report(first ? wave_moved_out[4] : 0, uint64_t(c_invalid) + (first ? wave_moved_out[0] : 0), uint64_t(c_negative) + (first ? wave_moved_out[1] : 0),
                      uint64_t(c_searches) + (first ? wave_moved_out[2] : 0), uint64_t(c_extensions) + (first ? wave_moved_out[3] : 0), report);
@@ -674,17 +737,101 @@ stream_rows_sum_kernel(const uint64_t* __restrict__ rows, const uint64_t n_reads
     block_report(c_kmers, c_invalid, c_negative, c_searches, c_extensions, report);
 }
 
+/* ---- an exclusive prefix sum over 64-bit words, in place (counts per read -> run_offsets; head marks -> ranks): tiles of 4096 words, three
+        launches -- the tiles' sums, their scan by one workgroup, the tiles again with their sums in front. Two reads and a write a word. ---- */
+constexpr uint32_t SCAN_PER_LANE = 16, SCAN_TILE = 256 * SCAN_PER_LANE;
+inline uint64_t scan_tiles(uint64_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
+
+/* (a workgroup of 256) what the lanes before this one hold together; `total`: what all hold */
+__device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t v, uint64_t& total) {
+    __shared__ uint64_t wave_total[4];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint64_t inc = v;
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+        const uint64_t t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    __syncthreads();  // (called in a loop: the totals of the call before have been read)
+    if (lane == 63) wave_total[w] = inc;
+    __syncthreads();
+    uint64_t before = 0;
+    total = 0;
+    for (uint32_t j = 0; j < 4; ++j) {
+        if (j < w) before += wave_total[j];
+        total += wave_total[j];
+    }
+    return before + inc - v;
+}
+
+__global__ void __launch_bounds__(256)
+scan_tile_sums_kernel(const uint64_t* __restrict__ data, const uint64_t n, uint64_t* __restrict__ sums) {
+    const uint64_t base = uint64_t(blockIdx.x) * SCAN_TILE + threadIdx.x * SCAN_PER_LANE;
+    uint64_t v = 0;
+    for (uint32_t j = 0; j < SCAN_PER_LANE; ++j)
+        if (base + j < n) v += data[base + j];
+    uint64_t total;
+    block_exclusive_scan(v, total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(256)
+scan_sums_kernel(uint64_t* __restrict__ sums, const uint64_t tiles) {  // one workgroup
+    uint64_t carry = 0;
+    for (uint64_t at = 0; at < tiles; at += 256) {
+        const uint64_t i = at + threadIdx.x;
+        const uint64_t v = i < tiles ? sums[i] : 0;
+        uint64_t total;
+        const uint64_t before = block_exclusive_scan(v, total);
+        if (i < tiles) sums[i] = carry + before;
+        carry += total;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+scan_apply_kernel(uint64_t* __restrict__ data, const uint64_t n, const uint64_t* __restrict__ sums) {
+    const uint64_t base = uint64_t(blockIdx.x) * SCAN_TILE + threadIdx.x * SCAN_PER_LANE;
+    uint64_t e[SCAN_PER_LANE], v = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < SCAN_PER_LANE; ++j) {
+        e[j] = base + j < n ? data[base + j] : 0;
+        v += e[j];
+    }
+    uint64_t total;
+    uint64_t at = sums[blockIdx.x] + block_exclusive_scan(v, total);
+#pragma unroll
+    for (uint32_t j = 0; j < SCAN_PER_LANE; ++j) {
+        if (base + j < n) data[base + j] = at;
+        at += e[j];
+    }
+}
+
+/* data[i] = data[0] + .. + data[i - 1] for i < n; `sums`: scan_tiles(n) words of scratch */
+void exclusive_scan_u64(uint64_t* data, uint64_t n, uint64_t* sums, hipStream_t s) {
+    if (n == 0) return;
+    const uint64_t tiles = scan_tiles(n);
+    hipLaunchKernelGGL(scan_tile_sums_kernel, dim3(uint32_t(tiles)), dim3(256), 0, s, data, n, sums);
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(256), 0, s, sums, tiles);
+    hipLaunchKernelGGL(scan_apply_kernel, dim3(uint32_t(tiles)), dim3(256), 0, s, data, n, sums);
+    HIP_CHECK(hipGetLastError());
+}
+
+/* `run_phases` (with `sink`): RUNS_COUNT -- sink.run_offsets becomes the CSR offsets of the reads' runs (the counting form of the kernel, then
+   the scan; `report` as without, may be null) --, RUNS_WRITE -- the records, for run_offsets that hold those offsets --, or both. */
+enum : int { RUNS_COUNT = 1, RUNS_WRITE = 2 };
 template <int W, bool CANON>
 void launch_streaming_runs(device_replica const* rep, dict_view const& d, char const* bases, uint64_t const* offsets, uint64_t n_reads,
-                           uint64_t total_bases, uint64_t* report, hipStream_t s, uint64_t* rows = nullptr /* per read: n_reads x 6 words; `report` may then be null */) {
+                           uint64_t total_bases, uint64_t* report, hipStream_t s, uint64_t* rows = nullptr /* per read: n_reads x 6 words; `report` may then be null */,
+                           run_sink sink = run_sink{nullptr, nullptr, 0}, int run_phases = 0) {
     /* two bits and a validity bit a base, in words of 32 and 64 bases; three words of slack behind the last base (a seed and a
        run read up to two words past their first) */
     const uint64_t packed_bytes = ((total_bases + 31) / 32 + 3) * 8, okay_bytes = ((total_bases + 63) / 64 + 2) * 8;
     /* (scratch the replica keeps for this stream, replica.hpp; two host threads that share a stream must not interleave their
        launch sequences, which share it) */
+    const uint64_t runs_bytes = run_phases ? (scan_tiles(n_reads + 1) + 6) * 8 : 0;  // (the scan's tile sums; six counters nobody asked for)
     std::lock_guard<std::mutex> sequence(rep->launch_mutex);
-    uint64_t* packed = static_cast<uint64_t*>(rep->read_scratch_for(s, packed_bytes + okay_bytes));
+    uint64_t* packed = static_cast<uint64_t*>(rep->read_scratch_for(s, packed_bytes + okay_bytes + runs_bytes));
     uint64_t* okay = packed + packed_bytes / 8;
+    uint64_t* scan_sums = okay + okay_bytes / 8;
     if (total_bases) {
         const uint64_t lanes = (total_bases + 7) / 8;
         hipLaunchKernelGGL(stream_pack_kernel, dim3(uint32_t((lanes + 255) / 256)), dim3(256), 0, s, bases, total_bases,
@@ -699,10 +846,31 @@ void launch_streaming_runs(device_replica const* rep, dict_view const& d, char c
     const uint64_t reads_per_wave = (n_reads + waves - 1) / waves;
     const dim3 grid(uint32_t(waves / 4)), block(256);
     const uint32_t move_out_every = uint32_t(test_hook_u64("stream_move_out_every", uint64_t(1) << 16, 1, uint64_t(1) << 16));
+    if (run_phases) {
+        if (reads_per_wave >> 31) throw error(error_kind::argument, "too many reads for one call");  // (as below)
+        if (run_phases & RUNS_COUNT) {
+            uint64_t* totals = report;
+            if (!totals) {
+                totals = scan_sums + scan_tiles(n_reads + 1);
+                HIP_CHECK(hipMemsetAsync(totals, 0, 6 * sizeof(uint64_t), s));
+            }
+            if (d.sk.enabled) hipLaunchKernelGGL((streaming_run_kernel<W, CANON, true, STREAM_RUN_COUNTS>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, totals, sink);
+            else hipLaunchKernelGGL((streaming_run_kernel<W, CANON, false, STREAM_RUN_COUNTS>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, totals, sink);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemsetAsync(sink.run_offsets + n_reads, 0, sizeof(uint64_t), s));
+            exclusive_scan_u64(sink.run_offsets, n_reads + 1, scan_sums, s);
+        }
+        if (run_phases & RUNS_WRITE) {
+            if (d.sk.enabled) hipLaunchKernelGGL((streaming_run_kernel<W, CANON, true, STREAM_RUN_RECORDS>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, static_cast<uint64_t*>(nullptr), sink);
+            else hipLaunchKernelGGL((streaming_run_kernel<W, CANON, false, STREAM_RUN_RECORDS>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, static_cast<uint64_t*>(nullptr), sink);
+            HIP_CHECK(hipGetLastError());
+        }
+        return;
+    }
     if (rows) {
         if (reads_per_wave >> 31) throw error(error_kind::argument, "too many reads for one call");  // (a lane keeps its read's index in its wave's share in 31 bits)
-        if (d.sk.enabled) hipLaunchKernelGGL((streaming_run_kernel<W, CANON, true, true>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, rows);
-        else hipLaunchKernelGGL((streaming_run_kernel<W, CANON, false, true>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, rows);
+        if (d.sk.enabled) hipLaunchKernelGGL((streaming_run_kernel<W, CANON, true, STREAM_ROWS>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, rows, sink);
+        else hipLaunchKernelGGL((streaming_run_kernel<W, CANON, false, STREAM_ROWS>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, rows, sink);
         HIP_CHECK(hipGetLastError());
         if (report) {
             const uint32_t blocks = uint32_t(std::min<uint64_t>((n_reads + 255) / 256, 1024));
@@ -711,8 +879,8 @@ void launch_streaming_runs(device_replica const* rep, dict_view const& d, char c
         }
         return;
     }
-    if (d.sk.enabled) hipLaunchKernelGGL((streaming_run_kernel<W, CANON, true, false>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, report);
-    else hipLaunchKernelGGL((streaming_run_kernel<W, CANON, false, false>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, report);
+    if (d.sk.enabled) hipLaunchKernelGGL((streaming_run_kernel<W, CANON, true, STREAM_TOTALS>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, report, sink);
+    else hipLaunchKernelGGL((streaming_run_kernel<W, CANON, false, STREAM_TOTALS>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, report, sink);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -762,6 +930,40 @@ void engine::streaming_query_per_read_device(int device, char const* d_bases, ui
     else if (!wide && d.canonical) launch_streaming_runs<1, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, d_rows);
     else if (wide && !d.canonical) launch_streaming_runs<2, false>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, d_rows);
     else launch_streaming_runs<2, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, d_rows);
+}
+
+/* The runs of every read (sshash_streaming_runs_device): count -> scan -> write, always the run kernel. */
+void engine::streaming_runs_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
+                                   uint64_t* d_run_offsets, void* d_runs, uint64_t runs_capacity, uint64_t* d_report, void* stream) const {
+    (void)replica(device);  // (not resident: that error first)
+    if (n_reads == 0 && !d_run_offsets) return;
+    if (!d_run_offsets) throw error(error_kind::argument, "run_offsets pointer is null");
+    if (!d_runs && runs_capacity) throw error(error_kind::argument, "runs pointer is null");
+    streaming_runs_passes(device, d_bases, d_read_offsets, n_reads, total_bases, run_sink{d_run_offsets, d_runs, runs_capacity}, d_report, stream, true,
+                          runs_capacity != 0);
+}
+
+void engine::streaming_runs_passes(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
+                                   run_sink const& sink, uint64_t* d_report, void* stream, bool count, bool write) const {
+    device_replica const* rep = replica(device);
+    device_guard guard(device);
+    dict_view const& d = rep->view;
+    hipStream_t s = hipStream_t(stream);
+    const bool wide = d.k > 31;
+    if (n_reads && total_bases == 0) {
+        HIP_CHECK(hipMemcpyAsync(&total_bases, d_read_offsets + n_reads, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    }
+    if (n_reads == 0 || total_bases == 0) {  // no read, or empty reads only: no run
+        if (count) HIP_CHECK(hipMemsetAsync(sink.run_offsets, 0, (n_reads + 1) * sizeof(uint64_t), s));
+        return;
+    }
+    const int phases = (count ? RUNS_COUNT : 0) | (write ? RUNS_WRITE : 0);
+    if (!phases) return;
+    if (!wide && !d.canonical) launch_streaming_runs<1, false>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, phases);
+    else if (!wide && d.canonical) launch_streaming_runs<1, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, phases);
+    else if (wide && !d.canonical) launch_streaming_runs<2, false>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, phases);
+    else launch_streaming_runs<2, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, phases);
 }
 
 /* ---- per-k-mer results: the streaming query as a position-parallel pipeline -----------------------------------
@@ -1004,10 +1206,74 @@ stream_classify_rows_kernel(const uint8_t* __restrict__ flags, const uint64_t to
     if (n_extension) atomicAdd(row + 5, n_extension);
 }
 
+/* ---- the runs out of the per-k-mer results (the host call's route for reads too long for one lane): a positive k-mer is the HEAD of a run
+        unless it continues the run of the k-mer before it -- the rule of the classification above --; the heads' ranks in place order are
+        their places in the CSR layout (reads lie in place order), so one scan over the marks gives run_offsets -- the rank at every
+        read's first base -- and every head's place; a head's lane then walks to the first k-mer that does not continue its run. One lane
+        a place: rare inputs, correctness first. ---- */
+constexpr uint8_t RUN_HEAD = 1, RUN_CONTINUES = 2;
+
+__global__ void __launch_bounds__(256)
+stream_run_marks_kernel(const uint8_t* __restrict__ flags, const uint64_t total_bases, const uint64_t* __restrict__ kmer_id,
+                        const uint64_t* __restrict__ string_id, const int8_t* __restrict__ orientation, uint8_t* __restrict__ marks /* total_bases + 1 */,
+                        uint64_t* __restrict__ rank /* total_bases + 1 */) {
+    const uint64_t p = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (p > total_bases) return;
+    uint8_t mark = 0;
+    if (p < total_bases) {
+        const uint8_t f = flags[p];
+        if (!(f & SQ_INVALID) && (f & SQ_VALID)) {
+            const uint64_t id = kmer_id[p];
+            if (id != INVALID_U64) {
+                bool extension = false;
+                if (!(f & SQ_FIRST) && p > 0 && (flags[p - 1] & SQ_VALID)) {  // (as stream_classify_kernel)
+                    const uint64_t before = kmer_id[p - 1];
+                    extension = before != INVALID_U64 && string_id[p - 1] == string_id[p] && id == before + uint64_t(int64_t(orientation[p - 1]));
+                }
+                mark = extension ? RUN_CONTINUES : RUN_HEAD;
+            }
+        }
+    }
+    marks[p] = mark;
+    rank[p] = mark == RUN_HEAD ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(256)
+stream_run_offsets_kernel(const uint64_t* __restrict__ rank, const uint64_t total_bases, const uint64_t* __restrict__ offsets, const uint64_t n_reads,
+                          uint64_t* __restrict__ run_offsets) {
+    const uint64_t r = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (r > n_reads) return;
+    const uint64_t at = offsets[r];
+    run_offsets[r] = rank[at < total_bases ? at : total_bases];
+}
+
+__global__ void __launch_bounds__(256)
+stream_run_records_kernel(const uint8_t* __restrict__ marks, const uint64_t* __restrict__ rank, const uint64_t total_bases,
+                          const uint64_t* __restrict__ kmer_id, const uint64_t* __restrict__ string_id, const uint64_t* __restrict__ kmer_id_in_string,
+                          const int8_t* __restrict__ orientation, const uint64_t* __restrict__ offsets, const uint64_t n_reads, const run_sink sink) {
+    const uint64_t p = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (p >= total_bases || marks[p] != RUN_HEAD) return;
+    const uint64_t at = rank[p];
+    if (at >= sink.capacity) return;
+    uint64_t n = 1;
+    while (marks[p + n] == RUN_CONTINUES) ++n;  // (marks[total_bases] = 0 ends the last)
+    uint64_t lo = 0, hi = n_reads - 1;  // my read: the largest r with offsets[r] <= p
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (offsets[mid] <= p) lo = mid;
+        else hi = mid - 1;
+    }
+    const uint64_t id = kmer_id[p], in_string = kmer_id_in_string[p];
+    uint4* const rec = static_cast<uint4*>(sink.records) + 2 * at;
+    rec[0] = make_uint4(uint32_t(id), uint32_t(id >> 32), uint32_t(string_id[p]), uint32_t(string_id[p] >> 32));
+    rec[1] = make_uint4(uint32_t(in_string), uint32_t(in_string >> 32), uint32_t(p - offsets[lo]), uint32_t(n) | (orientation[p] > 0 ? 0u : 0x80000000u));
+}
+
 void engine::streaming_lookup_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
-                                     uint64_t total_bases, result_view const& d_out, uint64_t* d_report, void* stream, uint64_t* d_rows) const {
+                                     uint64_t total_bases, result_view const& d_out, uint64_t* d_report, void* stream, uint64_t* d_rows,
+                                     run_sink const* runs) const {
     device_replica const* rep = replica(device);
-    if (!d_out.kmer_id && !d_report && !d_rows) throw error(error_kind::argument, "neither a kmer_id array nor a report to fill");
+    if (!d_out.kmer_id && !d_report && !d_rows && !runs) throw error(error_kind::argument, "neither a kmer_id array nor a report to fill");
     if (d_out.minimizer_found) throw error(error_kind::argument, "the streaming lookup does not report minimizer_found");
     if (n_reads == 0 || total_bases == 0) return;
     device_guard guard(device);
@@ -1025,7 +1291,10 @@ void engine::streaming_lookup_device(int device, char const* d_bases, uint64_t c
     uint64_t* tile_read = tmp.alloc<uint64_t>((chunk + 255) / 256);
     if (!sid) sid = tmp.alloc<uint64_t>(total_bases);
     if (!ori) ori = tmp.alloc<int8_t>(total_bases);
+    uint64_t* in_string = d_out.kmer_id_in_string;
+    if (runs && !in_string) in_string = tmp.alloc<uint64_t>(total_bases);
     result_view all = d_out;
+    all.kmer_id_in_string = in_string;
     all.kmer_id = ids;
     all.string_id = sid;
     all.kmer_orientation = ori;
@@ -1049,6 +1318,20 @@ void engine::streaming_lookup_device(int device, char const* d_bases, uint64_t c
     if (d_rows) {
         hipLaunchKernelGGL(stream_classify_rows_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, flags, total_bases, ids, sid, ori,
                            d_read_offsets, n_reads, d_rows);
+        HIP_CHECK(hipGetLastError());
+    }
+    if (runs) {
+        const uint64_t places = total_bases + 1;
+        uint8_t* marks = tmp.alloc<uint8_t>(places);
+        uint64_t* rank = tmp.alloc<uint64_t>(places);
+        uint64_t* sums = tmp.alloc<uint64_t>(scan_tiles(places));
+        hipLaunchKernelGGL(stream_run_marks_kernel, dim3(uint32_t((places + 255) / 256)), dim3(256), 0, s, flags, total_bases, ids, sid, ori, marks, rank);
+        HIP_CHECK(hipGetLastError());
+        exclusive_scan_u64(rank, places, sums, s);
+        hipLaunchKernelGGL(stream_run_offsets_kernel, dim3(uint32_t((n_reads + 256) / 256)), dim3(256), 0, s, rank, total_bases, d_read_offsets, n_reads, runs->run_offsets);
+        if (runs->capacity)
+            hipLaunchKernelGGL(stream_run_records_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, marks, rank, total_bases, ids, sid, in_string, ori,
+                               d_read_offsets, n_reads, *runs);
         HIP_CHECK(hipGetLastError());
     }
 }
@@ -1192,6 +1475,106 @@ streaming_report engine::streaming_query_per_read_host(char const* bases, uint64
         }
         partial[li] = read_back(d_report, s);
     });
+    streaming_report total;
+    for (auto const& p : partial) total += p;
+    return total;
+}
+
+/* The runs of every read, host buffers (sshash_streaming_runs): the pieces and lanes of streaming_query_per_read_host. A piece's
+   run_offsets are local to the piece and its record count is known only after its counting pass, so a lane counts, reads the count
+   back, sizes the piece's device records from it and writes them; the pieces' records wait on the host until every piece's count is
+   known -- only then is a piece's place in the caller's array --, and are stitched in piece order, clipped at `runs_capacity`. */
+streaming_report engine::streaming_runs_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* run_offsets,
+                                             void* runs, uint64_t runs_capacity) const {
+    constexpr uint64_t RECORD_BYTES = 32;
+    if (n_reads == 0) {
+        if (run_offsets) run_offsets[0] = 0;
+        return {};
+    }
+    for (uint64_t r = 0; r < n_reads; ++r)
+        if ((read_offsets[r + 1] - read_offsets[r]) >> 31) throw error(error_kind::argument, "a read of 2^31 bases or more: a run record could not hold its positions");
+    const std::vector<int> devs = resident_devices(*this);
+    const uint64_t G = devs.size();
+    const uint64_t piece_bases = uint64_t(32) << 20;
+    const uint64_t piece_reads = test_hook_u64("stream_piece_reads", uint64_t(1) << 20, 1, uint64_t(1) << 20);
+    std::vector<uint64_t> cuts{0};
+    uint64_t max_bases = 0, max_reads = 0;
+    for (uint64_t at = 0; at < n_reads;) {
+        uint64_t end = at + 1;
+        while (end < n_reads && end - at < piece_reads && read_offsets[end + 1] - read_offsets[at] <= piece_bases) ++end;
+        max_bases = std::max(max_bases, read_offsets[end] - read_offsets[at]);
+        max_reads = std::max(max_reads, end - at);
+        cuts.push_back(end);
+        at = end;
+    }
+    const uint64_t num_pieces = cuts.size() - 1;
+    const uint64_t off_bytes = (max_reads + 1) * sizeof(uint64_t);
+    const uint64_t bases_at = (off_bytes + 255) & ~uint64_t(255);
+    const uint64_t report_at = (bases_at + max_bases + 255) & ~uint64_t(255);
+    const uint64_t counts_at = (report_at + 6 * sizeof(uint64_t) + 255) & ~uint64_t(255);
+    const uint64_t lane_bytes = counts_at + off_bytes;
+
+    std::atomic<uint64_t> next{0};
+    const uint64_t hw = std::max(1u, std::thread::hardware_concurrency());
+    const uint64_t lanes_per_device = std::min<uint64_t>({(num_pieces + G - 1) / G, 8, std::max<uint64_t>(1, hw / G)});
+    std::vector<int> lane_devs(lanes_per_device * G);
+    for (uint64_t li = 0; li < lane_devs.size(); ++li) lane_devs[li] = devs[li % G];
+    std::vector<streaming_report> partial(lane_devs.size());
+    std::vector<std::vector<uint64_t>> piece_records(num_pieces);  // (four words a record)
+    std::vector<uint64_t> piece_total(num_pieces, 0);
+    run_lanes(*this, lane_devs, lane_bytes, [&](size_t li, int device, host_lane& lane) {
+        hipStream_t s = lane.stream;
+        device_replica const* rep = replica(device);
+        char* hp = static_cast<char*>(lane.pinned);
+        char* dp = static_cast<char*>(lane.device);
+        uint64_t* d_report = reinterpret_cast<uint64_t*>(dp + report_at);
+        uint64_t* d_counts = reinterpret_cast<uint64_t*>(dp + counts_at);
+        uint64_t const* d_offsets = reinterpret_cast<uint64_t const*>(dp);
+        HIP_CHECK(hipMemsetAsync(d_report, 0, 6 * sizeof(uint64_t), s));
+        for (;;) {
+            const uint64_t piece = next.fetch_add(1);
+            if (piece >= num_pieces) break;
+            const uint64_t first = cuts[piece], last = cuts[piece + 1], n = last - first;
+            const uint64_t nb = read_offsets[last] - read_offsets[first];
+            uint64_t* rel = reinterpret_cast<uint64_t*>(hp);
+            for (uint64_t i = first; i <= last; ++i) rel[i - first] = read_offsets[i] - read_offsets[first];
+            std::memcpy(hp + bases_at, bases + read_offsets[first], nb);
+            HIP_CHECK(hipMemcpyAsync(dp, hp, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipMemcpyAsync(dp + bases_at, hp + bases_at, nb, hipMemcpyHostToDevice, s));
+            bool long_read = false;  // (as streaming_query_per_read_host)
+            for (uint64_t i = first; i < last && !long_read; ++i) long_read = read_offsets[i + 1] - read_offsets[i] > LONG_READ_BASES;
+            const run_sink counting{d_counts, nullptr, 0};
+            if (nb == 0) HIP_CHECK(hipMemsetAsync(d_counts, 0, (n + 1) * sizeof(uint64_t), s));
+            else if (long_read) streaming_lookup_device(device, dp + bases_at, d_offsets, n, nb, result_view{}, d_report, s, nullptr, &counting);
+            else streaming_runs_device(device, dp + bases_at, d_offsets, n, nb, d_counts, nullptr, 0, d_report, s);
+            uint64_t const* counts = reinterpret_cast<uint64_t const*>(hp + counts_at);
+            HIP_CHECK(hipMemcpyAsync(hp + counts_at, d_counts, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            const uint64_t total = counts[n];
+            piece_total[piece] = total;
+            for (uint64_t i = 1; i <= n; ++i) run_offsets[first + i] = counts[i];  // (local to the piece until the pieces are stitched)
+            if (runs_capacity && total) {
+                std::vector<uint64_t>& mine = piece_records[piece];
+                mine.resize(total * (RECORD_BYTES / 8));
+                device_buffers records(rep, s);
+                void* d_records = records.alloc<uint64_t>(total * (RECORD_BYTES / 8));
+                const run_sink writing{d_counts, d_records, total};
+                if (long_read) streaming_lookup_device(device, dp + bases_at, d_offsets, n, nb, result_view{}, nullptr, s, nullptr, &writing);
+                else streaming_runs_passes(device, dp + bases_at, d_offsets, n, nb, writing, nullptr, s, false, true);
+                HIP_CHECK(hipMemcpyAsync(mine.data(), d_records, total * RECORD_BYTES, hipMemcpyDeviceToHost, s));
+                HIP_CHECK(hipStreamSynchronize(s));
+            }
+        }
+        partial[li] = read_back(d_report, s);
+    });
+    run_offsets[0] = 0;
+    uint64_t base = 0;
+    for (uint64_t piece = 0; piece < num_pieces; ++piece) {
+        for (uint64_t r = cuts[piece] + 1; r <= cuts[piece + 1]; ++r) run_offsets[r] += base;
+        if (base < runs_capacity && piece_total[piece])
+            std::memcpy(static_cast<char*>(runs) + base * RECORD_BYTES, piece_records[piece].data(), std::min(piece_total[piece], runs_capacity - base) * RECORD_BYTES);
+        base += piece_total[piece];
+    }
     streaming_report total;
     for (auto const& p : partial) total += p;
     return total;
