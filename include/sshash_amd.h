@@ -327,6 +327,47 @@ sshash_status sshash_streaming_runs(const sshash_dict* d, const char* bases, con
                                     uint64_t* run_offsets, sshash_streaming_run* runs, uint64_t runs_capacity,
                                     sshash_streaming_report* report);
 
+/* ---- WHICH k-mers of the dictionary a read set holds: the streaming query seen from the dictionary's side (no reference counterpart
+ *      as a call). A COVER is a bitmap over the k-mer ids: ceil(num_kmers / 64) words of 64 bits (sshash_cover_words); k-mer id i is bit
+ *      i & 63 of word i >> 6 (bit 0 = the least significant); the bits of the last word at or above num_kmers are never set by these
+ *      calls. After a call the bitmap holds, besides what it held before, exactly the set of kmer_id values other than
+ *      SSHASH_INVALID_U64 that sshash_streaming_lookup returns over the same reads -- every positive k-mer of every read, whatever its
+ *      strand. The calls OR into the bitmap (a sample of many batches, or of several files, marks one bitmap; the caller zeroes it
+ *      first), so the result does not depend on the order of the reads, of the batches or of the calls.
+ *      Preconditions and status codes as the runs calls: a null dictionary, or null bases / read_offsets / cover with num_reads > 0,
+ *      is SSHASH_ERR_ARGUMENT before anything runs; num_reads == 0 succeeds and touches nothing; a dictionary that is not resident
+ *      is SSHASH_ERR_NO_DEVICE. A minimizer shard (num_shards > 1) behaves as with sshash_streaming_runs: it finds the k-mers it owns
+ *      and no others, under the ids of the whole index (strings stay complete), so it marks its share of the cover and the shards'
+ *      bitmaps ORed together are the cover of the whole index. ---- */
+sshash_status sshash_cover_words(const sshash_dict* d, uint64_t* words);
+/* device buffers, asynchronous on hip_stream. cover: sshash_cover_words words, ACCUMULATED into (OR); nothing at or beyond them is
+ * touched. report: 6 uint64 counters, ACCUMULATED into as sshash_streaming_query_device does -- the same six counters --; may be
+ * NULL. total_bases as for sshash_streaming_query_device. Always the run kernel (one lane walks one read, whatever its length), in
+ * ONE launch: where sshash_streaming_runs_device writes a run's record this call ORs the run's id range into the bitmap, one 64-bit
+ * atomic for the first and for the last word it touches; no scratch beyond that of sshash_streaming_query_device. */
+sshash_status sshash_streaming_cover_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
+                                            uint64_t num_reads, uint64_t total_bases, uint64_t* cover, uint64_t* report, void* hip_stream);
+/* host buffers, sharded over all resident replicas like sshash_streaming_query: every replica marks a bitmap of its own in HBM (8
+ * bytes per 64 k-mers, for the length of the call) and those are ORed into `cover` (host, sshash_cover_words words) at the end. A piece
+ * that holds a read above 2^16 bases goes through the position-parallel pipeline of sshash_streaming_lookup and is marked from its
+ * per-k-mer ids, which gives the same bits. report may be NULL. */
+sshash_status sshash_streaming_cover(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
+                                     uint64_t* cover, sshash_streaming_report* report);
+/* a query file (.fa/.fasta/.fq/.fastq, optionally .gz; `multiline` as for sshash_streaming_query_from_file): every replica keeps ONE
+ * bitmap in HBM for the whole file, and they are ORed into `cover` (host) once, at the end. Every kind of file takes the sequential
+ * reader (a reader thread a batch ahead of the devices): host memory stays bounded whatever the size of the file, and the call runs
+ * at that reader's pace. report may be NULL. */
+sshash_status sshash_streaming_cover_from_file(const sshash_dict* d, const char* filename, int multiline, uint64_t* cover,
+                                               sshash_streaming_report* report);
+/* Covered k-mers per string: counts[s] = the set bits of `cover` among the k-mer ids of string s, [string_offsets(s).begin - s*(k-1),
+ * string_offsets(s).end - (s+1)*(k-1)) -- at most sshash_string_size(s) --; counts: num_strings uint64, OVERWRITTEN; total (may be
+ * NULL): one uint64, overwritten with their sum, the number of covered k-mers. Bits at or above num_kmers are not counted. NULL
+ * dictionary, cover or counts: SSHASH_ERR_ARGUMENT. The device variant (device pointers, asynchronous on hip_stream) goes over the
+ * bitmap's words, one lane a word; the host variant is plain CPU code and needs no GPU. */
+sshash_status sshash_cover_string_counts_device(const sshash_dict* d, int device, const uint64_t* cover, uint64_t* counts,
+                                                uint64_t* total, void* hip_stream);
+sshash_status sshash_cover_string_counts(const sshash_dict* d, const uint64_t* cover, uint64_t* counts, uint64_t* total);
+
 /* ---- streaming_query<Dict,canonical>::lookup for EVERY k-mer of every read (include/streaming_query.hpp:56-109),
  *      batched: what the reference returns k-mer by k-mer while it streams a read. Every non-NULL array of `out` has one
  *      entry per BASE of `bases` (total_bases = read_offsets[num_reads] entries): entry read_offsets[r] + j is the result

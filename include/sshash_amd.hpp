@@ -307,6 +307,46 @@ public:
         check(sshash_streaming_runs_device(m_h, device, d_bases, d_read_offsets, num_reads, total_bases, d_run_offsets, d_runs, runs_capacity, d_report, hip_stream));
     }
 
+    /* WHICH k-mers of the dictionary the reads hold (sshash_streaming_cover; the bit layout is in include/sshash_amd.h): k-mer id i is
+       bit i & 63 of cover[i >> 6]. `cover` is sized to cover_words() if it is not (new words zero) and ORed into. Returns the batch's
+       report. */
+    uint64_t cover_words() const {
+        uint64_t words = 0;
+        check(sshash_cover_words(m_h, &words));
+        return words;
+    }
+    streaming_query_report streaming_cover(char const* bases, uint64_t const* read_offsets, uint64_t num_reads, std::vector<uint64_t>& cover) const {
+        cover.resize(cover_words(), 0);
+        sshash_streaming_report s;
+        check(sshash_streaming_cover(m_h, bases, read_offsets, num_reads, cover.data(), &s));
+        return to_report(s);
+    }
+    /* device buffers, asynchronous on hip_stream (sshash_streaming_cover_device): d_cover -- cover_words() uint64 -- is ORed into,
+       d_report -- may be null -- six counters (accumulated into) */
+    void streaming_cover_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t num_reads, uint64_t total_bases,
+                                uint64_t* d_cover, uint64_t* d_report, void* hip_stream) const {
+        check(sshash_streaming_cover_device(m_h, device, d_bases, d_read_offsets, num_reads, total_bases, d_cover, d_report, hip_stream));
+    }
+    /* a query file into one bitmap (sshash_streaming_cover_from_file) */
+    streaming_query_report streaming_cover_from_file(std::string const& filename, bool multiline, std::vector<uint64_t>& cover) const {
+        cover.resize(cover_words(), 0);
+        sshash_streaming_report s;
+        check(sshash_streaming_cover_from_file(m_h, filename.c_str(), multiline, cover.data(), &s));
+        return to_report(s);
+    }
+    /* covered k-mers per string and in all (sshash_cover_string_counts: CPU, no GPU needed; _device: device buffers, asynchronous) */
+    uint64_t cover_string_counts(std::vector<uint64_t> const& cover, std::vector<uint64_t>& counts) const {
+        if (cover.size() < cover_words()) throw std::invalid_argument("cover has fewer than cover_words() words");
+        counts.assign(num_strings(), 0);
+        uint64_t total = 0;
+        std::vector<uint64_t> none(1);
+        check(sshash_cover_string_counts(m_h, cover.empty() ? none.data() : cover.data(), counts.empty() ? none.data() : counts.data(), &total));
+        return total;
+    }
+    void cover_string_counts_device(int device, uint64_t const* d_cover, uint64_t* d_counts, uint64_t* d_total, void* hip_stream) const {
+        check(sshash_cover_string_counts_device(m_h, device, d_cover, d_counts, d_total, hip_stream));
+    }
+
     /* a query file, one row per record, handed over in file order: fn(first_read, rows, n) for one batch after the other; a
        non-zero return stops the query (std::runtime_error). Fn: int(uint64_t, streaming_query_report const*, uint64_t). */
     template <typename Fn>

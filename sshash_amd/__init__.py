@@ -18,9 +18,11 @@ from ._binding import (  # noqa: F401
     LookupResult,
     SSHashError,
     StreamingQueryReport,
+    cover_to_ids,
     device_count,
     encode_kmers,
     expand_runs,
+    ids_to_cover,
     library_path,
 )
 
@@ -32,8 +34,10 @@ __all__ = [
     "LookupResult",
     "SSHashError",
     "StreamingQueryReport",
+    "cover_to_ids",
     "device_count",
     "encode_kmers",
     "expand_runs",
+    "ids_to_cover",
     "library_path",
 ]

@@ -193,6 +193,12 @@ def _load() -> C.CDLL:
         "sshash_streaming_query_from_file_per_read": (C.c_int, [P, C.c_char_p, C.c_int, _PerReadFn, P, C.POINTER(_Report)]),
         "sshash_streaming_runs_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, P, C.c_uint64, P, P]),
         "sshash_streaming_runs": (C.c_int, [P, P, P, C.c_uint64, P, P, C.c_uint64, C.POINTER(_Report)]),
+        "sshash_cover_words": (C.c_int, [P, C.POINTER(C.c_uint64)]),
+        "sshash_streaming_cover_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, P, P]),
+        "sshash_streaming_cover": (C.c_int, [P, P, P, C.c_uint64, P, C.POINTER(_Report)]),
+        "sshash_streaming_cover_from_file": (C.c_int, [P, C.c_char_p, C.c_int, P, C.POINTER(_Report)]),
+        "sshash_cover_string_counts_device": (C.c_int, [P, C.c_int, P, P, P, P]),
+        "sshash_cover_string_counts": (C.c_int, [P, P, P, C.POINTER(C.c_uint64)]),
         "sshash_route_packed_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P, P]),
         "sshash_route_bucket_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, C.c_int, P, P, P, P]),
         "sshash_route_bucket_by_key_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P, P, P]),
@@ -219,6 +225,8 @@ C_ABI_SYMBOLS = (
     "sshash_streaming_query_from_file sshash_streaming_query sshash_streaming_query_device "
     "sshash_streaming_query_per_read sshash_streaming_query_per_read_device sshash_streaming_query_from_file_per_read "
     "sshash_streaming_runs sshash_streaming_runs_device "
+    "sshash_cover_words sshash_streaming_cover sshash_streaming_cover_device sshash_streaming_cover_from_file "
+    "sshash_cover_string_counts sshash_cover_string_counts_device "
     "sshash_streaming_lookup sshash_streaming_lookup_device sshash_sharded_lookup_device sshash_sharded_lookup_rccl "
     "sshash_route_packed_device sshash_route_bucket_device sshash_route_bucket_by_key_device sshash_route_combine_device "
     "sshash_iterate_packed sshash_iterate_packed_device sshash_check_device"
@@ -750,6 +758,62 @@ class Dictionary:
                                                     int(total_bases), C.c_void_p(d_run_offsets), C.c_void_p(d_runs), int(runs_capacity),
                                                     C.c_void_p(d_report), C.c_void_p(stream)))
 
+    # ---- streaming cover: which k-mers of the dictionary a read set holds ---------------------------
+    def cover_words(self) -> int:
+        """Words of a cover bitmap: ceil(num_kmers / 64); k-mer id i is bit i & 63 of word i >> 6."""
+        words = C.c_uint64(0)
+        _check(_load().sshash_cover_words(self._h, C.byref(words)))
+        return int(words.value)
+
+    def _cover_array(self, cover) -> np.ndarray:
+        words = self.cover_words()
+        if cover is None:
+            return np.zeros(words, dtype=np.uint64)
+        if not (isinstance(cover, np.ndarray) and cover.dtype == np.uint64 and cover.ndim == 1 and cover.size == words and cover.flags.c_contiguous):
+            raise ValueError(f"cover: a contiguous uint64 array of cover_words() = {words} words")
+        return cover
+
+    def streaming_cover(self, reads: Sequence[Union[str, bytes]], cover: Optional[np.ndarray] = None):
+        """WHICH k-mers of the dictionary the reads hold -> (cover, StreamingQueryReport): the ids of all positive k-mers of the reads
+        (the kmer_id values streaming_lookup returns, INVALID_U64 aside) as a bitmap of cover_words() uint64; `cover` (None: a zeroed one)
+        is ORed into, in place, and returned. cover_to_ids() lists the ids."""
+        chunks = [s.encode("ascii", "replace") if isinstance(s, str) else bytes(s) for s in reads]
+        offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
+        if chunks:
+            offsets[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
+        bases = np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8)
+        cover = self._cover_array(cover)
+        r = _Report()
+        _check(_load().sshash_streaming_cover(self._h, bases.ctypes.data, offsets.ctypes.data, len(chunks), cover.ctypes.data, C.byref(r)))
+        return cover, self._report(r)
+
+    def streaming_cover_device(self, device: int, d_bases: int, d_read_offsets: int, num_reads: int, d_cover: int, d_report: int = 0,
+                               stream: int = 0, total_bases: int = 0) -> None:
+        """Device buffers: d_cover (cover_words() uint64) is ORed into, d_report (0: none) six counters (accumulated into).
+        `total_bases` as for streaming_query_device."""
+        _check(_load().sshash_streaming_cover_device(self._h, int(device), C.c_void_p(d_bases), C.c_void_p(d_read_offsets), int(num_reads),
+                                                     int(total_bases), C.c_void_p(d_cover), C.c_void_p(d_report), C.c_void_p(stream)))
+
+    def streaming_cover_from_file(self, filename: str, cover: Optional[np.ndarray] = None, multiline: bool = False):
+        """A query file into one bitmap -> (cover, StreamingQueryReport); `cover` as for streaming_cover."""
+        cover = self._cover_array(cover)
+        r = _Report()
+        _check(_load().sshash_streaming_cover_from_file(self._h, os.fsencode(filename), 1 if multiline else 0, cover.ctypes.data, C.byref(r)))
+        return cover, self._report(r)
+
+    def cover_string_counts(self, cover: np.ndarray):
+        """-> (counts, total): covered k-mers of every string (num_strings uint64) and in all. CPU, no GPU needed."""
+        cover = self._cover_array(cover)
+        counts = np.zeros(max(self.num_strings(), 1), dtype=np.uint64)
+        total = C.c_uint64(0)
+        _check(_load().sshash_cover_string_counts(self._h, cover.ctypes.data if cover.size else counts.ctypes.data, counts.ctypes.data, C.byref(total)))
+        return counts[:self.num_strings()], int(total.value)
+
+    def cover_string_counts_device(self, device: int, d_cover: int, d_counts: int, d_total: int = 0, stream: int = 0) -> None:
+        """Device buffers: d_counts (num_strings uint64) and d_total (0: none; one uint64) are overwritten."""
+        _check(_load().sshash_cover_string_counts_device(self._h, int(device), C.c_void_p(d_cover), C.c_void_p(d_counts), C.c_void_p(d_total),
+                                                         C.c_void_p(stream)))
+
     def streaming_lookup(self, reads: Sequence[Union[str, bytes]], full: bool = False):
         """streaming_query::lookup for every k-mer of every read (reference include/streaming_query.hpp:56-109), batched.
         -> (list of LookupResult, one per read, len(read) - k + 1 entries each; StreamingQueryReport)."""
@@ -824,3 +888,19 @@ def expand_runs(run_offsets, runs, read_lengths, k: int):
             ori[at:at + count] = -1 if backward else 1
         out.append(LookupResult(kmer_id=ids, kmer_id_in_string=in_string, kmer_orientation=ori, string_id=sid))
     return out
+
+
+def cover_to_ids(cover) -> np.ndarray:
+    """The k-mer ids a cover bitmap holds, ascending (uint64): id i is bit i & 63 of word i >> 6."""
+    words = np.ascontiguousarray(cover, dtype="<u8")
+    bits = np.unpackbits(words.view(np.uint8), bitorder="little")
+    return np.flatnonzero(bits).astype(np.uint64)
+
+
+def ids_to_cover(ids, words: int) -> np.ndarray:
+    """The inverse: a bitmap of `words` uint64 with the bits of `ids` set (INVALID_U64 entries are skipped)."""
+    ids = np.asarray(ids, dtype=np.uint64).reshape(-1)
+    ids = ids[ids != np.uint64(INVALID_U64)]
+    cover = np.zeros(int(words), dtype=np.uint64)
+    np.bitwise_or.at(cover, (ids >> np.uint64(6)).astype(np.int64), np.uint64(1) << (ids & np.uint64(63)))
+    return cover

@@ -559,6 +559,84 @@ sshash_status sshash_streaming_runs(const sshash_dict* d, const char* bases, con
     });
 }
 
+sshash_status sshash_cover_words(const sshash_dict* d, uint64_t* words) {
+    if (!d || !words) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    *words = (d->idx->num_kmers + 63) / 64;
+    return SSHASH_OK;
+}
+
+sshash_status sshash_streaming_cover_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
+                                            uint64_t num_reads, uint64_t total_bases, uint64_t* cover, uint64_t* report, void* hip_stream) {
+    if (!d || (num_reads && (!bases || !read_offsets || !cover))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] { d->eng->streaming_cover_device(device, bases, read_offsets, num_reads, total_bases, cover, report, hip_stream); });
+}
+
+sshash_status sshash_streaming_cover(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
+                                     uint64_t* cover, sshash_streaming_report* report) {
+    if (!d || (num_reads && (!bases || !read_offsets || !cover))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (report) std::memset(report, 0, sizeof(*report));
+    return guarded([&] {
+        if (num_reads == 0) return;
+        const cover_bitmaps on_devices(*d->eng);
+        const streaming_report r = d->eng->streaming_cover_host(bases, read_offsets, num_reads, on_devices);
+        on_devices.or_into(cover);
+        if (report) fill_report(report, r);
+    });
+}
+
+sshash_status sshash_streaming_cover_from_file(const sshash_dict* d, const char* filename, int multiline, uint64_t* cover,
+                                               sshash_streaming_report* report) {
+    if (!d || !filename || !cover) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (report) std::memset(report, 0, sizeof(*report));
+    return guarded([&] {
+        read_stream in(filename, multiline != 0, d->idx->k);
+        if (!in.supported()) {
+            fprintf(stderr, "unsupported query file format\n");
+            return;
+        }
+        /* every kind of file takes the sequential reader (as sshash_streaming_query_from_file_per_read); the bitmaps stay on the
+           devices from the first batch to the last */
+        const cover_bitmaps on_devices(*d->eng);
+        streaming_report total;
+        for_each_batch(in, [&](read_batch const& batch) {
+            total += d->eng->streaming_cover_host(batch.bases.data(), batch.offsets.data(), batch.num_reads(), on_devices);
+        });
+        on_devices.or_into(cover);
+        if (report) fill_report(report, total);
+    });
+}
+
+sshash_status sshash_cover_string_counts_device(const sshash_dict* d, int device, const uint64_t* cover, uint64_t* counts, uint64_t* total,
+                                                void* hip_stream) {
+    if (!d || !cover || !counts) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] { d->eng->cover_string_counts_device(device, cover, counts, total, hip_stream); });
+}
+
+sshash_status sshash_cover_string_counts(const sshash_dict* d, const uint64_t* cover, uint64_t* counts, uint64_t* total) {
+    if (!d || !cover || !counts) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] {
+        host_index const& x = *d->idx;
+        /* set bits among the ids [lo, hi) */
+        auto bits_in = [cover](uint64_t lo, uint64_t hi) {
+            uint64_t n = 0;
+            while (lo < hi) {
+                const uint64_t end = std::min(hi, (lo | 63) + 1);  // the part of [lo, hi) inside lo's word
+                uint64_t w = cover[lo >> 6] >> (lo & 63);
+                if (end - lo < 64) w &= (uint64_t(1) << (end - lo)) - 1;
+                n += uint64_t(__builtin_popcountll(w));
+                lo = end;
+            }
+            return n;
+        };
+        uint64_t all = 0;
+        for (uint64_t s = 0; s < x.num_strings; ++s) {  // at_string_id(s): [endpoints[s] - s (k - 1), endpoints[s + 1] - (s + 1)(k - 1))
+            counts[s] = bits_in(x.endpoints[s] - s * (x.k - 1), x.endpoints[s + 1] - (s + 1) * (x.k - 1));
+            all += counts[s];
+        }
+        if (total) *total = all;
+    });
+}
+
 sshash_status sshash_streaming_lookup_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
                                              uint64_t num_reads, uint64_t total_bases, const sshash_results* out, uint64_t* report,
                                              void* hip_stream) {

@@ -48,6 +48,24 @@ struct run_sink {
     uint64_t capacity;
 };
 
+class engine;
+
+/* One cover bitmap (ceil(num_kmers / 64) words, zeroed) in the HBM of every resident replica, for the length of a host call or of a
+   whole query file (streaming.hip); throws no_device when no replica is resident. */
+class cover_bitmaps {
+public:
+    explicit cover_bitmaps(engine const& eng);
+    ~cover_bitmaps();
+    cover_bitmaps(cover_bitmaps const&) = delete;
+    cover_bitmaps& operator=(cover_bitmaps const&) = delete;
+    uint64_t* on(int device) const;          // the bitmap on `device` (device pointer)
+    void or_into(uint64_t* h_cover) const;  // every replica's bitmap ORed into the caller's host bitmap; the lanes' work is done
+private:
+    uint64_t m_words;
+    std::vector<int> m_devices;
+    std::vector<uint64_t*> m_bitmaps;
+};
+
 class engine {
 public:
     explicit engine(std::shared_ptr<host_index> idx);
@@ -129,7 +147,8 @@ public:
     /* The same with one report PER READ: `rows` (host, n_reads x 6 words in the order of the device report, row r for read r; null:
        the totals only) is overwritten; returns the totals. A piece that holds a read above 2^16 bases takes the position-parallel
        pipeline, the others the run kernel; both give the same rows. */
-    streaming_report streaming_query_per_read_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* rows) const;
+    streaming_report streaming_query_per_read_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* rows,
+                                                   cover_bitmaps const* cover = nullptr /* streaming_cover_host */) const;
     /* An uncompressed FASTQ file, read and parsed by the lanes themselves (reads.hpp: fastq_pieces): every lane takes pieces of
        the file from a shared counter, parses a piece straight into its pinned block, uploads it and runs the streaming
        kernels -- no single reader thread, no intermediate batch. Returns false when the file turned out not to be four lines
@@ -154,6 +173,19 @@ public:
     streaming_report streaming_runs_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* run_offsets, void* runs,
                                          uint64_t runs_capacity) const;
 
+    /* WHICH k-mers of the dictionary the reads hold (sshash_streaming_cover[_device] in include/sshash_amd.h): bit i & 63 of word i >> 6
+       of `d_cover` (ceil(num_kmers / 64) words) for k-mer id i, ORed into. Device buffers, asynchronous, always the run kernel, its cover
+       form: one launch; `d_report` (nullable) is accumulated into. */
+    void streaming_cover_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
+                                uint64_t* d_cover, uint64_t* d_report, void* stream) const;
+    /* Host buffers, over all resident replicas, into the bitmaps `cover` keeps on them (the caller ORs those into its own when it is
+       done: cover_bitmaps::or_into); a piece that holds a read above 2^16 bases takes the position-parallel pipeline and marks from
+       its per-k-mer ids, which gives the same bits. Returns the totals. */
+    streaming_report streaming_cover_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, cover_bitmaps const& cover) const;
+    /* Covered k-mers per string out of a cover bitmap, device buffers, asynchronous: `d_counts` (num_strings words) and `d_total`
+       (one word, nullable) are overwritten. */
+    void cover_string_counts_device(int device, uint64_t const* d_cover, uint64_t* d_counts, uint64_t* d_total, void* stream) const;
+
     /* Per-k-mer results of the streaming query (streaming_query::lookup for every k-mer of every read,
        include/streaming_query.hpp:56-109): entry read_offsets[r] + j of every non-null array of `d_out` = the k-mer
        starting at base j of read r; places where no k-mer starts are left untouched. `d_report` (nullable): the six
@@ -162,7 +194,8 @@ public:
                                  uint64_t total_bases, result_view const& d_out, uint64_t* d_report, void* stream,
                                  uint64_t* d_rows = nullptr /* one report per read, n_reads x 6 words, ADDED to */,
                                  run_sink const* d_runs = nullptr /* the reads' runs, compacted out of the per-k-mer results: run_offsets overwritten,
-                                                                      records below its capacity written */) const;
+                                                                      records below its capacity written */,
+                                 uint64_t* d_cover = nullptr /* a cover bitmap: the ids of the positive k-mers ORed into it */) const;
     streaming_report streaming_lookup_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads,
                                            result_view const& h_out) const;
 

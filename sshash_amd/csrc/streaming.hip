@@ -295,8 +295,12 @@ __device__ __forceinline__ void row_flush(uint64_t* __restrict__ row, bool parti
                          cursor at sink.run_offsets[r] -- the counts of a STREAM_RUN_COUNTS launch over the same reads, scanned -- and
                          stores the record of every hit where its run has been measured (top of the turn after the hit; a hit that
                          nothing can follow: where it is found), two 16-byte stores, nothing at or beyond sink.capacity and nothing at
-                         or beyond run_offsets[r + 1]. The hit's string travels across the turn in one more register. */
-enum : int { STREAM_TOTALS = 0, STREAM_ROWS = 1, STREAM_RUN_COUNTS = 2, STREAM_RUN_RECORDS = 3 };
+                         or beyond run_offsets[r + 1]. The hit's string travels across the turn in one more register.
+     STREAM_COVER        the six counters of the batch as STREAM_TOTALS, and WHICH k-mers of the dictionary the reads hold: where the record form
+                         stores a run's record this one marks the run's range of k-mer ids in the bitmap at sink.records (cover_mark: bit
+                         i & 63 of word i >> 6 for k-mer id i) -- the hit's string travels across the turn as there (kmer_id = off - sid * (k - 1)).
+                         One launch: no count per read, no cursor, no run_offsets, and sink.capacity means nothing. */
+enum : int { STREAM_TOTALS = 0, STREAM_ROWS = 1, STREAM_RUN_COUNTS = 2, STREAM_RUN_RECORDS = 3, STREAM_COVER = 4 };
 
 /* the record of the run of `n` k-mers whose first (in read order) starts at base `at` of the packed reads and lies at offset `off` of
    the strings, in string `sid`: to place `cursor` of the records, unless that is past what the read or the caller has room for */
@@ -310,12 +314,36 @@ __device__ __forceinline__ void run_record_store(dict_view const& d, run_sink co
     rec[1] = make_uint4(uint32_t(in_string), uint32_t(in_string >> 32), read_pos, length);
 }
 
+/* the k-mer ids [lo, hi), hi > lo, into the bitmap: an atomic OR (nothing comes back: the lane does not wait for it) for the first and the
+   last word -- other runs may end in them --, a plain store for the words in between: whoever else touches such a word ORs into it or
+   stores the same all-ones, and all-ones is what every order of those leaves behind. Ids at or above num_kmers are in no run. */
+__device__ __forceinline__ void cover_mark(uint64_t* __restrict__ cover, uint64_t lo, uint64_t hi) {
+    const uint64_t w0 = lo >> 6, w1 = (hi - 1) >> 6;
+    const unsigned long long first = ~0ULL << (lo & 63u), last = ~0ULL >> (63u - (uint32_t(hi - 1) & 63u));
+    unsigned long long* const words = reinterpret_cast<unsigned long long*>(cover);
+    if (w0 == w1) {
+        (void)__hip_atomic_fetch_or(words + w0, first & last, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    (void)__hip_atomic_fetch_or(words + w0, first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (uint64_t w = w0 + 1; w < w1; ++w) words[w] = ~0ULL;
+    (void)__hip_atomic_fetch_or(words + w1, last, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+/* the run of `n` k-mers whose first (in read order) lies at offset `off` of the strings, in string `sid`: forward its ids go up from that
+   k-mer's, backward down (run_record_store: the same run as a record) */
+__device__ __forceinline__ void cover_mark_run(dict_view const& d, run_sink const& sink, uint64_t off, uint32_t sid, int ori, uint64_t n) {
+    const uint64_t kmer_id = off - uint64_t(sid) * (d.k - 1);
+    const uint64_t lo = ori > 0 ? kmer_id : kmer_id + 1 - n;
+    cover_mark(static_cast<uint64_t*>(sink.records), lo, lo + n);
+}
+
 template <int W, bool CANON, bool SK, int MODE>
 __global__ void __launch_bounds__(256, SSHASH_STREAM_WAVES)
 streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, const uint64_t* __restrict__ packed,
                      const uint64_t* __restrict__ okay, const uint64_t* __restrict__ offsets, const uint64_t n_reads,
                      const uint64_t reads_per_wave, const uint32_t move_out_every, uint64_t* __restrict__ report, const run_sink sink) {
-    constexpr bool PER_READ = MODE == STREAM_ROWS, COUNT_RUNS = MODE == STREAM_RUN_COUNTS, RECORDS = MODE == STREAM_RUN_RECORDS;
+    constexpr bool PER_READ = MODE == STREAM_ROWS, COUNT_RUNS = MODE == STREAM_RUN_COUNTS, RECORDS = MODE == STREAM_RUN_RECORDS, COVER = MODE == STREAM_COVER;
     __shared__ uint4 stage[SK ? 4 * 256 : 1];  // a wave's 64 bucket lines on their way from the quads that fetch them to the lanes that own them
     uint4* const wave_stage = stage + (SK ? (threadIdx.x >> 6) * 256 : 0);
     /* the counters are 32 bits wide in the lanes (six registers fewer than five 64-bit ones: with them the k <= 63 kernel fits five waves a
@@ -410,6 +438,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
         if (pending) {
             const uint64_t b = cur + k - 1, valid_end = inv < rd_end ? inv : rd_end;
             const uint64_t run = extend_run<W>(d, packed, off, ori, b, valid_end - b, run_step_load<W>(d, packed, off, ori > 0, b, 0));
+            if constexpr (COVER) cover_mark_run(d, sink, off, hit_sid, ori, run + 1);
             if constexpr (RECORDS) {  // (the hit lies a base before cur)
                 run_record_store(d, sink, offsets, wave_first + my_row, cursor, cur - 1, off, hit_sid, ori, run + 1);
                 ++cursor;
@@ -641,7 +670,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                     found = r.outcome == FAST_HIT;
                     off = r.kmer_offset;
                     ori = r.orientation;
-                    if constexpr (RECORDS) hit_sid = r.string_id;
+                    if constexpr (RECORDS || COVER) hit_sid = r.string_id;
                     const bool stands = !found && !(where & WALK_VISITED);
                     if (stands || (where & WALK_HEAVY_PENDING)) {
                         /* a miss that stands for the k-mers behind this one: those that elect the same key occurrence (sk_key_persists)
@@ -679,7 +708,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                 found = h.found;
                 off = h.kmer_offset;
                 ori = h.orientation;
-                if constexpr (RECORDS) hit_sid = h.string_id;
+                if constexpr (RECORDS || COVER) hit_sid = h.string_id;
                 neg_unknown_mini = !SK && !h.found && !h.minimizer_found;
             }
         }
@@ -694,6 +723,9 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                         run_record_store(d, sink, offsets, wave_first + my_row, cursor, cur, off, hit_sid, ori, 1);
                         ++cursor;
                     }
+                }
+                if constexpr (COVER) {
+                    if (!pending) cover_mark_run(d, sink, off, hit_sid, ori, 1);  // a run of one
                 }
             } else {
                 ++c_negative;
@@ -816,8 +848,9 @@ void exclusive_scan_u64(uint64_t* data, uint64_t n, uint64_t* sums, hipStream_t 
 }
 
 /* `run_phases` (with `sink`): RUNS_COUNT -- sink.run_offsets becomes the CSR offsets of the reads' runs (the counting form of the kernel, then
-   the scan; `report` as without, may be null) --, RUNS_WRITE -- the records, for run_offsets that hold those offsets --, or both. */
-enum : int { RUNS_COUNT = 1, RUNS_WRITE = 2 };
+   the scan; `report` as without, may be null) --, RUNS_WRITE -- the records, for run_offsets that hold those offsets --, or both; or
+   RUNS_COVER alone -- the cover form, ONE launch: the runs' k-mer ids marked in the bitmap at sink.records, `report` as without, may be null. */
+enum : int { RUNS_COUNT = 1, RUNS_WRITE = 2, RUNS_COVER = 4 };
 template <int W, bool CANON>
 void launch_streaming_runs(device_replica const* rep, dict_view const& d, char const* bases, uint64_t const* offsets, uint64_t n_reads,
                            uint64_t total_bases, uint64_t* report, hipStream_t s, uint64_t* rows = nullptr /* per read: n_reads x 6 words; `report` may then be null */,
@@ -847,6 +880,17 @@ void launch_streaming_runs(device_replica const* rep, dict_view const& d, char c
     const dim3 grid(uint32_t(waves / 4)), block(256);
     const uint32_t move_out_every = uint32_t(test_hook_u64("stream_move_out_every", uint64_t(1) << 16, 1, uint64_t(1) << 16));
     if (run_phases) {
+        if (run_phases & RUNS_COVER) {
+            uint64_t* totals = report;
+            if (!totals) {  // (six counters nobody asked for, as the counting form's)
+                totals = scan_sums + scan_tiles(n_reads + 1);
+                HIP_CHECK(hipMemsetAsync(totals, 0, 6 * sizeof(uint64_t), s));
+            }
+            if (d.sk.enabled) hipLaunchKernelGGL((streaming_run_kernel<W, CANON, true, STREAM_COVER>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, totals, sink);
+            else hipLaunchKernelGGL((streaming_run_kernel<W, CANON, false, STREAM_COVER>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, totals, sink);
+            HIP_CHECK(hipGetLastError());
+            return;
+        }
         if (reads_per_wave >> 31) throw error(error_kind::argument, "too many reads for one call");  // (as below)
         if (run_phases & RUNS_COUNT) {
             uint64_t* totals = report;
@@ -964,6 +1008,28 @@ void engine::streaming_runs_passes(int device, char const* d_bases, uint64_t con
     else if (!wide && d.canonical) launch_streaming_runs<1, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, phases);
     else if (wide && !d.canonical) launch_streaming_runs<2, false>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, phases);
     else launch_streaming_runs<2, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, phases);
+}
+
+/* Which k-mers of the dictionary the reads hold (sshash_streaming_cover_device): the cover form of the run kernel, one launch. */
+void engine::streaming_cover_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
+                                    uint64_t* d_cover, uint64_t* d_report, void* stream) const {
+    device_replica const* rep = replica(device);  // (not resident: that error first)
+    if (n_reads == 0) return;
+    if (!d_cover) throw error(error_kind::argument, "cover pointer is null");
+    device_guard guard(device);
+    dict_view const& d = rep->view;
+    hipStream_t s = hipStream_t(stream);
+    const bool wide = d.k > 31;
+    if (total_bases == 0) {
+        HIP_CHECK(hipMemcpyAsync(&total_bases, d_read_offsets + n_reads, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (total_bases == 0) return;  // empty reads only: no k-mer
+    }
+    const run_sink sink{nullptr, d_cover, 0};
+    if (!wide && !d.canonical) launch_streaming_runs<1, false>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, RUNS_COVER);
+    else if (!wide && d.canonical) launch_streaming_runs<1, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, RUNS_COVER);
+    else if (wide && !d.canonical) launch_streaming_runs<2, false>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, RUNS_COVER);
+    else launch_streaming_runs<2, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, RUNS_COVER);
 }
 
 /* ---- per-k-mer results: the streaming query as a position-parallel pipeline -----------------------------------
@@ -1269,11 +1335,132 @@ stream_run_records_kernel(const uint8_t* __restrict__ marks, const uint64_t* __r
     rec[1] = make_uint4(uint32_t(in_string), uint32_t(in_string >> 32), uint32_t(p - offsets[lo]), uint32_t(n) | (orientation[p] > 0 ? 0u : 0x80000000u));
 }
 
+/* ---- the cover out of the per-k-mer results (the host calls' route for reads too long for one lane): one lane a place, the bit of its
+        k-mer's id ORed into the bitmap. Along a hit the ids of neighbouring places are neighbours, 64 of them in a word: the lanes of a
+        wave first OR their bits together wherever a lane further on holds the same word (any two bits of one word may be merged, whatever
+        lies between their lanes), and a lane whose predecessor holds that word leaves the atomic to it. ---- */
+__global__ void __launch_bounds__(256)
+cover_mark_ids_kernel(const uint8_t* __restrict__ flags, const uint64_t* __restrict__ kmer_id, const uint64_t total_bases, uint64_t* __restrict__ cover) {
+    const uint64_t p = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    uint64_t word = ~uint64_t(0), bits = 0;  // (no k-mer, or not in the dictionary: no word)
+    if (p < total_bases && (flags[p] & SQ_VALID)) {
+        const uint64_t id = kmer_id[p];
+        if (id != INVALID_U64) {
+            word = id >> 6;
+            bits = uint64_t(1) << (id & 63u);
+        }
+    }
+    if (__ballot(bits != 0) == 0) return;  // (uniform)
+    const uint64_t before = __shfl_up(word, 1, 64);
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+        const uint64_t w = __shfl_down(word, o, 64), b = __shfl_down(bits, o, 64);
+        if (lane + o < 64 && w == word) bits |= b;
+    }
+    if (bits == 0 || (lane > 0 && before == word)) return;
+    (void)__hip_atomic_fetch_or(reinterpret_cast<unsigned long long*>(cover) + word, (unsigned long long)bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+/* ---- covered k-mers per string: a segmented popcount of a cover bitmap. The ids of string s are [begin(s), begin(s + 1)),
+        begin(s) = endpoints[s] - s * (k - 1); strings hold from one k-mer to millions, so the lanes go over the bitmap's WORDS, one each.
+        A lane finds the string of its word's first id -- the workgroup's first lane by bisection over all strings, the others from
+        there: every string holds a k-mer, so the string of an id j ids further on is at most j strings further on, and as a rule it
+        is the same one or the next (a doubling search, then a bisection inside its last step) --, and cuts its word at every string
+        boundary inside it. The strings that END inside the word get their piece with one atomic each; the last piece belongs to a string
+        that may go on through the words of the lanes behind, so the lanes of a wave sum their last pieces over neighbours with the same
+        string first (stream_classify_rows_kernel does that for rows), and the first lane of such a stretch adds the sum. `counts` is
+        zeroed by the caller. The total: the popcount of the words, once a workgroup. ---- */
+__device__ __forceinline__ uint64_t string_first_id(const uint64_t* __restrict__ endpoints, uint64_t s, uint32_t k) { return endpoints[s] - s * (k - 1); }
+
+__global__ void __launch_bounds__(256)
+cover_string_counts_kernel(const uint64_t* __restrict__ cover, const uint64_t num_kmers, const uint64_t* __restrict__ endpoints, const uint64_t num_strings,
+                           const uint32_t k, uint64_t* __restrict__ counts, uint64_t* __restrict__ total) {
+    __shared__ uint64_t block_string;
+    __shared__ uint64_t block_sum[4];
+    const uint64_t words = (num_kmers + 63) / 64;
+    const uint64_t w = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    if (threadIdx.x == 0) {  // the string of the workgroup's first id: the largest s with begin(s) <= id (w < words: the grid holds no empty workgroup)
+        const uint64_t id = w * 64;
+        uint64_t lo = 0, hi = num_strings - 1;
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo + 1) / 2;
+            if (string_first_id(endpoints, mid, k) <= id) lo = mid;
+            else hi = mid - 1;
+        }
+        block_string = lo;
+    }
+    __syncthreads();
+    const bool has = w < words;
+    uint64_t bits = 0;
+    uint32_t last_string = ~0u, last_count = 0;
+    if (has) {
+        const uint64_t id0 = w * 64, id_end = id0 + 64 < num_kmers ? id0 + 64 : num_kmers;
+        bits = cover[w];
+        if (id_end - id0 < 64) bits &= (uint64_t(1) << (id_end - id0)) - 1;  // (bits at or above num_kmers are no k-mers)
+        /* my first string: the largest s in [block_string, num_strings) with begin(s) <= id0 */
+        uint64_t lo = block_string, step = 1;
+        while (lo + step < num_strings && string_first_id(endpoints, lo + step, k) <= id0) {
+            lo += step;
+            step <<= 1;
+        }
+        uint64_t hi = lo + step - 1 < num_strings - 1 ? lo + step - 1 : num_strings - 1;  // (begin(lo + step) > id0, or there is no such string)
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo + 1) / 2;
+            if (string_first_id(endpoints, mid, k) <= id0) lo = mid;
+            else hi = mid - 1;
+        }
+        uint64_t s = lo, at = id0;
+        for (;;) {
+            const uint64_t next = string_first_id(endpoints, s + 1, k);  // (begin(num_strings) = num_kmers)
+            if (next >= id_end) break;
+            /* string s ends inside the word: ids [at, next) */
+            const uint64_t piece = (bits >> (at - id0)) & ((uint64_t(1) << (next - at)) - 1);  // (next - at < 64: next < id_end)
+            if (piece) atomicAdd(reinterpret_cast<unsigned long long*>(counts + s), (unsigned long long)__popcll(piece));
+            at = next;
+            ++s;
+        }
+        last_string = uint32_t(s);
+        last_count = uint32_t(__popcll(bits >> (at - id0)));
+    }
+    /* the last pieces: summed over the lanes behind that are in the same string (they are neighbours: strings follow each other) */
+    const uint32_t before = __shfl_up(last_string, 1, 64);
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+        const uint32_t s = __shfl_down(last_string, o, 64), c = __shfl_down(last_count, o, 64);
+        if (lane + o < 64 && s == last_string) last_count += c;
+    }
+    if (has && last_count && (lane == 0 || before != last_string))
+        atomicAdd(reinterpret_cast<unsigned long long*>(counts + last_string), (unsigned long long)last_count);
+    if (!total) return;  // (uniform)
+    const uint64_t wave_bits = wave_sum(uint64_t(__popcll(bits)));
+    if (lane == 0) block_sum[threadIdx.x >> 6] = wave_bits;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint64_t sum = block_sum[0] + block_sum[1] + block_sum[2] + block_sum[3];
+        if (sum) atomicAdd(reinterpret_cast<unsigned long long*>(total), (unsigned long long)sum);
+    }
+}
+
+void engine::cover_string_counts_device(int device, uint64_t const* d_cover, uint64_t* d_counts, uint64_t* d_total, void* stream) const {
+    device_replica const* rep = replica(device);
+    if (!d_cover || !d_counts) throw error(error_kind::argument, "null pointer");
+    device_guard guard(device);
+    dict_view const& d = rep->view;
+    hipStream_t s = hipStream_t(stream);
+    HIP_CHECK(hipMemsetAsync(d_counts, 0, d.num_strings * sizeof(uint64_t), s));
+    if (d_total) HIP_CHECK(hipMemsetAsync(d_total, 0, sizeof(uint64_t), s));
+    const uint64_t words = (d.num_kmers + 63) / 64;
+    if (words == 0 || d.num_strings == 0) return;
+    hipLaunchKernelGGL(cover_string_counts_kernel, dim3(uint32_t((words + 255) / 256)), dim3(256), 0, s, d_cover, d.num_kmers, d.endpoints, d.num_strings, d.k,
+                       d_counts, d_total);
+    HIP_CHECK(hipGetLastError());
+}
+
 void engine::streaming_lookup_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
                                      uint64_t total_bases, result_view const& d_out, uint64_t* d_report, void* stream, uint64_t* d_rows,
-                                     run_sink const* runs) const {
+                                     run_sink const* runs, uint64_t* d_cover) const {
     device_replica const* rep = replica(device);
-    if (!d_out.kmer_id && !d_report && !d_rows && !runs) throw error(error_kind::argument, "neither a kmer_id array nor a report to fill");
+    if (!d_out.kmer_id && !d_report && !d_rows && !runs && !d_cover) throw error(error_kind::argument, "neither a kmer_id array nor a report to fill");
     if (d_out.minimizer_found) throw error(error_kind::argument, "the streaming lookup does not report minimizer_found");
     if (n_reads == 0 || total_bases == 0) return;
     device_guard guard(device);
@@ -1318,6 +1505,10 @@ void engine::streaming_lookup_device(int device, char const* d_bases, uint64_t c
     if (d_rows) {
         hipLaunchKernelGGL(stream_classify_rows_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, flags, total_bases, ids, sid, ori,
                            d_read_offsets, n_reads, d_rows);
+        HIP_CHECK(hipGetLastError());
+    }
+    if (d_cover) {
+        hipLaunchKernelGGL(cover_mark_ids_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, flags, ids, total_bases, d_cover);
         HIP_CHECK(hipGetLastError());
     }
     if (runs) {
@@ -1407,8 +1598,10 @@ streaming_report engine::streaming_query_host(char const* bases, uint64_t const*
 }
 
 /* The same pieces and lanes; with `rows` (n_reads x 6 words, host) a lane's device block also holds a row for every read of the largest
-   piece, and a piece's rows come back into the caller's array at the piece's first read. */
-streaming_report engine::streaming_query_per_read_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* rows) const {
+   piece, and a piece's rows come back into the caller's array at the piece's first read. With `cover` (and no rows) a piece's k-mers
+   are marked in the bitmap that `cover` keeps on the lane's device: the lanes of a device share it, OR commutes. */
+streaming_report engine::streaming_query_per_read_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* rows,
+                                                       cover_bitmaps const* cover) const {
     if (n_reads == 0) return {};
     const std::vector<int> devs = resident_devices(*this);
     const uint64_t G = devs.size();
@@ -1465,6 +1658,9 @@ streaming_report engine::streaming_query_per_read_host(char const* bases, uint64
                 if (long_read) streaming_lookup_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, result_view{}, d_report, s, d_rows);
                 else if (nb) streaming_query_per_read_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, d_rows, d_report, s);
                 HIP_CHECK(hipMemcpyAsync(hp + rows_at, d_rows, row_bytes, hipMemcpyDeviceToHost, s));  // (through the lane's pinned block: the caller's array is pageable)
+            } else if (cover) {
+                if (long_read) streaming_lookup_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, result_view{}, d_report, s, nullptr, nullptr, cover->on(device));
+                else if (nb) streaming_cover_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, cover->on(device), d_report, s);
             } else if (long_read) {
                 streaming_lookup_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, result_view{}, d_report, s);
             } else {
@@ -1478,6 +1674,64 @@ streaming_report engine::streaming_query_per_read_host(char const* bases, uint64
     streaming_report total;
     for (auto const& p : partial) total += p;
     return total;
+}
+
+/* ---- the cover bitmaps of a host call: one per resident replica, zeroed, in HBM for as long as the object lives (a call over host
+        buffers, or a whole query file), ORed into the caller's host bitmap at the end ---- */
+cover_bitmaps::cover_bitmaps(engine const& eng) : m_words((eng.index().num_kmers + 63) / 64), m_devices(resident_devices(eng)) {
+    int prev = 0;
+    HIP_CHECK(hipGetDevice(&prev));
+    try {
+        for (int device : m_devices) {
+            HIP_CHECK(hipSetDevice(device));
+            void* p = nullptr;
+            HIP_CHECK(hipMalloc(&p, std::max<uint64_t>(m_words, 1) * sizeof(uint64_t)));
+            m_bitmaps.push_back(static_cast<uint64_t*>(p));
+            HIP_CHECK(hipMemsetAsync(p, 0, std::max<uint64_t>(m_words, 1) * sizeof(uint64_t), nullptr));
+            HIP_CHECK(hipStreamSynchronize(nullptr));  // (the lanes' streams do not wait for the null stream)
+        }
+    } catch (...) {
+        for (size_t i = 0; i < m_bitmaps.size(); ++i) {
+            (void)hipSetDevice(m_devices[i]);
+            (void)hipFree(m_bitmaps[i]);
+        }
+        (void)hipSetDevice(prev);
+        throw;
+    }
+    (void)hipSetDevice(prev);
+}
+
+cover_bitmaps::~cover_bitmaps() {
+    int prev = 0;
+    if (hipGetDevice(&prev) != hipSuccess) return;
+    for (size_t i = 0; i < m_bitmaps.size(); ++i) {
+        (void)hipSetDevice(m_devices[i]);
+        (void)hipFree(m_bitmaps[i]);
+    }
+    (void)hipSetDevice(prev);
+}
+
+uint64_t* cover_bitmaps::on(int device) const {
+    for (size_t i = 0; i < m_devices.size(); ++i)
+        if (m_devices[i] == device) return m_bitmaps[i];
+    throw error(error_kind::internal, "no cover bitmap on this device");
+}
+
+void cover_bitmaps::or_into(uint64_t* h_cover) const {
+    const uint64_t chunk = uint64_t(1) << 21;  // 16 MiB of words at a time: the host side stays bounded
+    std::vector<uint64_t> part(std::min(chunk, m_words));
+    for (size_t i = 0; i < m_devices.size(); ++i) {
+        device_guard guard(m_devices[i]);
+        for (uint64_t at = 0; at < m_words; at += chunk) {
+            const uint64_t n = std::min(chunk, m_words - at);
+            HIP_CHECK(hipMemcpy(part.data(), m_bitmaps[i] + at, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            for (uint64_t j = 0; j < n; ++j) h_cover[at + j] |= part[j];
+        }
+    }
+}
+
+streaming_report engine::streaming_cover_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, cover_bitmaps const& cover) const {
+    return streaming_query_per_read_host(bases, read_offsets, n_reads, nullptr, &cover);
 }
 
 /* The runs of every read, host buffers (sshash_streaming_runs): the pieces and lanes of streaming_query_per_read_host. A piece's
