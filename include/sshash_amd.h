@@ -395,9 +395,13 @@ sshash_status sshash_route_packed_device(const sshash_dict* d, int device, const
  *      owner; `cursors`: num_shards device uint64, zeroed by the caller) -- the send counts of the all-to-all;
  *   2. cursors[s] = index of the first message of shard s (exclusive prefix sum of the counts): message t gets
  *      send[t*W .. t*W+W) = the packed k-mer and slots[t] = the index of its query. Messages of one shard are
- *      contiguous; their order inside the shard is unspecified. n < 2^32, num_shards <= 1024.
+ *      contiguous; their order inside the shard is unspecified. n < 2^32, num_shards <= 1024. The second call elects the
+ *      owners again and advances the cursors as the first did: afterwards cursors[s] = index behind the last message of
+ *      shard s. Words of `send` and `slots` behind the last message are not written.
+ * Both calls: SSHASH_ERR_ARGUMENT, before anything is launched, for num_shards outside [1, 1024], n >= 2^32, or only one
+ * of send / slots; n == 0 writes nothing.
  * sshash_route_combine_device: out[slots[t]] = replies[t] for every reply != UINT64_MAX (`out` pre-filled with
- * UINT64_MAX by the caller); owners that both find a k-mer return the same id. */
+ * UINT64_MAX by the caller; a reply of UINT64_MAX writes nothing); owners that both find a k-mer return the same id. */
 sshash_status sshash_route_bucket_device(const sshash_dict* d, int device, const uint64_t* kmers, uint64_t n,
                                          uint32_t num_shards, int check_reverse_complement, uint64_t* cursors,
                                          uint64_t* send, uint32_t* slots, void* hip_stream);
