@@ -211,11 +211,6 @@ public:
     device_replica const* replica(int device) const;
 
 private:
-    /* the passes of streaming_runs_device (streaming.hip): `count` -- d_run_offsets from the reads, `d_report` accumulated into --,
-       `write` -- the records, for a d_run_offsets that holds the offsets of these very reads (streaming_runs_host counts, sizes a
-       piece's records from the count and writes) */
-    void streaming_runs_passes(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
-                               run_sink const& sink, uint64_t* d_report, void* stream, bool count, bool write) const;
     std::shared_ptr<host_index> m_idx;
     /* to_device may run while other host threads query: readers share, the upload's final push_back is exclusive */
     mutable std::shared_mutex m_replicas_mutex;

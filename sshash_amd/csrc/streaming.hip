@@ -847,14 +847,33 @@ void exclusive_scan_u64(uint64_t* data, uint64_t n, uint64_t* sums, hipStream_t 
     HIP_CHECK(hipGetLastError());
 }
 
+/* The one place that launches the run kernel: (k > 31, canonical, skew table) -> <W, CANON, SK>, in the form MODE. */
+template <int MODE>
+void launch_run_kernel(device_replica const* rep, dict_view const& d, dim3 grid, dim3 block, hipStream_t s, uint64_t const* packed, uint64_t const* okay,
+                       uint64_t const* offsets, uint64_t n_reads, uint64_t reads_per_wave, uint32_t move_out_every, uint64_t* report, run_sink const& sink) {
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, report, sink);
+        HIP_CHECK(hipGetLastError());
+    };
+    const bool wide = d.k > 31, canon = d.canonical, sk = d.sk.enabled;
+    if (!wide && !canon && !sk) launch(streaming_run_kernel<1, false, false, MODE>);
+    else if (!wide && !canon) launch(streaming_run_kernel<1, false, true, MODE>);
+    else if (!wide && !sk) launch(streaming_run_kernel<1, true, false, MODE>);
+    else if (!wide) launch(streaming_run_kernel<1, true, true, MODE>);
+    else if (!canon && !sk) launch(streaming_run_kernel<2, false, false, MODE>);
+    else if (!canon) launch(streaming_run_kernel<2, false, true, MODE>);
+    else if (!sk) launch(streaming_run_kernel<2, true, false, MODE>);
+    else launch(streaming_run_kernel<2, true, true, MODE>);
+}
+
 /* `run_phases` (with `sink`): RUNS_COUNT -- sink.run_offsets becomes the CSR offsets of the reads' runs (the counting form of the kernel, then
    the scan; `report` as without, may be null) --, RUNS_WRITE -- the records, for run_offsets that hold those offsets --, or both; or
    RUNS_COVER alone -- the cover form, ONE launch: the runs' k-mer ids marked in the bitmap at sink.records, `report` as without, may be null. */
 enum : int { RUNS_COUNT = 1, RUNS_WRITE = 2, RUNS_COVER = 4 };
-template <int W, bool CANON>
-void launch_streaming_runs(device_replica const* rep, dict_view const& d, char const* bases, uint64_t const* offsets, uint64_t n_reads,
-                           uint64_t total_bases, uint64_t* report, hipStream_t s, uint64_t* rows = nullptr /* per read: n_reads x 6 words; `report` may then be null */,
+void launch_streaming_runs(device_replica const* rep, char const* bases, uint64_t const* offsets, uint64_t n_reads, uint64_t total_bases, uint64_t* report,
+                           hipStream_t s, uint64_t* rows = nullptr /* per read: n_reads x 6 words; `report` may then be null */,
                            run_sink sink = run_sink{nullptr, nullptr, 0}, int run_phases = 0) {
+    dict_view const& d = rep->view;
     /* two bits and a validity bit a base, in words of 32 and 64 bases; three words of slack behind the last base (a seed and a
        run read up to two words past their first) */
     const uint64_t packed_bytes = ((total_bases + 31) / 32 + 3) * 8, okay_bytes = ((total_bases + 63) / 64 + 2) * 8;
@@ -873,59 +892,67 @@ void launch_streaming_runs(device_replica const* rep, dict_view const& d, char c
     /* waves: as many as the chip holds at once -- a lane that finishes its read takes the next of its wave's share, and the longer the
        share, the better the lanes of a wave even out --, fewer for a small call (a piece of a query file: some 10^4 reads, many calls
        side by side on their own streams), down to two reads a lane */
-    const uint64_t max_waves = uint64_t(256) * 4 * SSHASH_STREAM_WAVES;  // (what the chip holds of this kernel: five waves a SIMD, 96 registers)  // (what the chip holds of this kernel: 96 registers at k <= 31, 106 at k <= 63)
+    const uint64_t max_waves = uint64_t(256) * 4 * SSHASH_STREAM_WAVES;  // (what the chip holds of this kernel: 256 CUs, four SIMDs each, SSHASH_STREAM_WAVES waves a SIMD)
     uint64_t waves = std::min<uint64_t>(max_waves, std::max<uint64_t>(1, n_reads / (64 * 2)));
     waves = (waves + 3) / 4 * 4;
     const uint64_t reads_per_wave = (n_reads + waves - 1) / waves;
     const dim3 grid(uint32_t(waves / 4)), block(256);
     const uint32_t move_out_every = uint32_t(test_hook_u64("stream_move_out_every", uint64_t(1) << 16, 1, uint64_t(1) << 16));
-    if (run_phases) {
-        if (run_phases & RUNS_COVER) {
-            uint64_t* totals = report;
-            if (!totals) {  // (six counters nobody asked for, as the counting form's)
-                totals = scan_sums + scan_tiles(n_reads + 1);
-                HIP_CHECK(hipMemsetAsync(totals, 0, 6 * sizeof(uint64_t), s));
-            }
-            if (d.sk.enabled) hipLaunchKernelGGL((streaming_run_kernel<W, CANON, true, STREAM_COVER>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, totals, sink);
-            else hipLaunchKernelGGL((streaming_run_kernel<W, CANON, false, STREAM_COVER>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, totals, sink);
-            HIP_CHECK(hipGetLastError());
-            return;
-        }
-        if (reads_per_wave >> 31) throw error(error_kind::argument, "too many reads for one call");  // (as below)
+    /* the cover and the counting form count the batch as they go: where nobody asked for the six counters they go into the scratch */
+    auto totals = [&]() {
+        if (report) return report;
+        uint64_t* spare = scan_sums + scan_tiles(n_reads + 1);
+        HIP_CHECK(hipMemsetAsync(spare, 0, 6 * sizeof(uint64_t), s));
+        return spare;
+    };
+    /* the row, counting and record forms keep a lane's read as a 31-bit index into its wave's share -- not the cover and totals forms */
+    if ((rows || (run_phases & (RUNS_COUNT | RUNS_WRITE))) && reads_per_wave >> 31) throw error(error_kind::argument, "too many reads for one call");
+    if (run_phases & RUNS_COVER) {
+        launch_run_kernel<STREAM_COVER>(rep, d, grid, block, s, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, totals(), sink);
+    } else if (run_phases) {
         if (run_phases & RUNS_COUNT) {
-            uint64_t* totals = report;
-            if (!totals) {
-                totals = scan_sums + scan_tiles(n_reads + 1);
-                HIP_CHECK(hipMemsetAsync(totals, 0, 6 * sizeof(uint64_t), s));
-            }
-            if (d.sk.enabled) hipLaunchKernelGGL((streaming_run_kernel<W, CANON, true, STREAM_RUN_COUNTS>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, totals, sink);
-            else hipLaunchKernelGGL((streaming_run_kernel<W, CANON, false, STREAM_RUN_COUNTS>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, totals, sink);
-            HIP_CHECK(hipGetLastError());
+            launch_run_kernel<STREAM_RUN_COUNTS>(rep, d, grid, block, s, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, totals(), sink);
             HIP_CHECK(hipMemsetAsync(sink.run_offsets + n_reads, 0, sizeof(uint64_t), s));
             exclusive_scan_u64(sink.run_offsets, n_reads + 1, scan_sums, s);
         }
-        if (run_phases & RUNS_WRITE) {
-            if (d.sk.enabled) hipLaunchKernelGGL((streaming_run_kernel<W, CANON, true, STREAM_RUN_RECORDS>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, static_cast<uint64_t*>(nullptr), sink);
-            else hipLaunchKernelGGL((streaming_run_kernel<W, CANON, false, STREAM_RUN_RECORDS>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, static_cast<uint64_t*>(nullptr), sink);
-            HIP_CHECK(hipGetLastError());
-        }
-        return;
-    }
-    if (rows) {
-        if (reads_per_wave >> 31) throw error(error_kind::argument, "too many reads for one call");  // (a lane keeps its read's index in its wave's share in 31 bits)
-        if (d.sk.enabled) hipLaunchKernelGGL((streaming_run_kernel<W, CANON, true, STREAM_ROWS>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, rows, sink);
-        else hipLaunchKernelGGL((streaming_run_kernel<W, CANON, false, STREAM_ROWS>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, rows, sink);
-        HIP_CHECK(hipGetLastError());
+        if (run_phases & RUNS_WRITE)
+            launch_run_kernel<STREAM_RUN_RECORDS>(rep, d, grid, block, s, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, nullptr, sink);
+    } else if (rows) {
+        launch_run_kernel<STREAM_ROWS>(rep, d, grid, block, s, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, rows, sink);
         if (report) {
             const uint32_t blocks = uint32_t(std::min<uint64_t>((n_reads + 255) / 256, 1024));
             hipLaunchKernelGGL(stream_rows_sum_kernel, dim3(blocks), dim3(256), 0, s, rows, n_reads, report);
             HIP_CHECK(hipGetLastError());
         }
+    } else {
+        launch_run_kernel<STREAM_TOTALS>(rep, d, grid, block, s, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, report, sink);
+    }
+}
+
+/* The packing pass covers bases [0, read_offsets[n_reads]): a caller that does not say how many that is (total_bases = 0: the C ABI's
+   device entry points) costs the launch one 8-byte read-back on its stream. */
+uint64_t resolve_total_bases(uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases, hipStream_t s) {
+    if (n_reads && total_bases == 0) {
+        HIP_CHECK(hipMemcpyAsync(&total_bases, d_read_offsets + n_reads, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    }
+    return total_bases;
+}
+
+/* The passes of streaming_runs_device: `count` -- sink.run_offsets from the reads, `d_report` accumulated into --, `write` -- the records,
+   for run_offsets that hold the offsets of these very reads (streaming_runs_host counts, sizes a piece's records from the count and
+   writes). */
+void streaming_runs_passes(engine const& eng, int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
+                           run_sink const& sink, uint64_t* d_report, hipStream_t s, bool count, bool write) {
+    device_replica const* rep = eng.replica(device);
+    device_guard guard(device);
+    total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
+    if (n_reads == 0 || total_bases == 0) {  // no read, or empty reads only: no run
+        if (count) HIP_CHECK(hipMemsetAsync(sink.run_offsets, 0, (n_reads + 1) * sizeof(uint64_t), s));
         return;
     }
-    if (d.sk.enabled) hipLaunchKernelGGL((streaming_run_kernel<W, CANON, true, STREAM_TOTALS>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, report, sink);
-    else hipLaunchKernelGGL((streaming_run_kernel<W, CANON, false, STREAM_TOTALS>), grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, report, sink);
-    HIP_CHECK(hipGetLastError());
+    const int phases = (count ? RUNS_COUNT : 0) | (write ? RUNS_WRITE : 0);
+    if (phases) launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, phases);
 }
 
 }  // namespace
@@ -935,20 +962,10 @@ void engine::streaming_query_device(int device, char const* d_bases, uint64_t co
     device_replica const* rep = replica(device);
     if (n_reads == 0) return;
     device_guard guard(device);
-    dict_view const& d = rep->view;
     hipStream_t s = hipStream_t(stream);
-    const bool wide = d.k > 31;
-    if (total_bases == 0) {
-        /* the packing pass covers bases [0, read_offsets[n_reads]): a caller that does not say how many that is (the C ABI's device
-           entry point) costs the launch one 8-byte read-back on its stream */
-        HIP_CHECK(hipMemcpyAsync(&total_bases, d_read_offsets + n_reads, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (total_bases == 0) return;
-    }
-    if (!wide && !d.canonical) launch_streaming_runs<1, false>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s);
-    else if (!wide && d.canonical) launch_streaming_runs<1, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s);
-    else if (wide && !d.canonical) launch_streaming_runs<2, false>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s);
-    else launch_streaming_runs<2, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s);
+    total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
+    if (total_bases == 0) return;
+    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s);
 }
 
 /* One report per read, by the run kernel whatever the reads' lengths (a caller with device buffers has cut its batch itself, as with
@@ -959,21 +976,13 @@ void engine::streaming_query_per_read_device(int device, char const* d_bases, ui
     if (n_reads == 0) return;
     if (!d_rows) throw error(error_kind::argument, "per-read output pointer is null");
     device_guard guard(device);
-    dict_view const& d = rep->view;
     hipStream_t s = hipStream_t(stream);
-    const bool wide = d.k > 31;
-    if (total_bases == 0) {
-        HIP_CHECK(hipMemcpyAsync(&total_bases, d_read_offsets + n_reads, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (total_bases == 0) {  // empty reads only: their rows are zero
-            HIP_CHECK(hipMemsetAsync(d_rows, 0, n_reads * 6 * sizeof(uint64_t), s));
-            return;
-        }
+    total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
+    if (total_bases == 0) {  // empty reads only: their rows are zero
+        HIP_CHECK(hipMemsetAsync(d_rows, 0, n_reads * 6 * sizeof(uint64_t), s));
+        return;
     }
-    if (!wide && !d.canonical) launch_streaming_runs<1, false>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, d_rows);
-    else if (!wide && d.canonical) launch_streaming_runs<1, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, d_rows);
-    else if (wide && !d.canonical) launch_streaming_runs<2, false>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, d_rows);
-    else launch_streaming_runs<2, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, d_rows);
+    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, d_rows);
 }
 
 /* The runs of every read (sshash_streaming_runs_device): count -> scan -> write, always the run kernel. */
@@ -983,31 +992,8 @@ void engine::streaming_runs_device(int device, char const* d_bases, uint64_t con
     if (n_reads == 0 && !d_run_offsets) return;
     if (!d_run_offsets) throw error(error_kind::argument, "run_offsets pointer is null");
     if (!d_runs && runs_capacity) throw error(error_kind::argument, "runs pointer is null");
-    streaming_runs_passes(device, d_bases, d_read_offsets, n_reads, total_bases, run_sink{d_run_offsets, d_runs, runs_capacity}, d_report, stream, true,
-                          runs_capacity != 0);
-}
-
-void engine::streaming_runs_passes(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
-                                   run_sink const& sink, uint64_t* d_report, void* stream, bool count, bool write) const {
-    device_replica const* rep = replica(device);
-    device_guard guard(device);
-    dict_view const& d = rep->view;
-    hipStream_t s = hipStream_t(stream);
-    const bool wide = d.k > 31;
-    if (n_reads && total_bases == 0) {
-        HIP_CHECK(hipMemcpyAsync(&total_bases, d_read_offsets + n_reads, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-    }
-    if (n_reads == 0 || total_bases == 0) {  // no read, or empty reads only: no run
-        if (count) HIP_CHECK(hipMemsetAsync(sink.run_offsets, 0, (n_reads + 1) * sizeof(uint64_t), s));
-        return;
-    }
-    const int phases = (count ? RUNS_COUNT : 0) | (write ? RUNS_WRITE : 0);
-    if (!phases) return;
-    if (!wide && !d.canonical) launch_streaming_runs<1, false>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, phases);
-    else if (!wide && d.canonical) launch_streaming_runs<1, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, phases);
-    else if (wide && !d.canonical) launch_streaming_runs<2, false>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, phases);
-    else launch_streaming_runs<2, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, phases);
+    streaming_runs_passes(*this, device, d_bases, d_read_offsets, n_reads, total_bases, run_sink{d_run_offsets, d_runs, runs_capacity}, d_report,
+                          hipStream_t(stream), true, runs_capacity != 0);
 }
 
 /* Which k-mers of the dictionary the reads hold (sshash_streaming_cover_device): the cover form of the run kernel, one launch. */
@@ -1017,19 +1003,10 @@ void engine::streaming_cover_device(int device, char const* d_bases, uint64_t co
     if (n_reads == 0) return;
     if (!d_cover) throw error(error_kind::argument, "cover pointer is null");
     device_guard guard(device);
-    dict_view const& d = rep->view;
     hipStream_t s = hipStream_t(stream);
-    const bool wide = d.k > 31;
-    if (total_bases == 0) {
-        HIP_CHECK(hipMemcpyAsync(&total_bases, d_read_offsets + n_reads, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (total_bases == 0) return;  // empty reads only: no k-mer
-    }
-    const run_sink sink{nullptr, d_cover, 0};
-    if (!wide && !d.canonical) launch_streaming_runs<1, false>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, RUNS_COVER);
-    else if (!wide && d.canonical) launch_streaming_runs<1, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, RUNS_COVER);
-    else if (wide && !d.canonical) launch_streaming_runs<2, false>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, RUNS_COVER);
-    else launch_streaming_runs<2, true>(rep, d, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, RUNS_COVER);
+    total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
+    if (total_bases == 0) return;  // empty reads only: no k-mer
+    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, run_sink{nullptr, d_cover, 0}, RUNS_COVER);
 }
 
 /* ---- per-k-mer results: the streaming query as a position-parallel pipeline -----------------------------------
@@ -1535,6 +1512,31 @@ static streaming_report read_back(uint64_t const* d_report, hipStream_t s) {
     return streaming_report::from_device(h);
 }
 
+namespace {
+
+/* Pieces of whole reads: piece i is the reads [cuts[i], cuts[i + 1]), with at most `piece_bases` bases (a single longer read is its own
+   piece) and at most `piece_reads` reads. */
+struct piece_cuts {
+    std::vector<uint64_t> cuts{0};
+    uint64_t max_bases = 0, max_reads = 0;  // of the largest piece
+    uint64_t count() const { return cuts.size() - 1; }
+};
+
+piece_cuts cut_pieces(uint64_t const* read_offsets, uint64_t n_reads, uint64_t piece_bases, uint64_t piece_reads) {
+    piece_cuts p;
+    for (uint64_t at = 0; at < n_reads;) {
+        uint64_t end = at + 1;
+        while (end < n_reads && end - at < piece_reads && read_offsets[end + 1] - read_offsets[at] <= piece_bases) ++end;
+        p.max_bases = std::max(p.max_bases, read_offsets[end] - read_offsets[at]);
+        p.max_reads = std::max(p.max_reads, end - at);
+        p.cuts.push_back(end);
+        at = end;
+    }
+    return p;
+}
+
+}  // namespace
+
 /* Host buffers: pieces of whole reads (at most ~64 MiB of bases each) go through one stream: H2D, the device pipeline
    above, D2H of the arrays the caller asked for. */
 streaming_report engine::streaming_lookup_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads,
@@ -1543,32 +1545,22 @@ streaming_report engine::streaming_lookup_host(char const* bases, uint64_t const
     if (!h_out.kmer_id) throw error(error_kind::argument, "kmer_id output pointer is null");
     const int device = resident_devices(*this)[0];
     device_guard guard(device);
-    const uint64_t piece_bases = uint64_t(64) << 20;
     device_buffers own;
     const own_stream call(replica(device));  // (drained and its lookup scratch handed back before `own` frees the buffers)
     hipStream_t s = call.s;
-    uint64_t max_bases = 0, max_reads = 0;
-    std::vector<uint64_t> cuts{0};
-    for (uint64_t at = 0; at < n_reads;) {
-        uint64_t end = at + 1;
-        while (end < n_reads && read_offsets[end + 1] - read_offsets[at] <= piece_bases) ++end;
-        max_bases = std::max(max_bases, read_offsets[end] - read_offsets[at]);
-        max_reads = std::max(max_reads, end - at);
-        cuts.push_back(end);
-        at = end;
-    }
-    char* d_bases = own.alloc<char>(max_bases + 8);
-    uint64_t* d_offsets = own.alloc<uint64_t>(max_reads + 1);
+    const piece_cuts pieces = cut_pieces(read_offsets, n_reads, uint64_t(64) << 20, ~uint64_t(0));
+    char* d_bases = own.alloc<char>(pieces.max_bases + 8);
+    uint64_t* d_offsets = own.alloc<uint64_t>(pieces.max_reads + 1);
     uint64_t* d_report = own.alloc<uint64_t>(6);
     HIP_CHECK(hipMemsetAsync(d_report, 0, 48, s));
     if (h_out.minimizer_found) throw error(error_kind::argument, "the streaming lookup does not report minimizer_found");
     result_view d_out{};
     for_each_field([&](int, auto* h, auto*& d, uint64_t) {
-        if (h) d = own.alloc<std::remove_reference_t<decltype(*d)>>(max_bases);
+        if (h) d = own.alloc<std::remove_reference_t<decltype(*d)>>(pieces.max_bases);
     }, h_out, d_out);
-    std::vector<uint64_t> rel(max_reads + 1);
-    for (size_t piece = 0; piece + 1 < cuts.size(); ++piece) {
-        const uint64_t first = cuts[piece], last = cuts[piece + 1];
+    std::vector<uint64_t> rel(pieces.max_reads + 1);
+    for (size_t piece = 0; piece < pieces.count(); ++piece) {
+        const uint64_t first = pieces.cuts[piece], last = pieces.cuts[piece + 1];
         const uint64_t b0 = read_offsets[first], nb = read_offsets[last] - b0;
         if (nb == 0) continue;
         for (uint64_t i = first; i <= last; ++i) rel[i - first] = read_offsets[i] - b0;
@@ -1588,42 +1580,56 @@ streaming_report engine::streaming_lookup_host(char const* bases, uint64_t const
     return read_back(d_report, s);
 }
 
+namespace {
+
 /* Host buffers: the reads are cut into pieces of at most ~32 MiB of bases; per replica up to eight lanes (the
    pooled pinned pipelines of the lookup host path, replica.hpp) pull pieces from a shared counter and run
    copy-in -> H2D -> kernel, accumulating the six counters in device memory; one read-back per lane. */
-constexpr uint64_t LONG_READ_BASES = uint64_t(1) << 16;
-
-streaming_report engine::streaming_query_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads) const {
-    return streaming_query_per_read_host(bases, read_offsets, n_reads, nullptr);
+piece_cuts cut_lane_pieces(uint64_t const* read_offsets, uint64_t n_reads) {
+    return cut_pieces(read_offsets, n_reads, uint64_t(32) << 20,
+                      test_hook_u64("stream_piece_reads", uint64_t(1) << 20, 1, uint64_t(1) << 20));  // (tests: seams between pieces inside a small batch)
 }
 
-/* The same pieces and lanes; with `rows` (n_reads x 6 words, host) a lane's device block also holds a row for every read of the largest
-   piece, and a piece's rows come back into the caller's array at the piece's first read. With `cover` (and no rows) a piece's k-mers
-   are marked in the bitmap that `cover` keeps on the lane's device: the lanes of a device share it, OR commutes. */
-streaming_report engine::streaming_query_per_read_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* rows,
-                                                       cover_bitmaps const* cover) const {
-    if (n_reads == 0) return {};
-    const std::vector<int> devs = resident_devices(*this);
-    const uint64_t G = devs.size();
-    /* pieces: [first read, last read) with a bounded number of bases (a single longer read is its own piece) */
-    const uint64_t piece_bases = uint64_t(32) << 20;
-    const uint64_t piece_reads = test_hook_u64("stream_piece_reads", uint64_t(1) << 20, 1, uint64_t(1) << 20);  // (tests: seams between pieces inside a small batch)
-    std::vector<uint64_t> cuts{0};
-    uint64_t max_bases = 0, max_reads = 0;
-    for (uint64_t at = 0; at < n_reads;) {
-        uint64_t end = at + 1;
-        while (end < n_reads && end - at < piece_reads && read_offsets[end + 1] - read_offsets[at] <= piece_bases) ++end;
-        max_bases = std::max(max_bases, read_offsets[end] - read_offsets[at]);
-        max_reads = std::max(max_reads, end - at);
-        cuts.push_back(end);
-        at = end;
-    }
-    const uint64_t num_pieces = cuts.size() - 1;
-    const uint64_t off_bytes = (max_reads + 1) * sizeof(uint64_t);
-    const uint64_t bases_at = (off_bytes + 255) & ~uint64_t(255);
-    const uint64_t report_at = (bases_at + max_bases + 255) & ~uint64_t(255);
-    const uint64_t rows_at = (report_at + 6 * sizeof(uint64_t) + 255) & ~uint64_t(255);
-    const uint64_t lane_bytes = rows ? rows_at + max_reads * 6 * sizeof(uint64_t) : report_at + 6 * sizeof(uint64_t);
+/* One lane walks one read: a read of megabases (a contig, a multiline FASTA record) would keep a single lane busy for minutes; a
+   piece that holds such a read goes through the position-parallel pipeline, which gives the same results. */
+bool holds_long_read(uint64_t const* offsets, uint64_t n_reads) {
+    constexpr uint64_t LONG_READ_BASES = uint64_t(1) << 16;
+    for (uint64_t i = 0; i < n_reads; ++i)
+        if (offsets[i + 1] - offsets[i] > LONG_READ_BASES) return true;
+    return false;
+}
+
+/* the six counters of one staged piece, added to d_report */
+void piece_totals(engine const& eng, int device, bool long_read, char const* d_bases, uint64_t const* d_offsets, uint64_t n_reads, uint64_t n_bases,
+                  uint64_t* d_report, hipStream_t s) {
+    if (long_read) eng.streaming_lookup_device(device, d_bases, d_offsets, n_reads, n_bases, result_view{}, d_report, s);
+    else eng.streaming_query_device(device, d_bases, d_offsets, n_reads, n_bases, d_report, s);
+}
+
+/* a piece as a lane hands it to the call's own work: uploaded, nothing launched yet */
+struct staged_piece {
+    uint64_t index, first, n, nb;  // which piece; its first read, its reads, its bases
+    bool long_read;
+    int device;
+    hipStream_t s;
+    char const* d_bases;
+    uint64_t const* d_offsets;  // n + 1, relative to the piece's first base
+    uint64_t* d_report;         // the lane's six counters
+    char *h_extra, *d_extra;    // the call's own `extra_bytes` of the lane's pinned and device block
+};
+
+/* The lanes of a host call over its pieces. A lane's block: the piece's offsets, its bases, the six counters, `extra_bytes` for the
+   caller, each 256-byte aligned. `body` launches what the call wants of the piece on p.s and synchronizes before it returns: the
+   pinned block is reused by the next piece. Returns the lanes' counters, summed. */
+template <class Body>  // void(staged_piece const&)
+streaming_report run_piece_lanes(engine const& eng, char const* bases, uint64_t const* read_offsets, piece_cuts const& pieces, uint64_t extra_bytes,
+                                 Body const& body) {
+    const std::vector<int> devs = resident_devices(eng);
+    const uint64_t G = devs.size(), num_pieces = pieces.count();
+    const uint64_t bases_at = ((pieces.max_reads + 1) * sizeof(uint64_t) + 255) & ~uint64_t(255);
+    const uint64_t report_at = (bases_at + pieces.max_bases + 255) & ~uint64_t(255);
+    const uint64_t extra_at = (report_at + 6 * sizeof(uint64_t) + 255) & ~uint64_t(255);
+    const uint64_t lane_bytes = extra_bytes ? extra_at + extra_bytes : report_at + 6 * sizeof(uint64_t);
 
     std::atomic<uint64_t> next{0};
     const uint64_t hw = std::max(1u, std::thread::hardware_concurrency());
@@ -1631,49 +1637,70 @@ streaming_report engine::streaming_query_per_read_host(char const* bases, uint64
     std::vector<int> lane_devs(lanes_per_device * G);
     for (uint64_t li = 0; li < lane_devs.size(); ++li) lane_devs[li] = devs[li % G];
     std::vector<streaming_report> partial(lane_devs.size());
-    run_lanes(*this, lane_devs, lane_bytes, [&](size_t li, int device, host_lane& lane) {
-        hipStream_t s = lane.stream;
+    run_lanes(eng, lane_devs, lane_bytes, [&](size_t li, int device, host_lane& lane) {
         char* hp = static_cast<char*>(lane.pinned);
         char* dp = static_cast<char*>(lane.device);
-        uint64_t* d_report = reinterpret_cast<uint64_t*>(dp + report_at);
-        HIP_CHECK(hipMemsetAsync(d_report, 0, 6 * sizeof(uint64_t), s));
+        staged_piece p{};
+        p.device = device;
+        p.s = lane.stream;
+        p.d_bases = dp + bases_at;
+        p.d_offsets = reinterpret_cast<uint64_t const*>(dp);
+        p.d_report = reinterpret_cast<uint64_t*>(dp + report_at);
+        p.h_extra = hp + extra_at;
+        p.d_extra = dp + extra_at;
+        HIP_CHECK(hipMemsetAsync(p.d_report, 0, 6 * sizeof(uint64_t), p.s));
         for (;;) {
-            const uint64_t piece = next.fetch_add(1);
-            if (piece >= num_pieces) break;
-            const uint64_t first = cuts[piece], last = cuts[piece + 1];
-            const uint64_t nb = read_offsets[last] - read_offsets[first];
+            p.index = next.fetch_add(1);
+            if (p.index >= num_pieces) break;
+            p.first = pieces.cuts[p.index];
+            p.n = pieces.cuts[p.index + 1] - p.first;
+            uint64_t const* offsets = read_offsets + p.first;
+            p.nb = offsets[p.n] - offsets[0];
             uint64_t* rel = reinterpret_cast<uint64_t*>(hp);
-            for (uint64_t i = first; i <= last; ++i) rel[i - first] = read_offsets[i] - read_offsets[first];
-            std::memcpy(hp + bases_at, bases + read_offsets[first], nb);
-            HIP_CHECK(hipMemcpyAsync(dp, hp, (last - first + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-            HIP_CHECK(hipMemcpyAsync(dp + bases_at, hp + bases_at, nb, hipMemcpyHostToDevice, s));
-            /* one lane walks one read: a read of megabases (a contig, a multiline FASTA record) would keep a single
-               lane busy for minutes; such pieces go through the position-parallel pipeline, which gives the same counters */
-            bool long_read = false;
-            for (uint64_t i = first; i < last && !long_read; ++i) long_read = read_offsets[i + 1] - read_offsets[i] > LONG_READ_BASES;
-            if (rows) {
-                uint64_t* d_rows = reinterpret_cast<uint64_t*>(dp + rows_at);
-                const uint64_t row_bytes = (last - first) * 6 * sizeof(uint64_t);
-                if (long_read || nb == 0) HIP_CHECK(hipMemsetAsync(d_rows, 0, row_bytes, s));  // (the classify pass adds to its rows; no bases: no kernel at all)
-                if (long_read) streaming_lookup_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, result_view{}, d_report, s, d_rows);
-                else if (nb) streaming_query_per_read_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, d_rows, d_report, s);
-                HIP_CHECK(hipMemcpyAsync(hp + rows_at, d_rows, row_bytes, hipMemcpyDeviceToHost, s));  // (through the lane's pinned block: the caller's array is pageable)
-            } else if (cover) {
-                if (long_read) streaming_lookup_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, result_view{}, d_report, s, nullptr, nullptr, cover->on(device));
-                else if (nb) streaming_cover_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, cover->on(device), d_report, s);
-            } else if (long_read) {
-                streaming_lookup_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, result_view{}, d_report, s);
-            } else {
-                streaming_query_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), last - first, nb, d_report, s);
-            }
-            HIP_CHECK(hipStreamSynchronize(s));  // the pinned block is reused by the next piece
-            if (rows) std::memcpy(rows + 6 * first, hp + rows_at, (last - first) * 6 * sizeof(uint64_t));
+            for (uint64_t i = 0; i <= p.n; ++i) rel[i] = offsets[i] - offsets[0];
+            std::memcpy(hp + bases_at, bases + offsets[0], p.nb);
+            HIP_CHECK(hipMemcpyAsync(dp, hp, (p.n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p.s));
+            HIP_CHECK(hipMemcpyAsync(dp + bases_at, hp + bases_at, p.nb, hipMemcpyHostToDevice, p.s));
+            p.long_read = holds_long_read(offsets, p.n);
+            body(p);
         }
-        partial[li] = read_back(d_report, s);
+        partial[li] = read_back(p.d_report, p.s);
     });
     streaming_report total;
-    for (auto const& p : partial) total += p;
+    for (auto const& part : partial) total += part;
     return total;
+}
+
+}  // namespace
+
+streaming_report engine::streaming_query_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads) const {
+    return streaming_query_per_read_host(bases, read_offsets, n_reads, nullptr);
+}
+
+/* With `rows` (n_reads x 6 words, host) a lane's device block also holds a row for every read of the largest piece, and a piece's rows
+   come back into the caller's array at the piece's first read. With `cover` (and no rows) a piece's k-mers are marked in the bitmap
+   that `cover` keeps on the lane's device: the lanes of a device share it, OR commutes. */
+streaming_report engine::streaming_query_per_read_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* rows,
+                                                       cover_bitmaps const* cover) const {
+    if (n_reads == 0) return {};
+    const piece_cuts pieces = cut_lane_pieces(read_offsets, n_reads);
+    const uint64_t row_bytes = 6 * sizeof(uint64_t);
+    return run_piece_lanes(*this, bases, read_offsets, pieces, rows ? pieces.max_reads * row_bytes : 0, [&](staged_piece const& p) {
+        if (rows) {
+            uint64_t* d_rows = reinterpret_cast<uint64_t*>(p.d_extra);
+            if (p.long_read || p.nb == 0) HIP_CHECK(hipMemsetAsync(d_rows, 0, p.n * row_bytes, p.s));  // (the classify pass adds to its rows; no bases: no kernel at all)
+            if (p.long_read) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, d_rows);
+            else if (p.nb) streaming_query_per_read_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, d_rows, p.d_report, p.s);
+            HIP_CHECK(hipMemcpyAsync(p.h_extra, d_rows, p.n * row_bytes, hipMemcpyDeviceToHost, p.s));  // (through the lane's pinned block: the caller's array is pageable)
+        } else if (cover) {
+            if (p.long_read) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, nullptr, nullptr, cover->on(p.device));
+            else if (p.nb) streaming_cover_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, cover->on(p.device), p.d_report, p.s);
+        } else {
+            piece_totals(*this, p.device, p.long_read, p.d_bases, p.d_offsets, p.n, p.nb, p.d_report, p.s);
+        }
+        HIP_CHECK(hipStreamSynchronize(p.s));
+        if (rows) std::memcpy(rows + 6 * p.first, p.h_extra, p.n * row_bytes);
+    });
 }
 
 /* ---- the cover bitmaps of a host call: one per resident replica, zeroed, in HBM for as long as the object lives (a call over host
@@ -1734,7 +1761,7 @@ streaming_report engine::streaming_cover_host(char const* bases, uint64_t const*
     return streaming_query_per_read_host(bases, read_offsets, n_reads, nullptr, &cover);
 }
 
-/* The runs of every read, host buffers (sshash_streaming_runs): the pieces and lanes of streaming_query_per_read_host. A piece's
+/* The runs of every read, host buffers (sshash_streaming_runs): pieces and lanes as above (run_piece_lanes). A piece's
    run_offsets are local to the piece and its record count is known only after its counting pass, so a lane counts, reads the count
    back, sizes the piece's device records from it and writes them; the pieces' records wait on the host until every piece's count is
    known -- only then is a piece's place in the caller's array --, and are stitched in piece order, clipped at `runs_capacity`. */
@@ -1747,91 +1774,43 @@ streaming_report engine::streaming_runs_host(char const* bases, uint64_t const* 
     }
     for (uint64_t r = 0; r < n_reads; ++r)
         if ((read_offsets[r + 1] - read_offsets[r]) >> 31) throw error(error_kind::argument, "a read of 2^31 bases or more: a run record could not hold its positions");
-    const std::vector<int> devs = resident_devices(*this);
-    const uint64_t G = devs.size();
-    const uint64_t piece_bases = uint64_t(32) << 20;
-    const uint64_t piece_reads = test_hook_u64("stream_piece_reads", uint64_t(1) << 20, 1, uint64_t(1) << 20);
-    std::vector<uint64_t> cuts{0};
-    uint64_t max_bases = 0, max_reads = 0;
-    for (uint64_t at = 0; at < n_reads;) {
-        uint64_t end = at + 1;
-        while (end < n_reads && end - at < piece_reads && read_offsets[end + 1] - read_offsets[at] <= piece_bases) ++end;
-        max_bases = std::max(max_bases, read_offsets[end] - read_offsets[at]);
-        max_reads = std::max(max_reads, end - at);
-        cuts.push_back(end);
-        at = end;
-    }
-    const uint64_t num_pieces = cuts.size() - 1;
-    const uint64_t off_bytes = (max_reads + 1) * sizeof(uint64_t);
-    const uint64_t bases_at = (off_bytes + 255) & ~uint64_t(255);
-    const uint64_t report_at = (bases_at + max_bases + 255) & ~uint64_t(255);
-    const uint64_t counts_at = (report_at + 6 * sizeof(uint64_t) + 255) & ~uint64_t(255);
-    const uint64_t lane_bytes = counts_at + off_bytes;
-
-    std::atomic<uint64_t> next{0};
-    const uint64_t hw = std::max(1u, std::thread::hardware_concurrency());
-    const uint64_t lanes_per_device = std::min<uint64_t>({(num_pieces + G - 1) / G, 8, std::max<uint64_t>(1, hw / G)});
-    std::vector<int> lane_devs(lanes_per_device * G);
-    for (uint64_t li = 0; li < lane_devs.size(); ++li) lane_devs[li] = devs[li % G];
-    std::vector<streaming_report> partial(lane_devs.size());
+    const piece_cuts pieces = cut_lane_pieces(read_offsets, n_reads);
+    const uint64_t num_pieces = pieces.count();
     std::vector<std::vector<uint64_t>> piece_records(num_pieces);  // (four words a record)
     std::vector<uint64_t> piece_total(num_pieces, 0);
-    run_lanes(*this, lane_devs, lane_bytes, [&](size_t li, int device, host_lane& lane) {
-        hipStream_t s = lane.stream;
-        device_replica const* rep = replica(device);
-        char* hp = static_cast<char*>(lane.pinned);
-        char* dp = static_cast<char*>(lane.device);
-        uint64_t* d_report = reinterpret_cast<uint64_t*>(dp + report_at);
-        uint64_t* d_counts = reinterpret_cast<uint64_t*>(dp + counts_at);
-        uint64_t const* d_offsets = reinterpret_cast<uint64_t const*>(dp);
-        HIP_CHECK(hipMemsetAsync(d_report, 0, 6 * sizeof(uint64_t), s));
-        for (;;) {
-            const uint64_t piece = next.fetch_add(1);
-            if (piece >= num_pieces) break;
-            const uint64_t first = cuts[piece], last = cuts[piece + 1], n = last - first;
-            const uint64_t nb = read_offsets[last] - read_offsets[first];
-            uint64_t* rel = reinterpret_cast<uint64_t*>(hp);
-            for (uint64_t i = first; i <= last; ++i) rel[i - first] = read_offsets[i] - read_offsets[first];
-            std::memcpy(hp + bases_at, bases + read_offsets[first], nb);
-            HIP_CHECK(hipMemcpyAsync(dp, hp, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-            HIP_CHECK(hipMemcpyAsync(dp + bases_at, hp + bases_at, nb, hipMemcpyHostToDevice, s));
-            bool long_read = false;  // (as streaming_query_per_read_host)
-            for (uint64_t i = first; i < last && !long_read; ++i) long_read = read_offsets[i + 1] - read_offsets[i] > LONG_READ_BASES;
-            const run_sink counting{d_counts, nullptr, 0};
-            if (nb == 0) HIP_CHECK(hipMemsetAsync(d_counts, 0, (n + 1) * sizeof(uint64_t), s));
-            else if (long_read) streaming_lookup_device(device, dp + bases_at, d_offsets, n, nb, result_view{}, d_report, s, nullptr, &counting);
-            else streaming_runs_device(device, dp + bases_at, d_offsets, n, nb, d_counts, nullptr, 0, d_report, s);
-            uint64_t const* counts = reinterpret_cast<uint64_t const*>(hp + counts_at);
-            HIP_CHECK(hipMemcpyAsync(hp + counts_at, d_counts, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            const uint64_t total = counts[n];
-            piece_total[piece] = total;
-            for (uint64_t i = 1; i <= n; ++i) run_offsets[first + i] = counts[i];  // (local to the piece until the pieces are stitched)
-            if (runs_capacity && total) {
-                std::vector<uint64_t>& mine = piece_records[piece];
-                mine.resize(total * (RECORD_BYTES / 8));
-                device_buffers records(rep, s);
-                void* d_records = records.alloc<uint64_t>(total * (RECORD_BYTES / 8));
-                const run_sink writing{d_counts, d_records, total};
-                if (long_read) streaming_lookup_device(device, dp + bases_at, d_offsets, n, nb, result_view{}, nullptr, s, nullptr, &writing);
-                else streaming_runs_passes(device, dp + bases_at, d_offsets, n, nb, writing, nullptr, s, false, true);
-                HIP_CHECK(hipMemcpyAsync(mine.data(), d_records, total * RECORD_BYTES, hipMemcpyDeviceToHost, s));
-                HIP_CHECK(hipStreamSynchronize(s));
-            }
+    const streaming_report report = run_piece_lanes(*this, bases, read_offsets, pieces, (pieces.max_reads + 1) * sizeof(uint64_t), [&](staged_piece const& p) {
+        uint64_t* d_counts = reinterpret_cast<uint64_t*>(p.d_extra);
+        uint64_t const* counts = reinterpret_cast<uint64_t const*>(p.h_extra);
+        const run_sink counting{d_counts, nullptr, 0};
+        if (p.nb == 0) HIP_CHECK(hipMemsetAsync(d_counts, 0, (p.n + 1) * sizeof(uint64_t), p.s));
+        else if (p.long_read) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, nullptr, &counting);
+        else streaming_runs_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, d_counts, nullptr, 0, p.d_report, p.s);
+        HIP_CHECK(hipMemcpyAsync(p.h_extra, d_counts, (p.n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, p.s));
+        HIP_CHECK(hipStreamSynchronize(p.s));
+        const uint64_t total = counts[p.n];
+        piece_total[p.index] = total;
+        for (uint64_t i = 1; i <= p.n; ++i) run_offsets[p.first + i] = counts[i];  // (local to the piece until the pieces are stitched)
+        if (runs_capacity && total) {
+            std::vector<uint64_t>& mine = piece_records[p.index];
+            mine.resize(total * (RECORD_BYTES / 8));
+            device_buffers records(replica(p.device), p.s);
+            void* d_records = records.alloc<uint64_t>(total * (RECORD_BYTES / 8));
+            const run_sink writing{d_counts, d_records, total};
+            if (p.long_read) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, nullptr, p.s, nullptr, &writing);
+            else streaming_runs_passes(*this, p.device, p.d_bases, p.d_offsets, p.n, p.nb, writing, nullptr, p.s, false, true);
+            HIP_CHECK(hipMemcpyAsync(mine.data(), d_records, total * RECORD_BYTES, hipMemcpyDeviceToHost, p.s));
+            HIP_CHECK(hipStreamSynchronize(p.s));
         }
-        partial[li] = read_back(d_report, s);
     });
     run_offsets[0] = 0;
     uint64_t base = 0;
     for (uint64_t piece = 0; piece < num_pieces; ++piece) {
-        for (uint64_t r = cuts[piece] + 1; r <= cuts[piece + 1]; ++r) run_offsets[r] += base;
+        for (uint64_t r = pieces.cuts[piece] + 1; r <= pieces.cuts[piece + 1]; ++r) run_offsets[r] += base;
         if (base < runs_capacity && piece_total[piece])
             std::memcpy(static_cast<char*>(runs) + base * RECORD_BYTES, piece_records[piece].data(), std::min(piece_total[piece], runs_capacity - base) * RECORD_BYTES);
         base += piece_total[piece];
     }
-    streaming_report total;
-    for (auto const& p : partial) total += p;
-    return total;
+    return report;
 }
 
 /* The file query of an uncompressed FASTQ (engine.hpp). One reader thread feeding batches through streaming_query_host splits
@@ -1886,10 +1865,7 @@ bool engine::streaming_query_fastq_pieces(std::string const& filename, streaming
             if (got.num_reads == 0) continue;
             HIP_CHECK(hipMemcpyAsync(dp, hp, (got.num_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
             HIP_CHECK(hipMemcpyAsync(dp + bases_at, hp + bases_at, got.num_bases, hipMemcpyHostToDevice, s));
-            bool long_read = false;  // (as streaming_query_host: a read of megabases must not sit on one lane of a wave)
-            for (uint64_t i = 0; i < got.num_reads && !long_read; ++i) long_read = offsets[i + 1] - offsets[i] > LONG_READ_BASES;
-            if (long_read) streaming_lookup_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), got.num_reads, got.num_bases, result_view{}, d_report, s);
-            else streaming_query_device(device, dp + bases_at, reinterpret_cast<uint64_t const*>(dp), got.num_reads, got.num_bases, d_report, s);
+            piece_totals(*this, device, holds_long_read(offsets, got.num_reads), dp + bases_at, reinterpret_cast<uint64_t const*>(dp), got.num_reads, got.num_bases, d_report, s);
             HIP_CHECK(hipStreamSynchronize(s));  // the pinned block is parsed into again
         }
         partial[li] = read_back(d_report, s);
