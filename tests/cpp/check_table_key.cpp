@@ -11,6 +11,15 @@
 
 using namespace sshash_amd;
 
+/* an even-length m-mer that is its own reverse complement, h followed by revcomp(h) (the complement of code c is c ^ 2): it reads the
+   same on both strands, so a k-mer in which it wins the election has no key. Random k-mers hold none at m = 30. */
+static void self_complementary(uint8_t* out, uint32_t m, std::mt19937_64& rng) {
+    for (uint32_t i = 0; i < m / 2; ++i) {
+        out[i] = uint8_t(rng() % 4);
+        out[m - 1 - i] = out[i] ^ 2;
+    }
+}
+
 template <int W>
 static int check(uint32_t k, uint32_t m, uint64_t trials, std::mt19937_64& rng, uint64_t& ties) {
     const uint64_t mask = low_mask(2 * m);
@@ -19,6 +28,15 @@ static int check(uint32_t k, uint32_t m, uint64_t trials, std::mt19937_64& rng, 
         for (int j = 0; j < W; ++j) x.w[j] = rng();
         if (t % 7 == 0) x.w[0] &= 0x3333333333333333ULL;  // low-complexity k-mers: repeated m-mers inside one window
         x = kmer_take_chars<W>(x, k);
+        if (m % 2 == 0 && t % 5 == 1) {  // even m: a self-complementary m-mer somewhere in the k-mer
+            uint8_t p[32];
+            self_complementary(p, m, rng);
+            const uint32_t at = uint32_t(rng() % (k - m + 1));
+            for (uint32_t i = 0; i < m; ++i) {
+                uint64_t& w = x.w[(at + i) / 32];
+                w = (w & ~(uint64_t(3) << (2 * ((at + i) % 32)))) | (uint64_t(p[i]) << (2 * ((at + i) % 32)));
+            }
+        }
         const kmer_w<W> y = kmer_revcomp<W>(x, k);
         const sk_key_t a = sk_key<W>(x, y, k, m), b = sk_key<W>(y, x, k, m);
         if (a.tie != b.tie) return printf("tie flag differs between strands (k=%u m=%u)\n", k, m), 1;
@@ -63,6 +81,7 @@ static int check_persists(uint32_t k, uint32_t m, uint64_t reads, std::mt19937_6
         const uint32_t alphabet = t % 5 == 0 ? 2 : 4;
         std::vector<uint8_t> read(len + 80);
         for (uint32_t j = 0; j < read.size(); ++j) read[j] = uint8_t(t % 11 == 0 && (j / 40) % 2 ? 0 : rng() % alphabet);
+        if (m % 2 == 0 && t % 3 == 1) self_complementary(&read[rng() % (len - m + 1)], m, rng);  // even m: followers that tie
         auto bases32 = [&](uint32_t from) {  // (what read_bases32 of streaming.hip hands over: whatever lies there, also behind the read's end)
             uint64_t w = 0;
             for (uint32_t i = 0; i < 32; ++i) w |= uint64_t(from + i < read.size() ? read[from + i] : 0) << (2 * i);
@@ -101,7 +120,8 @@ static int check_persists(uint32_t k, uint32_t m, uint64_t reads, std::mt19937_6
 int main() {
     std::mt19937_64 rng(12345);
     uint64_t ties = 0, checked = 0;
-    const uint32_t cases[][2] = {{31, 21}, {31, 13}, {15, 7}, {21, 21}, {31, 1}, {63, 25}, {63, 31}, {47, 20}, {33, 5}};
+    const uint32_t cases[][2] = {{31, 21}, {31, 13}, {15, 7}, {21, 21}, {31, 1}, {63, 25}, {63, 31}, {47, 20}, {33, 5},
+                                 {15, 4}, {31, 6}, {31, 12}, {31, 30}, {33, 12}, {35, 30}};  // even m
     for (auto const& c : cases) {
         const uint64_t trials = 200000;
         const uint64_t before = ties;
