@@ -368,6 +368,52 @@ sshash_status sshash_cover_string_counts_device(const sshash_dict* d, int device
                                                 uint64_t* total, void* hip_stream);
 sshash_status sshash_cover_string_counts(const sshash_dict* d, const uint64_t* cover, uint64_t* counts, uint64_t* total);
 
+/* ---- HOW OFTEN a read set holds each k-mer of the dictionary: k-mer counting restricted to the dictionary (no reference counterpart as a
+ *      call; what `ab:Z:` abundances of a weighted build are made from). A DEPTH ARRAY holds num_kmers words of uint32_t, word i for
+ *      k-mer id i. After a call depth[i] has grown by the number of places in the reads where sshash_streaming_lookup over the same reads
+ *      returns kmer_id == i: every strand counts, every occurrence counts. All arithmetic is modulo 2^32: a result is exact when the true
+ *      count is below 2^32, whatever the intermediate values were; a k-mer held 2^32 times or more WRAPS (nothing saturates).
+ *      The device side works on a DELTA ARRAY of the same size and type, a difference array: a maximal run of consecutive ids [lo, hi)
+ *      adds 1 to delta[lo] and, if hi < num_kmers, subtracts 1 from delta[hi], whatever its length; depth[i] = delta[0] + .. + delta[i]
+ *      (sshash_depth_finish_device). Deltas of many calls add up -- one array takes a sample of many batches or files --, and the
+ *      order of the reads, of the batches and of the calls does not matter.
+ *      Preconditions and status codes as the cover calls: a null dictionary, or null bases / read_offsets / output with num_reads > 0,
+ *      is SSHASH_ERR_ARGUMENT before anything runs; num_reads == 0 succeeds and touches nothing; a dictionary that is not resident is
+ *      SSHASH_ERR_NO_DEVICE. A minimizer shard (num_shards > 1) counts the k-mers it owns and no others, under the ids of the whole
+ *      index, and the shards' depth arrays added together are the depth array of the whole index. For that a shard's host and file
+ *      calls look every k-mer up on its own (the pipeline of sshash_streaming_lookup, whatever the reads' lengths): the run kernel
+ *      measures a run along the string, which a shard holds whole, so it would follow a k-mer of its own through k-mers of other
+ *      shards and those would be counted once per shard. sshash_streaming_depth_device, which is that kernel, is SSHASH_ERR_ARGUMENT
+ *      on a minimizer shard. ---- */
+/* device buffers, asynchronous on hip_stream. deltas: num_kmers uint32, ACCUMULATED into (the caller zeroes it before the first call);
+ * nothing at or beyond deltas + num_kmers is touched. report and total_bases as for sshash_streaming_cover_device. Always the run kernel,
+ * in ONE launch: where sshash_streaming_cover_device ORs a run's id range into the bitmap this call issues one or two 32-bit atomic
+ * adds; no scratch beyond that of sshash_streaming_query_device. */
+sshash_status sshash_streaming_depth_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
+                                            uint64_t num_reads, uint64_t total_bases, uint32_t* deltas, uint64_t* report, void* hip_stream);
+/* deltas -> depths: depth[i] = deltas[0] + .. + deltas[i] modulo 2^32 over the num_kmers words (device pointers, asynchronous on
+ * hip_stream; three launches, none of which waits for another workgroup). depth == deltas (in place) is allowed; any other overlap is the
+ * caller's error. The scratch for the tile sums (4 bytes per 4096 k-mers) is sized, allocated and freed by the call itself, stream-ordered
+ * on hip_stream, out of the replica's own memory pool. NULL dictionary, deltas or depth: SSHASH_ERR_ARGUMENT. */
+sshash_status sshash_depth_finish_device(const sshash_dict* d, int device, const uint32_t* deltas, uint32_t* depth, void* hip_stream);
+/* host buffers, sharded over all resident replicas like sshash_streaming_cover: every replica keeps one delta array in HBM (4 bytes per
+ * k-mer, zeroed, for the length of the call), finishes it on the device, and the results are ADDED into `depth` (host, num_kmers uint32;
+ * the caller zeroes it for a fresh count). A piece that holds a read above 2^16 bases goes through the position-parallel pipeline of
+ * sshash_streaming_lookup and is marked from its per-k-mer ids, which gives the same depths. report may be NULL. */
+sshash_status sshash_streaming_depth(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
+                                     uint32_t* depth, sshash_streaming_report* report);
+/* a query file, as sshash_streaming_cover_from_file (the sequential reader, bounded host memory): every replica keeps ONE delta array in
+ * HBM for the whole file; they are finished and added into `depth` (host) once, at the end. report may be NULL. */
+sshash_status sshash_streaming_depth_from_file(const sshash_dict* d, const char* filename, int multiline, uint32_t* depth,
+                                               sshash_streaming_report* report);
+/* Depth per string: sums[s] = the 64-bit sum of `depth` over the k-mer ids of string s (the id range of sshash_cover_string_counts);
+ * sums: num_strings uint64, OVERWRITTEN; total (may be NULL): one uint64, overwritten with their sum. The mean depth of string s is
+ * sums[s] / sshash_string_size(s). NULL dictionary, depth or sums: SSHASH_ERR_ARGUMENT. The device variant (device pointers,
+ * asynchronous on hip_stream) goes over the ids, one lane each; the host variant is plain CPU code and needs no GPU. */
+sshash_status sshash_depth_string_sums_device(const sshash_dict* d, int device, const uint32_t* depth, uint64_t* sums, uint64_t* total,
+                                              void* hip_stream);
+sshash_status sshash_depth_string_sums(const sshash_dict* d, const uint32_t* depth, uint64_t* sums, uint64_t* total);
+
 /* ---- streaming_query<Dict,canonical>::lookup for EVERY k-mer of every read (include/streaming_query.hpp:56-109),
  *      batched: what the reference returns k-mer by k-mer while it streams a read. Every non-NULL array of `out` has one
  *      entry per BASE of `bases` (total_bases = read_offsets[num_reads] entries): entry read_offsets[r] + j is the result

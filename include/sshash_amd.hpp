@@ -347,6 +347,47 @@ public:
         check(sshash_cover_string_counts_device(m_h, device, d_cover, d_counts, d_total, hip_stream));
     }
 
+    /* HOW OFTEN the reads hold each k-mer of the dictionary (sshash_streaming_depth; the definitions are in include/sshash_amd.h): depth[i]
+       grows by the occurrences of k-mer id i in the reads, either strand, modulo 2^32. `depth` is sized to num_kmers() if it is not (new
+       words zero) and added into. Returns the batch's report. */
+    streaming_query_report streaming_depth(char const* bases, uint64_t const* read_offsets, uint64_t num_reads, std::vector<uint32_t>& depth) const {
+        depth.resize(num_kmers(), 0);
+        sshash_streaming_report s;
+        check(sshash_streaming_depth(m_h, bases, read_offsets, num_reads, depth.data(), &s));
+        return to_report(s);
+    }
+    /* device buffers, asynchronous on hip_stream (sshash_streaming_depth_device): d_deltas -- num_kmers() uint32, a difference array -- is
+       added into, d_report -- may be null -- six counters (accumulated into); depth_finish_device turns deltas into depths (d_depth may
+       be d_deltas) */
+    void streaming_depth_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t num_reads, uint64_t total_bases,
+                                uint32_t* d_deltas, uint64_t* d_report, void* hip_stream) const {
+        check(sshash_streaming_depth_device(m_h, device, d_bases, d_read_offsets, num_reads, total_bases, d_deltas, d_report, hip_stream));
+    }
+    void depth_finish_device(int device, uint32_t const* d_deltas, uint32_t* d_depth, void* hip_stream) const {
+        check(sshash_depth_finish_device(m_h, device, d_deltas, d_depth, hip_stream));
+    }
+    /* a query file into one depth array (sshash_streaming_depth_from_file) */
+    streaming_query_report streaming_depth_from_file(std::string const& filename, bool multiline, std::vector<uint32_t>& depth) const {
+        depth.resize(num_kmers(), 0);
+        sshash_streaming_report s;
+        check(sshash_streaming_depth_from_file(m_h, filename.c_str(), multiline, depth.data(), &s));
+        return to_report(s);
+    }
+    /* the sum of depth over every string's ids, and over all (sshash_depth_string_sums: CPU, no GPU needed; _device: device buffers,
+       asynchronous); the mean depth of string s is sums[s] / string_size(s) */
+    uint64_t depth_string_sums(std::vector<uint32_t> const& depth, std::vector<uint64_t>& sums) const {
+        if (depth.size() < num_kmers()) throw std::invalid_argument("depth has fewer than num_kmers() words");
+        sums.assign(num_strings(), 0);
+        uint64_t total = 0;
+        std::vector<uint32_t> no_depth(1);
+        std::vector<uint64_t> none(1);
+        check(sshash_depth_string_sums(m_h, depth.empty() ? no_depth.data() : depth.data(), sums.empty() ? none.data() : sums.data(), &total));
+        return total;
+    }
+    void depth_string_sums_device(int device, uint32_t const* d_depth, uint64_t* d_sums, uint64_t* d_total, void* hip_stream) const {
+        check(sshash_depth_string_sums_device(m_h, device, d_depth, d_sums, d_total, hip_stream));
+    }
+
     /* a query file, one row per record, handed over in file order: fn(first_read, rows, n) for one batch after the other; a
        non-zero return stops the query (std::runtime_error). Fn: int(uint64_t, streaming_query_report const*, uint64_t). */
     template <typename Fn>

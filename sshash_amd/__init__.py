@@ -24,6 +24,7 @@ from ._binding import (  # noqa: F401
     expand_runs,
     ids_to_cover,
     library_path,
+    write_weighted_fasta,
 )
 
 __all__ = [
@@ -40,4 +41,5 @@ __all__ = [
     "expand_runs",
     "ids_to_cover",
     "library_path",
+    "write_weighted_fasta",
 ]

@@ -199,6 +199,12 @@ def _load() -> C.CDLL:
         "sshash_streaming_cover_from_file": (C.c_int, [P, C.c_char_p, C.c_int, P, C.POINTER(_Report)]),
         "sshash_cover_string_counts_device": (C.c_int, [P, C.c_int, P, P, P, P]),
         "sshash_cover_string_counts": (C.c_int, [P, P, P, C.POINTER(C.c_uint64)]),
+        "sshash_streaming_depth_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, P, P]),
+        "sshash_depth_finish_device": (C.c_int, [P, C.c_int, P, P, P]),
+        "sshash_streaming_depth": (C.c_int, [P, P, P, C.c_uint64, P, C.POINTER(_Report)]),
+        "sshash_streaming_depth_from_file": (C.c_int, [P, C.c_char_p, C.c_int, P, C.POINTER(_Report)]),
+        "sshash_depth_string_sums_device": (C.c_int, [P, C.c_int, P, P, P, P]),
+        "sshash_depth_string_sums": (C.c_int, [P, P, P, C.POINTER(C.c_uint64)]),
         "sshash_route_packed_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P, P]),
         "sshash_route_bucket_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, C.c_int, P, P, P, P]),
         "sshash_route_bucket_by_key_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P, P, P]),
@@ -227,6 +233,8 @@ C_ABI_SYMBOLS = (
     "sshash_streaming_runs sshash_streaming_runs_device "
     "sshash_cover_words sshash_streaming_cover sshash_streaming_cover_device sshash_streaming_cover_from_file "
     "sshash_cover_string_counts sshash_cover_string_counts_device "
+    "sshash_streaming_depth sshash_streaming_depth_device sshash_depth_finish_device sshash_streaming_depth_from_file "
+    "sshash_depth_string_sums sshash_depth_string_sums_device "
     "sshash_streaming_lookup sshash_streaming_lookup_device sshash_sharded_lookup_device sshash_sharded_lookup_rccl "
     "sshash_route_packed_device sshash_route_bucket_device sshash_route_bucket_by_key_device sshash_route_combine_device "
     "sshash_iterate_packed sshash_iterate_packed_device sshash_check_device"
@@ -814,6 +822,62 @@ class Dictionary:
         _check(_load().sshash_cover_string_counts_device(self._h, int(device), C.c_void_p(d_cover), C.c_void_p(d_counts), C.c_void_p(d_total),
                                                          C.c_void_p(stream)))
 
+    # ---- streaming depth: how often a read set holds each k-mer of the dictionary ---------------------
+    def _depth_array(self, depth) -> np.ndarray:
+        n = self.num_kmers()
+        if depth is None:
+            return np.zeros(n, dtype=np.uint32)
+        if not (isinstance(depth, np.ndarray) and depth.dtype == np.uint32 and depth.ndim == 1 and depth.size == n and depth.flags.c_contiguous):
+            raise ValueError(f"depth: a contiguous uint32 array of num_kmers() = {n} words")
+        return depth
+
+    def streaming_depth(self, reads: Sequence[Union[str, bytes]], depth: Optional[np.ndarray] = None):
+        """HOW OFTEN the reads hold each k-mer of the dictionary -> (depth, StreamingQueryReport): depth[i] grows by the number of places
+        where streaming_lookup over the same reads returns kmer_id == i (either strand, every occurrence; modulo 2^32, nothing
+        saturates). `depth` (None: a zeroed one), num_kmers() uint32, is added into, in place, and returned."""
+        chunks = [s.encode("ascii", "replace") if isinstance(s, str) else bytes(s) for s in reads]
+        offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
+        if chunks:
+            offsets[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
+        bases = np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8)
+        depth = self._depth_array(depth)
+        r = _Report()
+        _check(_load().sshash_streaming_depth(self._h, bases.ctypes.data, offsets.ctypes.data, len(chunks), depth.ctypes.data, C.byref(r)))
+        return depth, self._report(r)
+
+    def streaming_depth_device(self, device: int, d_bases: int, d_read_offsets: int, num_reads: int, d_deltas: int, d_report: int = 0,
+                               stream: int = 0, total_bases: int = 0) -> None:
+        """Device buffers: d_deltas (num_kmers() uint32, a difference array: +1 where a run of ids begins, -1 behind it) is added into,
+        d_report (0: none) six counters (accumulated into). `total_bases` as for streaming_query_device. depth_finish_device() turns the
+        deltas into depths."""
+        _check(_load().sshash_streaming_depth_device(self._h, int(device), C.c_void_p(d_bases), C.c_void_p(d_read_offsets), int(num_reads),
+                                                     int(total_bases), C.c_void_p(d_deltas), C.c_void_p(d_report), C.c_void_p(stream)))
+
+    def depth_finish_device(self, device: int, d_deltas: int, d_depth: int, stream: int = 0) -> None:
+        """Device buffers: d_depth[i] = d_deltas[0] + .. + d_deltas[i] modulo 2^32 over num_kmers() uint32; d_depth may be d_deltas."""
+        _check(_load().sshash_depth_finish_device(self._h, int(device), C.c_void_p(d_deltas), C.c_void_p(d_depth), C.c_void_p(stream)))
+
+    def streaming_depth_from_file(self, filename: str, depth: Optional[np.ndarray] = None, multiline: bool = False):
+        """A query file into one depth array -> (depth, StreamingQueryReport); `depth` as for streaming_depth."""
+        depth = self._depth_array(depth)
+        r = _Report()
+        _check(_load().sshash_streaming_depth_from_file(self._h, os.fsencode(filename), 1 if multiline else 0, depth.ctypes.data, C.byref(r)))
+        return depth, self._report(r)
+
+    def depth_string_sums(self, depth: np.ndarray):
+        """-> (sums, total): the sum of depth over the ids of every string (num_strings uint64) and over all; the mean depth of string s
+        is sums[s] / string_size(s). CPU, no GPU needed."""
+        depth = self._depth_array(depth)
+        sums = np.zeros(max(self.num_strings(), 1), dtype=np.uint64)
+        total = C.c_uint64(0)
+        _check(_load().sshash_depth_string_sums(self._h, depth.ctypes.data if depth.size else sums.ctypes.data, sums.ctypes.data, C.byref(total)))
+        return sums[:self.num_strings()], int(total.value)
+
+    def depth_string_sums_device(self, device: int, d_depth: int, d_sums: int, d_total: int = 0, stream: int = 0) -> None:
+        """Device buffers: d_sums (num_strings uint64) and d_total (0: none; one uint64) are overwritten."""
+        _check(_load().sshash_depth_string_sums_device(self._h, int(device), C.c_void_p(d_depth), C.c_void_p(d_sums), C.c_void_p(d_total),
+                                                       C.c_void_p(stream)))
+
     def streaming_lookup(self, reads: Sequence[Union[str, bytes]], full: bool = False):
         """streaming_query::lookup for every k-mer of every read (reference include/streaming_query.hpp:56-109), batched.
         -> (list of LookupResult, one per read, len(read) - k + 1 entries each; StreamingQueryReport)."""
@@ -888,6 +952,46 @@ def expand_runs(run_offsets, runs, read_lengths, k: int):
             ori[at:at + count] = -1 if backward else 1
         out.append(LookupResult(kmer_id=ids, kmer_id_in_string=in_string, kmer_orientation=ori, string_id=sid))
     return out
+
+
+def write_weighted_fasta(d: "Dictionary", depth, path: str) -> None:
+    """The dictionary's strings in id order with `depth` (num_kmers() counts, one per k-mer id) as their abundances, in the format a
+    weighted build reads: '>s LN:i:len ab:Z:c0 c1 ...' and the string on the next line (gzip when `path` ends in .gz).
+    Dictionary.build(path, k, m, weighted=True) over the file gives a dictionary with the same ids whose weight(i) is depth[i];
+    zeros are written as they are. CPU only: the strings come from the k-mer iterator, a few thousand strings at a time."""
+    import gzip
+
+    depth = np.asarray(depth)
+    n_kmers, n_strings, k = d.num_kmers(), d.num_strings(), d.k()
+    if depth.ndim != 1 or depth.size != n_kmers or depth.dtype.kind not in "ui":
+        raise ValueError(f"depth: {n_kmers} integer counts, one per k-mer id")
+    if depth.dtype.kind == "i" and depth.size and int(depth.min()) < 0:
+        raise ValueError("depth: counts are not negative")
+    letters = np.frombuffer(b"ACTG", dtype=np.uint8)  # 2-bit code -> character
+    W = d.words_per_kmer()
+    last_word, last_shift = (k - 1) // 32, np.uint64(2 * ((k - 1) % 32))
+    begin, end = d.string_offsets(np.arange(n_strings, dtype=np.uint64))
+    sid = np.arange(n_strings, dtype=np.uint64)
+    first_id = (begin - sid * np.uint64(k - 1)).astype(np.int64)  # ids of string s: [first_id[s], first_id[s] + size[s])
+    size = (end - begin).astype(np.int64) - (k - 1)
+    with (gzip.open(path, "wt") if str(path).endswith(".gz") else open(path, "w")) as f:
+        s0 = 0
+        while s0 < n_strings:
+            s1 = s0 + 1
+            while s1 < n_strings and s1 - s0 < 4096 and int(first_id[s1]) - int(first_id[s0]) < (1 << 22):
+                s1 += 1
+            lo, hi = int(first_id[s0]), int(first_id[s1 - 1] + size[s1 - 1])
+            packed = d.kmers(lo, hi).reshape(-1, W)
+            last = letters[((packed[:, last_word] >> last_shift) & np.uint64(3)).astype(np.uint8)]  # the last character of every k-mer
+            for s in range(s0, s1):
+                a, n = int(first_id[s]) - lo, int(size[s])
+                head = np.empty(k - 1, dtype=np.uint8)  # the first k-mer's characters but its last
+                for i in range(k - 1):
+                    head[i] = letters[int((int(packed[a, i // 32]) >> (2 * (i % 32))) & 3)]
+                text = head.tobytes() + last[a:a + n].tobytes()
+                counts = " ".join(map(str, depth[lo + a:lo + a + n].tolist()))
+                f.write(f">{s} LN:i:{len(text)} ab:Z:{counts}\n{text.decode('ascii')}\n")
+            s0 = s1
 
 
 def cover_to_ids(cover) -> np.ndarray:

@@ -637,6 +637,73 @@ sshash_status sshash_cover_string_counts(const sshash_dict* d, const uint64_t* c
     });
 }
 
+sshash_status sshash_streaming_depth_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
+                                            uint64_t num_reads, uint64_t total_bases, uint32_t* deltas, uint64_t* report, void* hip_stream) {
+    if (!d || (num_reads && (!bases || !read_offsets || !deltas))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] { d->eng->streaming_depth_device(device, bases, read_offsets, num_reads, total_bases, deltas, report, hip_stream); });
+}
+
+sshash_status sshash_depth_finish_device(const sshash_dict* d, int device, const uint32_t* deltas, uint32_t* depth, void* hip_stream) {
+    if (!d || !deltas || !depth) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] { d->eng->depth_finish_device(device, deltas, depth, hip_stream); });
+}
+
+sshash_status sshash_streaming_depth(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
+                                     uint32_t* depth, sshash_streaming_report* report) {
+    if (!d || (num_reads && (!bases || !read_offsets || !depth))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (report) std::memset(report, 0, sizeof(*report));
+    return guarded([&] {
+        if (num_reads == 0) return;
+        const depth_arrays on_devices(*d->eng);
+        const streaming_report r = d->eng->streaming_depth_host(bases, read_offsets, num_reads, on_devices);
+        on_devices.add_into(depth);
+        if (report) fill_report(report, r);
+    });
+}
+
+sshash_status sshash_streaming_depth_from_file(const sshash_dict* d, const char* filename, int multiline, uint32_t* depth,
+                                               sshash_streaming_report* report) {
+    if (!d || !filename || !depth) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (report) std::memset(report, 0, sizeof(*report));
+    return guarded([&] {
+        read_stream in(filename, multiline != 0, d->idx->k);
+        if (!in.supported()) {
+            fprintf(stderr, "unsupported query file format\n");
+            return;
+        }
+        /* the sequential reader, as sshash_streaming_cover_from_file; the deltas stay on the devices from the first batch to the last */
+        const depth_arrays on_devices(*d->eng);
+        streaming_report total;
+        for_each_batch(in, [&](read_batch const& batch) {
+            total += d->eng->streaming_depth_host(batch.bases.data(), batch.offsets.data(), batch.num_reads(), on_devices);
+        });
+        on_devices.add_into(depth);
+        if (report) fill_report(report, total);
+    });
+}
+
+sshash_status sshash_depth_string_sums_device(const sshash_dict* d, int device, const uint32_t* depth, uint64_t* sums, uint64_t* total,
+                                              void* hip_stream) {
+    if (!d || !depth || !sums) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] { d->eng->depth_string_sums_device(device, depth, sums, total, hip_stream); });
+}
+
+sshash_status sshash_depth_string_sums(const sshash_dict* d, const uint32_t* depth, uint64_t* sums, uint64_t* total) {
+    if (!d || !depth || !sums) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] {
+        host_index const& x = *d->idx;
+        uint64_t all = 0;
+        for (uint64_t s = 0; s < x.num_strings; ++s) {  // the ids of string s, as sshash_cover_string_counts
+            const uint64_t lo = x.endpoints[s] - s * (x.k - 1), hi = x.endpoints[s + 1] - (s + 1) * (x.k - 1);
+            uint64_t sum = 0;
+            for (uint64_t i = lo; i < hi; ++i) sum += depth[i];
+            sums[s] = sum;
+            all += sum;
+        }
+        if (total) *total = all;
+    });
+}
+
 sshash_status sshash_streaming_lookup_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
                                              uint64_t num_reads, uint64_t total_bases, const sshash_results* out, uint64_t* report,
                                              void* hip_stream) {

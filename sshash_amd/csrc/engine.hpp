@@ -66,6 +66,23 @@ private:
     std::vector<uint64_t*> m_bitmaps;
 };
 
+/* The deltas of one depth array (num_kmers words of 32 bits, zeroed) in the HBM of every resident replica, for the length of a host
+   call or of a whole query file (streaming.hip); throws no_device when no replica is resident. */
+class depth_arrays {
+public:
+    explicit depth_arrays(engine const& eng);
+    ~depth_arrays();
+    depth_arrays(depth_arrays const&) = delete;
+    depth_arrays& operator=(depth_arrays const&) = delete;
+    uint32_t* on(int device) const;           // the deltas on `device` (device pointer)
+    void add_into(uint32_t* h_depth) const;  // ONCE, when the lanes' work is done: every replica finishes its deltas in place and its depths are added to the caller's host array
+private:
+    engine const& m_eng;
+    uint64_t m_kmers;
+    std::vector<int> m_devices;
+    std::vector<uint32_t*> m_deltas;
+};
+
 class engine {
 public:
     explicit engine(std::shared_ptr<host_index> idx);
@@ -148,7 +165,8 @@ public:
        the totals only) is overwritten; returns the totals. A piece that holds a read above 2^16 bases takes the position-parallel
        pipeline, the others the run kernel; both give the same rows. */
     streaming_report streaming_query_per_read_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* rows,
-                                                   cover_bitmaps const* cover = nullptr /* streaming_cover_host */) const;
+                                                   cover_bitmaps const* cover = nullptr /* streaming_cover_host */,
+                                                   depth_arrays const* depth = nullptr /* streaming_depth_host */) const;
     /* An uncompressed FASTQ file, read and parsed by the lanes themselves (reads.hpp: fastq_pieces): every lane takes pieces of
        the file from a shared counter, parses a piece straight into its pinned block, uploads it and runs the streaming
        kernels -- no single reader thread, no intermediate batch. Returns false when the file turned out not to be four lines
@@ -186,6 +204,23 @@ public:
        (one word, nullable) are overwritten. */
     void cover_string_counts_device(int device, uint64_t const* d_cover, uint64_t* d_counts, uint64_t* d_total, void* stream) const;
 
+    /* HOW OFTEN the reads hold each k-mer of the dictionary (sshash_streaming_depth[_device] in include/sshash_amd.h), as a difference
+       array: for every run of ids [lo, hi) +1 is added to `d_deltas[lo]` and, if hi < num_kmers, -1 to `d_deltas[hi]` (num_kmers words of
+       32 bits, modulo 2^32, accumulated into). Device buffers, asynchronous, always the run kernel, its depth form: one launch; `d_report`
+       (nullable) is accumulated into. Throws on a minimizer shard (streaming.hip). */
+    void streaming_depth_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
+                                uint32_t* d_deltas, uint64_t* d_report, void* stream) const;
+    /* d_depth[i] = d_deltas[0] + .. + d_deltas[i] modulo 2^32 for the num_kmers ids; d_depth == d_deltas is allowed, no other overlap.
+       Asynchronous; the tile sums (4 bytes per 4096 k-mers) are allocated and freed by the call, stream-ordered, from the replica's pool. */
+    void depth_finish_device(int device, uint32_t const* d_deltas, uint32_t* d_depth, void* stream) const;
+    /* Host buffers, over all resident replicas, into the deltas `depth` keeps on them (the caller adds the finished depths into its own
+       array when it is done: depth_arrays::add_into); a piece that holds a read above 2^16 bases takes the position-parallel pipeline
+       and is marked from its per-k-mer ids, which gives the same depths -- as does every piece of a minimizer shard. Returns the totals. */
+    streaming_report streaming_depth_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, depth_arrays const& depth) const;
+    /* The 64-bit sum of a depth array over the ids of every string, device buffers, asynchronous: `d_sums` (num_strings words) and
+       `d_total` (one word, nullable) are overwritten. */
+    void depth_string_sums_device(int device, uint32_t const* d_depth, uint64_t* d_sums, uint64_t* d_total, void* stream) const;
+
     /* Per-k-mer results of the streaming query (streaming_query::lookup for every k-mer of every read,
        include/streaming_query.hpp:56-109): entry read_offsets[r] + j of every non-null array of `d_out` = the k-mer
        starting at base j of read r; places where no k-mer starts are left untouched. `d_report` (nullable): the six
@@ -195,7 +230,8 @@ public:
                                  uint64_t* d_rows = nullptr /* one report per read, n_reads x 6 words, ADDED to */,
                                  run_sink const* d_runs = nullptr /* the reads' runs, compacted out of the per-k-mer results: run_offsets overwritten,
                                                                       records below its capacity written */,
-                                 uint64_t* d_cover = nullptr /* a cover bitmap: the ids of the positive k-mers ORed into it */) const;
+                                 uint64_t* d_cover = nullptr /* a cover bitmap: the ids of the positive k-mers ORed into it */,
+                                 uint32_t* d_deltas = nullptr /* the deltas of a depth array: +1 / -1 around every positive k-mer's id added to them */) const;
     streaming_report streaming_lookup_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads,
                                            result_view const& h_out) const;
 

@@ -299,8 +299,12 @@ __device__ __forceinline__ void row_flush(uint64_t* __restrict__ row, bool parti
      STREAM_COVER        the six counters of the batch as STREAM_TOTALS, and WHICH k-mers of the dictionary the reads hold: where the record form
                          stores a run's record this one marks the run's range of k-mer ids in the bitmap at sink.records (cover_mark: bit
                          i & 63 of word i >> 6 for k-mer id i) -- the hit's string travels across the turn as there (kmer_id = off - sid * (k - 1)).
-                         One launch: no count per read, no cursor, no run_offsets, and sink.capacity means nothing. */
-enum : int { STREAM_TOTALS = 0, STREAM_ROWS = 1, STREAM_RUN_COUNTS = 2, STREAM_RUN_RECORDS = 3, STREAM_COVER = 4 };
+                         One launch: no count per read, no cursor, no run_offsets, and sink.capacity means nothing.
+     STREAM_DEPTH        the six counters of the batch as STREAM_TOTALS, and HOW OFTEN the reads hold each k-mer of the dictionary, as a difference
+                         array: where the cover form marks a run's range of ids [lo, hi) this one adds +1 to word lo and -1 to word hi of the
+                         32-bit deltas at sink.records (depth_mark_run; hi = num_kmers: no word, nothing added) -- one or two atomics a run,
+                         whatever its length; the inclusive prefix sum of the deltas (inclusive_scan_u32) is the depth. One launch, as the cover. */
+enum : int { STREAM_TOTALS = 0, STREAM_ROWS = 1, STREAM_RUN_COUNTS = 2, STREAM_RUN_RECORDS = 3, STREAM_COVER = 4, STREAM_DEPTH = 5 };
 
 /* the record of the run of `n` k-mers whose first (in read order) starts at base `at` of the packed reads and lies at offset `off` of
    the strings, in string `sid`: to place `cursor` of the records, unless that is past what the read or the caller has room for */
@@ -338,12 +342,23 @@ __device__ __forceinline__ void cover_mark_run(dict_view const& d, run_sink cons
     cover_mark(static_cast<uint64_t*>(sink.records), lo, lo + n);
 }
 
+/* the same run into the deltas of a depth array (num_kmers words of 32 bits, arithmetic modulo 2^32): +1 where its ids begin, -1 behind
+   them unless that is behind the array. Nothing comes back: the lane does not wait for either. */
+__device__ __forceinline__ void depth_mark_run(dict_view const& d, run_sink const& sink, uint64_t off, uint32_t sid, int ori, uint64_t n) {
+    const uint64_t kmer_id = off - uint64_t(sid) * (d.k - 1);
+    const uint64_t lo = ori > 0 ? kmer_id : kmer_id + 1 - n, hi = lo + n;
+    uint32_t* const deltas = static_cast<uint32_t*>(sink.records);
+    (void)__hip_atomic_fetch_add(deltas + lo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (hi < d.num_kmers) (void)__hip_atomic_fetch_add(deltas + hi, ~0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 template <int W, bool CANON, bool SK, int MODE>
 __global__ void __launch_bounds__(256, SSHASH_STREAM_WAVES)
 streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, const uint64_t* __restrict__ packed,
                      const uint64_t* __restrict__ okay, const uint64_t* __restrict__ offsets, const uint64_t n_reads,
                      const uint64_t reads_per_wave, const uint32_t move_out_every, uint64_t* __restrict__ report, const run_sink sink) {
-    constexpr bool PER_READ = MODE == STREAM_ROWS, COUNT_RUNS = MODE == STREAM_RUN_COUNTS, RECORDS = MODE == STREAM_RUN_RECORDS, COVER = MODE == STREAM_COVER;
+    constexpr bool PER_READ = MODE == STREAM_ROWS, COUNT_RUNS = MODE == STREAM_RUN_COUNTS, RECORDS = MODE == STREAM_RUN_RECORDS, COVER = MODE == STREAM_COVER,
+                   DEPTH = MODE == STREAM_DEPTH;
     __shared__ uint4 stage[SK ? 4 * 256 : 1];  // a wave's 64 bucket lines on their way from the quads that fetch them to the lanes that own them
     uint4* const wave_stage = stage + (SK ? (threadIdx.x >> 6) * 256 : 0);
     /* the counters are 32 bits wide in the lanes (six registers fewer than five 64-bit ones: with them the k <= 63 kernel fits five waves a
@@ -439,6 +454,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
             const uint64_t b = cur + k - 1, valid_end = inv < rd_end ? inv : rd_end;
             const uint64_t run = extend_run<W>(d, packed, off, ori, b, valid_end - b, run_step_load<W>(d, packed, off, ori > 0, b, 0));
             if constexpr (COVER) cover_mark_run(d, sink, off, hit_sid, ori, run + 1);
+            if constexpr (DEPTH) depth_mark_run(d, sink, off, hit_sid, ori, run + 1);
             if constexpr (RECORDS) {  // (the hit lies a base before cur)
                 run_record_store(d, sink, offsets, wave_first + my_row, cursor, cur - 1, off, hit_sid, ori, run + 1);
                 ++cursor;
@@ -670,7 +686,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                     found = r.outcome == FAST_HIT;
                     off = r.kmer_offset;
                     ori = r.orientation;
-                    if constexpr (RECORDS || COVER) hit_sid = r.string_id;
+                    if constexpr (RECORDS || COVER || DEPTH) hit_sid = r.string_id;
                     const bool stands = !found && !(where & WALK_VISITED);
                     if (stands || (where & WALK_HEAVY_PENDING)) {
                         /* a miss that stands for the k-mers behind this one: those that elect the same key occurrence (sk_key_persists)
@@ -708,7 +724,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                 found = h.found;
                 off = h.kmer_offset;
                 ori = h.orientation;
-                if constexpr (RECORDS || COVER) hit_sid = h.string_id;
+                if constexpr (RECORDS || COVER || DEPTH) hit_sid = h.string_id;
                 neg_unknown_mini = !SK && !h.found && !h.minimizer_found;
             }
         }
@@ -726,6 +742,9 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                 }
                 if constexpr (COVER) {
                     if (!pending) cover_mark_run(d, sink, off, hit_sid, ori, 1);  // a run of one
+                }
+                if constexpr (DEPTH) {
+                    if (!pending) depth_mark_run(d, sink, off, hit_sid, ori, 1);
                 }
             } else {
                 ++c_negative;
@@ -775,18 +794,19 @@ constexpr uint32_t SCAN_PER_LANE = 16, SCAN_TILE = 256 * SCAN_PER_LANE;
 inline uint64_t scan_tiles(uint64_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
 
 /* (a workgroup of 256) what the lanes before this one hold together; `total`: what all hold */
-__device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t v, uint64_t& total) {
-    __shared__ uint64_t wave_total[4];
+template <class T>  // uint64_t; uint32_t for the depth's deltas (modulo 2^32)
+__device__ __forceinline__ T block_exclusive_scan(T v, T& total) {
+    __shared__ T wave_total[4];
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    uint64_t inc = v;
+    T inc = v;
     for (uint32_t o = 1; o < 64; o <<= 1) {
-        const uint64_t t = __shfl_up(inc, o, 64);
+        const T t = __shfl_up(inc, o, 64);
         if (lane >= o) inc += t;
     }
     __syncthreads();  // (called in a loop: the totals of the call before have been read)
     if (lane == 63) wave_total[w] = inc;
     __syncthreads();
-    uint64_t before = 0;
+    T before = 0;
     total = 0;
     for (uint32_t j = 0; j < 4; ++j) {
         if (j < w) before += wave_total[j];
@@ -847,6 +867,82 @@ void exclusive_scan_u64(uint64_t* data, uint64_t n, uint64_t* sums, hipStream_t 
     HIP_CHECK(hipGetLastError());
 }
 
+/* ---- the depth out of its deltas: out[i] = in[0] + .. + in[i] modulo 2^32, the same three launches over words of 32 bits -- tile sums,
+        one workgroup over the sums (as many rounds of 256 as there are), apply; no workgroup waits for another. A lane holds 16
+        consecutive words, 64 bytes: four 16-byte loads and stores where the arrays are 16-byte aligned and the lane's words all lie
+        below n, word by word otherwise. out == in is allowed: a tile's words are all read (by the lanes that write them, in the apply
+        launch; by the sums launch before it) before one of them is written. ---- */
+__device__ __forceinline__ uint32_t scan_load16_u32(const uint32_t* __restrict__ in, uint64_t base, uint64_t n, bool aligned, uint32_t (&e)[SCAN_PER_LANE]) {
+    static_assert(SCAN_PER_LANE == 16, "four 16-byte pieces a lane");
+    uint32_t v = 0;
+    if (aligned && base + SCAN_PER_LANE <= n) {
+        const uint4* const q = reinterpret_cast<const uint4*>(in + base);
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint4 x = q[j];
+            e[4 * j] = x.x, e[4 * j + 1] = x.y, e[4 * j + 2] = x.z, e[4 * j + 3] = x.w;
+        }
+    } else {
+#pragma unroll
+        for (uint32_t j = 0; j < SCAN_PER_LANE; ++j) e[j] = base + j < n ? in[base + j] : 0u;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < SCAN_PER_LANE; ++j) v += e[j];
+    return v;
+}
+
+__global__ void __launch_bounds__(256)
+scan_tile_sums_u32_kernel(const uint32_t* in, const uint64_t n, uint32_t* __restrict__ sums) {
+    const uint64_t base = uint64_t(blockIdx.x) * SCAN_TILE + threadIdx.x * SCAN_PER_LANE;
+    uint32_t e[SCAN_PER_LANE], total;
+    block_exclusive_scan(scan_load16_u32(in, base, n, (reinterpret_cast<uintptr_t>(in) & 15u) == 0, e), total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(256)
+scan_sums_u32_kernel(uint32_t* __restrict__ sums, const uint64_t tiles) {  // one workgroup; sums[t] becomes what the tiles before t hold
+    uint32_t carry = 0;
+    for (uint64_t at = 0; at < tiles; at += 256) {
+        const uint64_t i = at + threadIdx.x;
+        const uint32_t v = i < tiles ? sums[i] : 0u;
+        uint32_t total;
+        const uint32_t before = block_exclusive_scan(v, total);
+        if (i < tiles) sums[i] = carry + before;
+        carry += total;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+scan_apply_inclusive_u32_kernel(const uint32_t* in, uint32_t* out, const uint64_t n, const uint32_t* __restrict__ sums) {  // (in and out may be one array)
+    const uint64_t base = uint64_t(blockIdx.x) * SCAN_TILE + threadIdx.x * SCAN_PER_LANE;
+    const bool aligned = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0;
+    uint32_t e[SCAN_PER_LANE], total;
+    const uint32_t v = scan_load16_u32(in, base, n, aligned, e);
+    uint32_t at = sums[blockIdx.x] + block_exclusive_scan(v, total);
+#pragma unroll
+    for (uint32_t j = 0; j < SCAN_PER_LANE; ++j) e[j] = at += e[j];
+    if (aligned && base + SCAN_PER_LANE <= n) {
+        uint4* const q = reinterpret_cast<uint4*>(out + base);
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) q[j] = make_uint4(e[4 * j], e[4 * j + 1], e[4 * j + 2], e[4 * j + 3]);
+    } else {
+#pragma unroll
+        for (uint32_t j = 0; j < SCAN_PER_LANE; ++j)
+            if (base + j < n) out[base + j] = e[j];
+    }
+}
+
+/* out[i] = in[0] + .. + in[i] modulo 2^32 for i < n; `sums`: scan_tiles(n) words of 32 bits of scratch */
+void inclusive_scan_u32(uint32_t const* in, uint32_t* out, uint64_t n, uint32_t* sums, hipStream_t s) {
+    if (n == 0) return;
+    const uint64_t tiles = scan_tiles(n);
+    if (tiles >> 31) throw error(error_kind::argument, "too many k-mers for one scan");
+    hipLaunchKernelGGL(scan_tile_sums_u32_kernel, dim3(uint32_t(tiles)), dim3(256), 0, s, in, n, sums);
+    hipLaunchKernelGGL(scan_sums_u32_kernel, dim3(1), dim3(256), 0, s, sums, tiles);
+    hipLaunchKernelGGL(scan_apply_inclusive_u32_kernel, dim3(uint32_t(tiles)), dim3(256), 0, s, in, out, n, sums);
+    HIP_CHECK(hipGetLastError());
+}
+
 /* The one place that launches the run kernel: (k > 31, canonical, skew table) -> <W, CANON, SK>, in the form MODE. */
 template <int MODE>
 void launch_run_kernel(device_replica const* rep, dict_view const& d, dim3 grid, dim3 block, hipStream_t s, uint64_t const* packed, uint64_t const* okay,
@@ -868,8 +964,9 @@ void launch_run_kernel(device_replica const* rep, dict_view const& d, dim3 grid,
 
 /* `run_phases` (with `sink`): RUNS_COUNT -- sink.run_offsets becomes the CSR offsets of the reads' runs (the counting form of the kernel, then
    the scan; `report` as without, may be null) --, RUNS_WRITE -- the records, for run_offsets that hold those offsets --, or both; or
-   RUNS_COVER alone -- the cover form, ONE launch: the runs' k-mer ids marked in the bitmap at sink.records, `report` as without, may be null. */
-enum : int { RUNS_COUNT = 1, RUNS_WRITE = 2, RUNS_COVER = 4 };
+   RUNS_COVER alone -- the cover form, ONE launch: the runs' k-mer ids marked in the bitmap at sink.records, `report` as without, may be null --;
+   or RUNS_DEPTH alone -- the depth form, ONE launch: the runs' +1 / -1 added to the 32-bit deltas at sink.records, `report` as with the cover. */
+enum : int { RUNS_COUNT = 1, RUNS_WRITE = 2, RUNS_COVER = 4, RUNS_DEPTH = 8 };
 void launch_streaming_runs(device_replica const* rep, char const* bases, uint64_t const* offsets, uint64_t n_reads, uint64_t total_bases, uint64_t* report,
                            hipStream_t s, uint64_t* rows = nullptr /* per read: n_reads x 6 words; `report` may then be null */,
                            run_sink sink = run_sink{nullptr, nullptr, 0}, int run_phases = 0) {
@@ -898,7 +995,7 @@ void launch_streaming_runs(device_replica const* rep, char const* bases, uint64_
     const uint64_t reads_per_wave = (n_reads + waves - 1) / waves;
     const dim3 grid(uint32_t(waves / 4)), block(256);
     const uint32_t move_out_every = uint32_t(test_hook_u64("stream_move_out_every", uint64_t(1) << 16, 1, uint64_t(1) << 16));
-    /* the cover and the counting form count the batch as they go: where nobody asked for the six counters they go into the scratch */
+    /* the cover, the depth and the counting form count the batch as they go: where nobody asked for the six counters they go into the scratch */
     auto totals = [&]() {
         if (report) return report;
         uint64_t* spare = scan_sums + scan_tiles(n_reads + 1);
@@ -909,6 +1006,8 @@ void launch_streaming_runs(device_replica const* rep, char const* bases, uint64_
     if ((rows || (run_phases & (RUNS_COUNT | RUNS_WRITE))) && reads_per_wave >> 31) throw error(error_kind::argument, "too many reads for one call");
     if (run_phases & RUNS_COVER) {
         launch_run_kernel<STREAM_COVER>(rep, d, grid, block, s, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, totals(), sink);
+    } else if (run_phases & RUNS_DEPTH) {
+        launch_run_kernel<STREAM_DEPTH>(rep, d, grid, block, s, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, totals(), sink);
     } else if (run_phases) {
         if (run_phases & RUNS_COUNT) {
             launch_run_kernel<STREAM_RUN_COUNTS>(rep, d, grid, block, s, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, totals(), sink);
@@ -1007,6 +1106,33 @@ void engine::streaming_cover_device(int device, char const* d_bases, uint64_t co
     total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
     if (total_bases == 0) return;  // empty reads only: no k-mer
     launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, run_sink{nullptr, d_cover, 0}, RUNS_COVER);
+}
+
+/* How often the reads hold each k-mer of the dictionary (sshash_streaming_depth_device): the depth form of the run kernel, one launch,
+   into the deltas; depth_finish_device turns deltas into depths. */
+void engine::streaming_depth_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
+                                    uint32_t* d_deltas, uint64_t* d_report, void* stream) const {
+    device_replica const* rep = replica(device);  // (not resident: that error first)
+    if (n_reads == 0) return;
+    if (!d_deltas) throw error(error_kind::argument, "deltas pointer is null");
+    /* (a run is measured along the STRING, which a shard holds whole: behind a k-mer of its own it runs on through k-mers of other
+       shards, and the shards' arrays added would hold those twice. The cover does not mind -- OR --, a count does.) */
+    if (m_idx->num_shards > 1) throw error(error_kind::argument, "a minimizer shard counts per k-mer: use the host call (sshash_streaming_depth)");
+    device_guard guard(device);
+    hipStream_t s = hipStream_t(stream);
+    total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
+    if (total_bases == 0) return;  // empty reads only: no k-mer
+    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, run_sink{nullptr, d_deltas, 0}, RUNS_DEPTH);
+}
+
+void engine::depth_finish_device(int device, uint32_t const* d_deltas, uint32_t* d_depth, void* stream) const {
+    device_replica const* rep = replica(device);
+    if (!d_deltas || !d_depth) throw error(error_kind::argument, "null pointer");
+    device_guard guard(device);
+    hipStream_t s = hipStream_t(stream);
+    const uint64_t n = rep->view.num_kmers;
+    device_buffers tmp(rep, s);  // (stream-ordered, out of the replica's pool: handed back behind the apply launch)
+    inclusive_scan_u32(d_deltas, d_depth, n, tmp.alloc<uint32_t>(scan_tiles(n)), s);
 }
 
 /* ---- per-k-mer results: the streaming query as a position-parallel pipeline -----------------------------------
@@ -1338,6 +1464,26 @@ cover_mark_ids_kernel(const uint8_t* __restrict__ flags, const uint64_t* __restr
     (void)__hip_atomic_fetch_or(reinterpret_cast<unsigned long long*>(cover) + word, (unsigned long long)bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+/* ---- the depth's deltas out of the per-k-mer results (the host calls' route for reads too long for one lane): one lane a place, +1 at
+        its k-mer's id and -1 behind it. Along a hit the next place holds the next id (forward) or the one before (backward), and then a
+        +1 and a -1 meet in one word: the pair (p, p + 1) takes both away -- forward the -1 of p and the +1 of p + 1, backward the +1 of p
+        and the -1 of p + 1 --, so that a run costs what it costs the run kernel and only its ends reach memory. A lane looks at both its
+        neighbours (whatever read they lie in: the sum is all that counts) and adds what is left of its two words, each -1, 0 or +1. ---- */
+__global__ void __launch_bounds__(256)
+depth_mark_ids_kernel(const uint8_t* __restrict__ flags, const uint64_t* __restrict__ kmer_id, const uint64_t total_bases, const uint64_t num_kmers,
+                      uint32_t* __restrict__ deltas) {
+    const uint64_t p = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    auto id_at = [&](uint64_t q) { return q < total_bases && (flags[q] & SQ_VALID) ? kmer_id[q] : INVALID_U64; };  // (p - 1 at p = 0: no place)
+    const uint64_t id = id_at(p);
+    if (id == INVALID_U64 || id >= num_kmers) return;
+    const uint64_t before = id_at(p - 1), after = id_at(p + 1);
+    const bool has_before = before != INVALID_U64, has_after = after != INVALID_U64;
+    const uint32_t plus = 1u - uint32_t(has_before && before + 1 == id) - uint32_t(has_after && after + 1 == id);
+    const uint32_t minus = 1u - uint32_t(has_after && id + 1 == after) - uint32_t(has_before && id + 1 == before);
+    if (plus) (void)__hip_atomic_fetch_add(deltas + id, plus, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (minus && id + 1 < num_kmers) (void)__hip_atomic_fetch_add(deltas + id + 1, 0u - minus, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 /* ---- covered k-mers per string: a segmented popcount of a cover bitmap. The ids of string s are [begin(s), begin(s + 1)),
         begin(s) = endpoints[s] - s * (k - 1); strings hold from one k-mer to millions, so the lanes go over the bitmap's WORDS, one each.
         A lane finds the string of its word's first id -- the workgroup's first lane by bisection over all strings, the others from
@@ -1433,11 +1579,86 @@ void engine::cover_string_counts_device(int device, uint64_t const* d_cover, uin
     HIP_CHECK(hipGetLastError());
 }
 
+/* ---- depth per string: sums[s] = the 64-bit sum of depth over the ids of string s (the id ranges of cover_string_counts_kernel). One
+        lane an id. Every string holds a k-mer, so the 256 ids of a workgroup lie in at most 256 strings, the first of which one lane finds
+        by bisection: the first ids of the 256 strings behind it go to LDS, a lane finds its string among them (8 steps, no global load),
+        the workgroup sums per string in LDS (a wave that lies inside one string: one add for the wave), and each string it met gets ONE global atomic. `sums` is zeroed by the caller. ---- */
+__global__ void __launch_bounds__(256)
+depth_string_sums_kernel(const uint32_t* __restrict__ depth, const uint64_t num_kmers, const uint64_t* __restrict__ endpoints, const uint64_t num_strings,
+                         const uint32_t k, uint64_t* __restrict__ sums, uint64_t* __restrict__ total) {
+    __shared__ uint64_t block_string;
+    __shared__ uint64_t first_id_behind[256];       // of string block_string + 1 + j (all-ones: there is no such string)
+    __shared__ unsigned long long string_sum[256];  // of string block_string + j
+    __shared__ uint64_t block_sum[4];
+    const uint64_t id0 = uint64_t(blockIdx.x) * 256, id = id0 + threadIdx.x;
+    if (threadIdx.x == 0) {  // the largest s with begin(s) <= id0 (id0 < num_kmers: the grid holds no empty workgroup)
+        uint64_t lo = 0, hi = num_strings - 1;
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo + 1) / 2;
+            if (string_first_id(endpoints, mid, k) <= id0) lo = mid;
+            else hi = mid - 1;
+        }
+        block_string = lo;
+    }
+    __syncthreads();
+    const uint64_t behind = block_string + 1 + threadIdx.x;
+    first_id_behind[threadIdx.x] = behind <= num_strings ? string_first_id(endpoints, behind, k) : ~uint64_t(0);  // (begin(num_strings) = num_kmers)
+    string_sum[threadIdx.x] = 0;
+    __syncthreads();
+    uint64_t v = 0;
+    uint32_t mine_at = 0;  // my string, counted from block_string (a lane behind the last id: none, and nothing to add)
+    const bool has = id < num_kmers;
+    if (has) {
+        v = depth[id];
+        /* how many of those strings begin at or before id: first_id_behind[j] > id0 + j, so fewer than 256 */
+        uint32_t lo = 0, hi = 256;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) / 2;
+            if (first_id_behind[mid] <= id) lo = mid + 1;
+            else hi = mid;
+        }
+        mine_at = lo;
+    }
+    /* strings hold hundreds of k-mers as a rule: a wave that lies in one string adds its sum once, a wave that does not adds lane by lane */
+    const uint32_t wave_at = __shfl(mine_at, 0, 64);
+    const uint64_t wave_total = wave_sum(v);
+    if (__ballot(has && mine_at != wave_at) == 0) {
+        if ((threadIdx.x & 63u) == 0 && wave_total) atomicAdd(string_sum + wave_at, (unsigned long long)wave_total);
+    } else if (v) {
+        atomicAdd(string_sum + mine_at, (unsigned long long)v);
+    }
+    __syncthreads();
+    const unsigned long long mine = string_sum[threadIdx.x];
+    if (mine) atomicAdd(reinterpret_cast<unsigned long long*>(sums + block_string + threadIdx.x), mine);
+    if (!total) return;  // (uniform)
+    if ((threadIdx.x & 63u) == 0) block_sum[threadIdx.x >> 6] = wave_total;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint64_t sum = block_sum[0] + block_sum[1] + block_sum[2] + block_sum[3];
+        if (sum) atomicAdd(reinterpret_cast<unsigned long long*>(total), (unsigned long long)sum);
+    }
+}
+
+void engine::depth_string_sums_device(int device, uint32_t const* d_depth, uint64_t* d_sums, uint64_t* d_total, void* stream) const {
+    device_replica const* rep = replica(device);
+    if (!d_depth || !d_sums) throw error(error_kind::argument, "null pointer");
+    device_guard guard(device);
+    dict_view const& d = rep->view;
+    hipStream_t s = hipStream_t(stream);
+    HIP_CHECK(hipMemsetAsync(d_sums, 0, d.num_strings * sizeof(uint64_t), s));
+    if (d_total) HIP_CHECK(hipMemsetAsync(d_total, 0, sizeof(uint64_t), s));
+    if (d.num_kmers == 0 || d.num_strings == 0) return;
+    const uint64_t blocks = (d.num_kmers + 255) / 256;
+    if (blocks >> 31) throw error(error_kind::argument, "too many k-mers for one launch");
+    hipLaunchKernelGGL(depth_string_sums_kernel, dim3(uint32_t(blocks)), dim3(256), 0, s, d_depth, d.num_kmers, d.endpoints, d.num_strings, d.k, d_sums, d_total);
+    HIP_CHECK(hipGetLastError());
+}
+
 void engine::streaming_lookup_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
                                      uint64_t total_bases, result_view const& d_out, uint64_t* d_report, void* stream, uint64_t* d_rows,
-                                     run_sink const* runs, uint64_t* d_cover) const {
+                                     run_sink const* runs, uint64_t* d_cover, uint32_t* d_deltas) const {
     device_replica const* rep = replica(device);
-    if (!d_out.kmer_id && !d_report && !d_rows && !runs && !d_cover) throw error(error_kind::argument, "neither a kmer_id array nor a report to fill");
+    if (!d_out.kmer_id && !d_report && !d_rows && !runs && !d_cover && !d_deltas) throw error(error_kind::argument, "neither a kmer_id array nor a report to fill");
     if (d_out.minimizer_found) throw error(error_kind::argument, "the streaming lookup does not report minimizer_found");
     if (n_reads == 0 || total_bases == 0) return;
     device_guard guard(device);
@@ -1486,6 +1707,10 @@ void engine::streaming_lookup_device(int device, char const* d_bases, uint64_t c
     }
     if (d_cover) {
         hipLaunchKernelGGL(cover_mark_ids_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, flags, ids, total_bases, d_cover);
+        HIP_CHECK(hipGetLastError());
+    }
+    if (d_deltas) {
+        hipLaunchKernelGGL(depth_mark_ids_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, flags, ids, total_bases, d.num_kmers, d_deltas);
         HIP_CHECK(hipGetLastError());
     }
     if (runs) {
@@ -1679,9 +1904,11 @@ streaming_report engine::streaming_query_host(char const* bases, uint64_t const*
 
 /* With `rows` (n_reads x 6 words, host) a lane's device block also holds a row for every read of the largest piece, and a piece's rows
    come back into the caller's array at the piece's first read. With `cover` (and no rows) a piece's k-mers are marked in the bitmap
-   that `cover` keeps on the lane's device: the lanes of a device share it, OR commutes. */
+   that `cover` keeps on the lane's device: the lanes of a device share it, OR commutes. With `depth` (and neither) its runs are added to
+   the deltas that `depth` keeps there: addition commutes as well. (A minimizer shard takes the per-k-mer route for every piece: only
+   that one asks of every k-mer whether the shard owns it -- streaming_depth_device.) */
 streaming_report engine::streaming_query_per_read_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* rows,
-                                                       cover_bitmaps const* cover) const {
+                                                       cover_bitmaps const* cover, depth_arrays const* depth) const {
     if (n_reads == 0) return {};
     const piece_cuts pieces = cut_lane_pieces(read_offsets, n_reads);
     const uint64_t row_bytes = 6 * sizeof(uint64_t);
@@ -1695,6 +1922,9 @@ streaming_report engine::streaming_query_per_read_host(char const* bases, uint64
         } else if (cover) {
             if (p.long_read) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, nullptr, nullptr, cover->on(p.device));
             else if (p.nb) streaming_cover_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, cover->on(p.device), p.d_report, p.s);
+        } else if (depth) {
+            if (p.long_read || m_idx->num_shards > 1) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, nullptr, nullptr, nullptr, depth->on(p.device));
+            else if (p.nb) streaming_depth_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, depth->on(p.device), p.d_report, p.s);
         } else {
             piece_totals(*this, p.device, p.long_read, p.d_bases, p.d_offsets, p.n, p.nb, p.d_report, p.s);
         }
@@ -1759,6 +1989,68 @@ void cover_bitmaps::or_into(uint64_t* h_cover) const {
 
 streaming_report engine::streaming_cover_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, cover_bitmaps const& cover) const {
     return streaming_query_per_read_host(bases, read_offsets, n_reads, nullptr, &cover);
+}
+
+/* ---- the depth arrays of a host call: the deltas of one depth array per resident replica, zeroed, in HBM for as long as the object
+        lives; at the end every replica finishes its own on the device and the depths are added into the caller's host array ---- */
+depth_arrays::depth_arrays(engine const& eng) : m_eng(eng), m_kmers(eng.index().num_kmers), m_devices(resident_devices(eng)) {
+    int prev = 0;
+    HIP_CHECK(hipGetDevice(&prev));
+    const uint64_t bytes = std::max<uint64_t>(m_kmers, 1) * sizeof(uint32_t);
+    try {
+        for (int device : m_devices) {
+            HIP_CHECK(hipSetDevice(device));
+            void* p = nullptr;
+            HIP_CHECK(hipMalloc(&p, bytes));
+            m_deltas.push_back(static_cast<uint32_t*>(p));
+            HIP_CHECK(hipMemsetAsync(p, 0, bytes, nullptr));
+            HIP_CHECK(hipStreamSynchronize(nullptr));  // (the lanes' streams do not wait for the null stream)
+        }
+    } catch (...) {
+        for (size_t i = 0; i < m_deltas.size(); ++i) {
+            (void)hipSetDevice(m_devices[i]);
+            (void)hipFree(m_deltas[i]);
+        }
+        (void)hipSetDevice(prev);
+        throw;
+    }
+    (void)hipSetDevice(prev);
+}
+
+depth_arrays::~depth_arrays() {
+    int prev = 0;
+    if (hipGetDevice(&prev) != hipSuccess) return;
+    for (size_t i = 0; i < m_deltas.size(); ++i) {
+        (void)hipSetDevice(m_devices[i]);
+        (void)hipFree(m_deltas[i]);
+    }
+    (void)hipSetDevice(prev);
+}
+
+uint32_t* depth_arrays::on(int device) const {
+    for (size_t i = 0; i < m_devices.size(); ++i)
+        if (m_devices[i] == device) return m_deltas[i];
+    throw error(error_kind::internal, "no depth array on this device");
+}
+
+void depth_arrays::add_into(uint32_t* h_depth) const {
+    const uint64_t chunk = uint64_t(1) << 22;  // 16 MiB of words at a time: the host side stays bounded
+    std::vector<uint32_t> part(std::min(chunk, m_kmers));
+    for (size_t i = 0; i < m_devices.size(); ++i) {
+        if (m_kmers == 0) break;
+        device_guard guard(m_devices[i]);
+        m_eng.depth_finish_device(m_devices[i], m_deltas[i], m_deltas[i], nullptr);  // in place: the deltas are gone
+        HIP_CHECK(hipStreamSynchronize(nullptr));
+        for (uint64_t at = 0; at < m_kmers; at += chunk) {
+            const uint64_t n = std::min(chunk, m_kmers - at);
+            HIP_CHECK(hipMemcpy(part.data(), m_deltas[i] + at, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            for (uint64_t j = 0; j < n; ++j) h_depth[at + j] += part[j];
+        }
+    }
+}
+
+streaming_report engine::streaming_depth_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, depth_arrays const& depth) const {
+    return streaming_query_per_read_host(bases, read_offsets, n_reads, nullptr, nullptr, &depth);
 }
 
 /* The runs of every read, host buffers (sshash_streaming_runs): pieces and lanes as above (run_piece_lanes). A piece's
