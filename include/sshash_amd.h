@@ -254,6 +254,37 @@ sshash_status sshash_streaming_query_device(const sshash_dict* d, int device, co
                                             const uint64_t* read_offsets, uint64_t num_reads, uint64_t total_bases,
                                             uint64_t* report, void* hip_stream);
 
+/* ---- LONG READS: segments. The streaming calls run on the run kernel, where one lane walks one read: a batch of few long reads -- ONT
+ *      or HiFi reads, contigs, chromosomes -- is few lanes, and takes as long as its longest read. A k-mer is positive, negative or
+ *      invalid whatever lies around it, so such a read can be cut: with S = kmers_per_segment a read of K k-mers becomes ceil(K / S)
+ *      SEGMENTS of S k-mers (neighbours overlap by k - 1 bases; nothing is copied), one lane each. What differs is put right on the
+ *      device: a segment's first k-mer counts as a search where in the whole read it may be an extension -- the rule of the runs
+ *      below --, and a pass over the seams moves those back. The six counters, every per-read row, the cover and the depth are
+ *      word for word what the uncut reads give.
+ *      Segmenting is OPT-IN: a new dictionary is at SSHASH_SEGMENTS_OFF with device_calls = 0 and takes the routes it always took.
+ *      kmers_per_segment: 0 = the library's default S (256, RESULTS.md: best of 256, 1024, 4096 through the host call; the device calls
+ *      favour 1024 slightly); SSHASH_SEGMENTS_OFF = never segment; otherwise 1 .. 2^30 (tiny values are allowed and only slow: tests
+ *      put seams into small reads with them). Anything else, or a NULL dictionary, is SSHASH_ERR_ARGUMENT. Needs no device. Not to be changed while a call
+ *      on the dictionary is in flight.
+ *      Host and file calls (sshash_streaming_query, _per_read, _cover, _depth and their _from_file forms), once an S is set: a piece of
+ *      the batch that holds a read of more than S k-mers takes the run kernel over segments; pieces of shorter reads take exactly the launches they took
+ *      before. With SSHASH_SEGMENTS_OFF a piece that holds a read above 2^16 bases goes through the position-parallel pipeline of
+ *      sshash_streaming_lookup instead (one point lookup per k-mer, the same results).
+ *      Device calls (sshash_streaming_query_device, _per_read_device, _cover_device, _depth_device): segment only with device_calls != 0
+ *      -- they cannot see the reads' lengths without a synchronisation, and building the table costs a batch of short reads three small
+ *      launches and a scan. With it: scratch of 24 bytes per segment (72 with rows) for at most num_reads + total_bases / S segments,
+ *      sized from that bound without a synchronisation; the entries past the true count are empty and lie behind the last segment, so
+ *      on reads shorter than S the last waves of the launch find nothing to do while the others carry all of it (150-base reads at
+ *      S = 256: two fifths of the waves, 4.5 -> 6.3 ms) -- switch it on for long reads. Without it they are launch for launch what they were.
+ *      Never segmented: sshash_streaming_runs[_device] (records that span seams want a merge pass), sshash_streaming_lookup[_device], and
+ *      every call on a minimizer shard (num_shards > 1: a shard's run kernel follows a run through k-mers it does not own, which a look
+ *      at a seam would miss) -- those keep their routes whatever is set here.
+ *      sshash_get_read_segments: the setting (S with the default resolved, or SSHASH_SEGMENTS_OFF), device_calls, and how many
+ *      launches of the run kernel over a segment table the dictionary has made so far; each pointer may be NULL. ---- */
+#define SSHASH_SEGMENTS_OFF UINT64_MAX
+sshash_status sshash_set_read_segments(sshash_dict* d, uint64_t kmers_per_segment, int device_calls);
+sshash_status sshash_get_read_segments(const sshash_dict* d, uint64_t* kmers_per_segment, int* device_calls, uint64_t* segmented_launches);
+
 /* ---- the streaming query PER READ (no reference counterpart as a call; the reference's state machine is reset at every read,
  *      src/query.cpp:78-108, so the report it would give for read r alone is well defined). Rows are sshash_streaming_report
  *      structs, one per read, row r for read r of the call; the six counters of sshash_streaming_query over the same reads are the
@@ -261,13 +292,14 @@ sshash_status sshash_streaming_query_device(const sshash_dict* d, int device, co
  *      codes as the calls above; per_read == NULL with num_reads > 0 is SSHASH_ERR_ARGUMENT, num_reads == 0 writes nothing. ---- */
 /* device buffers, asynchronous on hip_stream. per_read: num_reads rows, OVERWRITTEN (every row is written). report: 6 uint64
  * counters, ACCUMULATED into as sshash_streaming_query_device does; may be NULL. total_bases as for sshash_streaming_query_device.
- * Like that call it always takes the run kernel -- one lane walks one read, whatever its length: a caller holding reads of
- * megabases cuts them itself or takes the host call below. */
+ * Like that call it always takes the run kernel -- one lane walks one read, whatever its length, unless sshash_set_read_segments has
+ * switched segments on for the device calls: then one lane walks one segment, and a read of megabases costs what its bases cost. */
 sshash_status sshash_streaming_query_per_read_device(const sshash_dict* d, int device, const char* bases,
                                                      const uint64_t* read_offsets, uint64_t num_reads, uint64_t total_bases,
                                                      sshash_streaming_report* per_read, uint64_t* report, void* hip_stream);
-/* host buffers; sharded over all resident replicas like sshash_streaming_query (a piece that holds a read above 2^16 bases goes
- * through the position-parallel pipeline of sshash_streaming_lookup, which gives the same rows); report may be NULL */
+/* host buffers; sharded over all resident replicas like sshash_streaming_query (a piece that holds a long read takes the run kernel
+ * over segments -- sshash_set_read_segments; with segments off, above 2^16 bases, the position-parallel pipeline of
+ * sshash_streaming_lookup --, which gives the same rows); report may be NULL */
 sshash_status sshash_streaming_query_per_read(const sshash_dict* d, const char* bases, const uint64_t* read_offsets,
                                               uint64_t num_reads, sshash_streaming_report* per_read,
                                               sshash_streaming_report* report);
@@ -321,7 +353,7 @@ sshash_status sshash_streaming_runs_device(const sshash_dict* d, int device, con
                                            sshash_streaming_run* runs, uint64_t runs_capacity, uint64_t* report, void* hip_stream);
 /* host buffers, sharded over all resident replicas like sshash_streaming_query_per_read (a piece that holds a read above 2^16 bases
  * goes through the position-parallel pipeline of sshash_streaming_lookup and a compaction behind it, which give the same
- * records); same capacity rule; report may be NULL. A read of 2^31 bases or more is SSHASH_ERR_ARGUMENT (read_pos / num_kmers could
+ * records: the runs are never cut into segments); same capacity rule; report may be NULL. A read of 2^31 bases or more is SSHASH_ERR_ARGUMENT (read_pos / num_kmers could
  * not hold it). */
 sshash_status sshash_streaming_runs(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
                                     uint64_t* run_offsets, sshash_streaming_run* runs, uint64_t runs_capacity,
@@ -342,15 +374,15 @@ sshash_status sshash_streaming_runs(const sshash_dict* d, const char* bases, con
 sshash_status sshash_cover_words(const sshash_dict* d, uint64_t* words);
 /* device buffers, asynchronous on hip_stream. cover: sshash_cover_words words, ACCUMULATED into (OR); nothing at or beyond them is
  * touched. report: 6 uint64 counters, ACCUMULATED into as sshash_streaming_query_device does -- the same six counters --; may be
- * NULL. total_bases as for sshash_streaming_query_device. Always the run kernel (one lane walks one read, whatever its length), in
- * ONE launch: where sshash_streaming_runs_device writes a run's record this call ORs the run's id range into the bitmap, one 64-bit
+ * NULL. total_bases as for sshash_streaming_query_device. Always the run kernel (one lane walks one read, whatever its length, or
+ * one segment: sshash_set_read_segments -- the bits are the same, OR is idempotent), in ONE launch: where sshash_streaming_runs_device writes a run's record this call ORs the run's id range into the bitmap, one 64-bit
  * atomic for the first and for the last word it touches; no scratch beyond that of sshash_streaming_query_device. */
 sshash_status sshash_streaming_cover_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
                                             uint64_t num_reads, uint64_t total_bases, uint64_t* cover, uint64_t* report, void* hip_stream);
 /* host buffers, sharded over all resident replicas like sshash_streaming_query: every replica marks a bitmap of its own in HBM (8
  * bytes per 64 k-mers, for the length of the call) and those are ORed into `cover` (host, sshash_cover_words words) at the end. A piece
- * that holds a read above 2^16 bases goes through the position-parallel pipeline of sshash_streaming_lookup and is marked from its
- * per-k-mer ids, which gives the same bits. report may be NULL. */
+ * that holds a long read takes the run kernel over segments (sshash_set_read_segments; with segments off, above 2^16 bases, the
+ * position-parallel pipeline of sshash_streaming_lookup, marked from its per-k-mer ids), which gives the same bits. report may be NULL. */
 sshash_status sshash_streaming_cover(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
                                      uint64_t* cover, sshash_streaming_report* report);
 /* a query file (.fa/.fasta/.fq/.fastq, optionally .gz; `multiline` as for sshash_streaming_query_from_file): every replica keeps ONE
@@ -388,7 +420,8 @@ sshash_status sshash_cover_string_counts(const sshash_dict* d, const uint64_t* c
 /* device buffers, asynchronous on hip_stream. deltas: num_kmers uint32, ACCUMULATED into (the caller zeroes it before the first call);
  * nothing at or beyond deltas + num_kmers is touched. report and total_bases as for sshash_streaming_cover_device. Always the run kernel,
  * in ONE launch: where sshash_streaming_cover_device ORs a run's id range into the bitmap this call issues one or two 32-bit atomic
- * adds; no scratch beyond that of sshash_streaming_query_device. */
+ * adds; no scratch beyond that of sshash_streaming_query_device. Over segments (sshash_set_read_segments) a run that spans a seam arrives
+ * as two, [lo, mid) and [mid, hi): the +1 and the -1 at mid cancel, the deltas are those of [lo, hi). */
 sshash_status sshash_streaming_depth_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
                                             uint64_t num_reads, uint64_t total_bases, uint32_t* deltas, uint64_t* report, void* hip_stream);
 /* deltas -> depths: depth[i] = deltas[0] + .. + deltas[i] modulo 2^32 over the num_kmers words (device pointers, asynchronous on
@@ -398,8 +431,9 @@ sshash_status sshash_streaming_depth_device(const sshash_dict* d, int device, co
 sshash_status sshash_depth_finish_device(const sshash_dict* d, int device, const uint32_t* deltas, uint32_t* depth, void* hip_stream);
 /* host buffers, sharded over all resident replicas like sshash_streaming_cover: every replica keeps one delta array in HBM (4 bytes per
  * k-mer, zeroed, for the length of the call), finishes it on the device, and the results are ADDED into `depth` (host, num_kmers uint32;
- * the caller zeroes it for a fresh count). A piece that holds a read above 2^16 bases goes through the position-parallel pipeline of
- * sshash_streaming_lookup and is marked from its per-k-mer ids, which gives the same depths. report may be NULL. */
+ * the caller zeroes it for a fresh count). A piece that holds a long read takes the run kernel over segments (sshash_set_read_segments;
+ * with segments off, above 2^16 bases, the position-parallel pipeline of sshash_streaming_lookup, marked from its per-k-mer ids), which
+ * gives the same depths. report may be NULL. */
 sshash_status sshash_streaming_depth(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
                                      uint32_t* depth, sshash_streaming_report* report);
 /* a query file, as sshash_streaming_cover_from_file (the sequential reader, bounded host memory): every replica keeps ONE delta array in

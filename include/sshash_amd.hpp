@@ -363,6 +363,23 @@ public:
                                 uint32_t* d_deltas, uint64_t* d_report, void* hip_stream) const {
         check(sshash_streaming_depth_device(m_h, device, d_bases, d_read_offsets, num_reads, total_bases, d_deltas, d_report, hip_stream));
     }
+    /* long reads cut into segments of `kmers_per_segment` k-mers for the run kernel (sshash_set_read_segments), opt-in: 0 = the default S,
+       SSHASH_SEGMENTS_OFF = never, which is where a new dictionary stands; `device_calls`: the device entry points segment as well. Same results either way. */
+    struct read_segments_setting {
+        uint64_t kmers_per_segment;   // S, or SSHASH_SEGMENTS_OFF
+        bool device_calls;
+        uint64_t segmented_launches;  // launches of the run kernel over a segment table so far
+    };
+    void set_read_segments(uint64_t kmers_per_segment = 0, bool device_calls = false) {
+        check(sshash_set_read_segments(m_h, kmers_per_segment, device_calls ? 1 : 0));
+    }
+    read_segments_setting read_segments() const {
+        read_segments_setting r{};
+        int device_calls = 0;
+        check(sshash_get_read_segments(m_h, &r.kmers_per_segment, &device_calls, &r.segmented_launches));
+        r.device_calls = device_calls != 0;
+        return r;
+    }
     void depth_finish_device(int device, uint32_t const* d_deltas, uint32_t* d_depth, void* hip_stream) const {
         check(sshash_depth_finish_device(m_h, device, d_deltas, d_depth, hip_stream));
     }

@@ -10,6 +10,7 @@ from typing import Callable, Iterable, Optional, Sequence, Union
 import numpy as np
 
 INVALID_U64 = 0xFFFFFFFFFFFFFFFF  # reference include/constants.hpp:5
+SEGMENTS_OFF = 0xFFFFFFFFFFFFFFFF  # SSHASH_SEGMENTS_OFF: Dictionary.set_read_segments(SEGMENTS_OFF) never cuts a read into segments
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libsshash_amd.so"
@@ -201,6 +202,8 @@ def _load() -> C.CDLL:
         "sshash_cover_string_counts": (C.c_int, [P, P, P, C.POINTER(C.c_uint64)]),
         "sshash_streaming_depth_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, P, P]),
         "sshash_depth_finish_device": (C.c_int, [P, C.c_int, P, P, P]),
+        "sshash_set_read_segments": (C.c_int, [P, C.c_uint64, C.c_int]),
+        "sshash_get_read_segments": (C.c_int, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
         "sshash_streaming_depth": (C.c_int, [P, P, P, C.c_uint64, P, C.POINTER(_Report)]),
         "sshash_streaming_depth_from_file": (C.c_int, [P, C.c_char_p, C.c_int, P, C.POINTER(_Report)]),
         "sshash_depth_string_sums_device": (C.c_int, [P, C.c_int, P, P, P, P]),
@@ -234,7 +237,7 @@ C_ABI_SYMBOLS = (
     "sshash_cover_words sshash_streaming_cover sshash_streaming_cover_device sshash_streaming_cover_from_file "
     "sshash_cover_string_counts sshash_cover_string_counts_device "
     "sshash_streaming_depth sshash_streaming_depth_device sshash_depth_finish_device sshash_streaming_depth_from_file "
-    "sshash_depth_string_sums sshash_depth_string_sums_device "
+    "sshash_depth_string_sums sshash_depth_string_sums_device sshash_set_read_segments sshash_get_read_segments "
     "sshash_streaming_lookup sshash_streaming_lookup_device sshash_sharded_lookup_device sshash_sharded_lookup_rccl "
     "sshash_route_packed_device sshash_route_bucket_device sshash_route_bucket_by_key_device sshash_route_combine_device "
     "sshash_iterate_packed sshash_iterate_packed_device sshash_check_device"
@@ -852,6 +855,20 @@ class Dictionary:
         deltas into depths."""
         _check(_load().sshash_streaming_depth_device(self._h, int(device), C.c_void_p(d_bases), C.c_void_p(d_read_offsets), int(num_reads),
                                                      int(total_bases), C.c_void_p(d_deltas), C.c_void_p(d_report), C.c_void_p(stream)))
+
+    def set_read_segments(self, kmers: Optional[int] = None, device_calls: bool = False) -> None:
+        """Long reads: the streaming calls cut a read of more than `kmers` k-mers into segments of that many, one lane of the run kernel
+        each, and give word for word what the uncut reads give (counters, rows, cover, depth). Opt-in: a new dictionary never segments. None or 0: the library's default S;
+        SEGMENTS_OFF: never (a piece that holds a read above 2^16 bases then takes the position-parallel pipeline); else 1 .. 2^30.
+        The host and file calls segment by themselves; the device calls only with `device_calls`. Never the runs, never a minimizer
+        shard. Not to be changed while a call on this dictionary is in flight."""
+        _check(_load().sshash_set_read_segments(self._h, 0 if kmers is None else int(kmers), 1 if device_calls else 0))
+
+    def read_segments(self) -> dict:
+        """-> {"kmers": S or SEGMENTS_OFF, "device_calls": bool, "segmented_launches": launches of the run kernel over a segment table}"""
+        kmers, device_calls, launches = C.c_uint64(0), C.c_int(0), C.c_uint64(0)
+        _check(_load().sshash_get_read_segments(self._h, C.byref(kmers), C.byref(device_calls), C.byref(launches)))
+        return {"kmers": int(kmers.value), "device_calls": bool(device_calls.value), "segmented_launches": int(launches.value)}
 
     def depth_finish_device(self, device: int, d_deltas: int, d_depth: int, stream: int = 0) -> None:
         """Device buffers: d_depth[i] = d_deltas[0] + .. + d_deltas[i] modulo 2^32 over num_kmers() uint32; d_depth may be d_deltas."""

@@ -274,6 +274,19 @@ sshash_status sshash_device_bytes(const sshash_dict* d, int device, uint64_t* by
     return guarded([&] { *bytes = d->eng->device_bytes(device); });
 }
 
+sshash_status sshash_set_read_segments(sshash_dict* d, uint64_t kmers_per_segment, int device_calls) {
+    if (!d) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] { d->eng->set_read_segments(kmers_per_segment, device_calls != 0); });
+}
+
+sshash_status sshash_get_read_segments(const sshash_dict* d, uint64_t* kmers_per_segment, int* device_calls, uint64_t* segmented_launches) {
+    if (!d) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (kmers_per_segment) *kmers_per_segment = d->eng->read_segment_kmers();
+    if (device_calls) *device_calls = d->eng->read_segments_device_calls() ? 1 : 0;
+    if (segmented_launches) *segmented_launches = d->eng->segmented_launches();
+    return SSHASH_OK;
+}
+
 sshash_status sshash_device_stats(const sshash_dict* d, int device, uint64_t out[16]) {
     if (!d || !out) return fail(SSHASH_ERR_ARGUMENT, "null argument");
     return guarded([&] { d->eng->device_stats(device, out); });

@@ -1,6 +1,7 @@
 // engine.hpp -- host-side owner of the device-resident dictionary replicas and kernel launchers.
 #pragma once
 
+#include <atomic>
 #include <memory>
 #include <mutex>
 #include <shared_mutex>
@@ -9,6 +10,7 @@
 
 #include "device_layout.hpp"
 #include "index.hpp"
+#include "segments.hpp"
 
 namespace sshash_amd {
 
@@ -162,8 +164,8 @@ public:
        (read r = bases[read_offsets[r] .. read_offsets[r+1])). Host buffers. */
     streaming_report streaming_query_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads) const;
     /* The same with one report PER READ: `rows` (host, n_reads x 6 words in the order of the device report, row r for read r; null:
-       the totals only) is overwritten; returns the totals. A piece that holds a read above 2^16 bases takes the position-parallel
-       pipeline, the others the run kernel; both give the same rows. */
+       the totals only) is overwritten; returns the totals. A piece that holds a read of more than S k-mers takes the run kernel over
+       segments (set_read_segments; off: above 2^16 bases the position-parallel pipeline), the others the run kernel; all give the same rows. */
     streaming_report streaming_query_per_read_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* rows,
                                                    cover_bitmaps const* cover = nullptr /* streaming_cover_host */,
                                                    depth_arrays const* depth = nullptr /* streaming_depth_host */) const;
@@ -173,12 +175,27 @@ public:
        per record (or holds reads longer than a piece): the caller then takes the sequential reader, `total` is untouched. */
     bool streaming_query_fastq_pieces(std::string const& filename, streaming_report& total) const;
     /* Device buffers, asynchronous; `d_report` receives 6 u64 counters (accumulated). */
+    /* `segment_kmers` (here and in the three calls like it below): 0 -- one lane walks one read --, S -- the reads are cut into segments
+       of S k-mers, one lane a segment, same results (streaming.hip, "long reads: SEGMENTS") --, or SEGMENTS_AS_SET: as
+       set_read_segments says for the device calls. */
+    static constexpr uint64_t SEGMENTS_AS_SET = ~uint64_t(0) - 1;  // (not SEGMENTS_OFF, which a caller may pass for 0)
     void streaming_query_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
-                                uint64_t total_bases, uint64_t* d_report, void* stream) const;
+                                uint64_t total_bases, uint64_t* d_report, void* stream, uint64_t segment_kmers = SEGMENTS_AS_SET) const;
     /* Device buffers, asynchronous, always the run kernel; `d_rows` (n_reads x 6 words) is overwritten, every row of it; `d_report`
        (nullable) is accumulated into. */
     void streaming_query_per_read_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
-                                         uint64_t total_bases, uint64_t* d_rows, uint64_t* d_report, void* stream) const;
+                                         uint64_t total_bases, uint64_t* d_rows, uint64_t* d_report, void* stream,
+                                         uint64_t segment_kmers = SEGMENTS_AS_SET) const;
+
+    /* Long reads (sshash_set_read_segments in include/sshash_amd.h): `kmers_per_segment` 0 = the default S, SEGMENTS_OFF = never -- the state of
+       a new dictionary --, else 1 .. 2^30 (throws otherwise). The host and file calls -- counters, rows, cover, depth -- send a piece that holds a read of more
+       than S k-mers through the run kernel over segments; `device_calls`: the four device entry points segment as well. Never on a
+       minimizer shard, never the run records. Not to be changed while a call is in flight. */
+    void set_read_segments(uint64_t kmers_per_segment, bool device_calls);
+    uint64_t read_segment_kmers() const { return m_segment_kmers; }  // S, or SEGMENTS_OFF
+    bool read_segments_device_calls() const { return m_segment_device_calls; }
+    uint64_t segmented_launches() const { return m_segmented_launches; }  // how often the run kernel was launched over a segment table
+    uint64_t host_segments() const;                                        // what the host calls segment with: S, or 0 (off, or a shard)
 
     /* The maximal runs of every read (sshash_streaming_runs[_device] in include/sshash_amd.h): a run is a search and the extensions
        behind it. Device buffers, asynchronous, always the run kernel: count -> scan -> write; `d_run_offsets` (n_reads + 1 words) is
@@ -195,10 +212,10 @@ public:
        of `d_cover` (ceil(num_kmers / 64) words) for k-mer id i, ORed into. Device buffers, asynchronous, always the run kernel, its cover
        form: one launch; `d_report` (nullable) is accumulated into. */
     void streaming_cover_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
-                                uint64_t* d_cover, uint64_t* d_report, void* stream) const;
+                                uint64_t* d_cover, uint64_t* d_report, void* stream, uint64_t segment_kmers = SEGMENTS_AS_SET) const;
     /* Host buffers, over all resident replicas, into the bitmaps `cover` keeps on them (the caller ORs those into its own when it is
-       done: cover_bitmaps::or_into); a piece that holds a read above 2^16 bases takes the position-parallel pipeline and marks from
-       its per-k-mer ids, which gives the same bits. Returns the totals. */
+       done: cover_bitmaps::or_into); a piece that holds a long read takes the run kernel over segments (set_read_segments; off: above 2^16
+       bases the position-parallel pipeline, which marks from its per-k-mer ids), which gives the same bits. Returns the totals. */
     streaming_report streaming_cover_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, cover_bitmaps const& cover) const;
     /* Covered k-mers per string out of a cover bitmap, device buffers, asynchronous: `d_counts` (num_strings words) and `d_total`
        (one word, nullable) are overwritten. */
@@ -209,13 +226,13 @@ public:
        32 bits, modulo 2^32, accumulated into). Device buffers, asynchronous, always the run kernel, its depth form: one launch; `d_report`
        (nullable) is accumulated into. Throws on a minimizer shard (streaming.hip). */
     void streaming_depth_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
-                                uint32_t* d_deltas, uint64_t* d_report, void* stream) const;
+                                uint32_t* d_deltas, uint64_t* d_report, void* stream, uint64_t segment_kmers = SEGMENTS_AS_SET) const;
     /* d_depth[i] = d_deltas[0] + .. + d_deltas[i] modulo 2^32 for the num_kmers ids; d_depth == d_deltas is allowed, no other overlap.
        Asynchronous; the tile sums (4 bytes per 4096 k-mers) are allocated and freed by the call, stream-ordered, from the replica's pool. */
     void depth_finish_device(int device, uint32_t const* d_deltas, uint32_t* d_depth, void* stream) const;
     /* Host buffers, over all resident replicas, into the deltas `depth` keeps on them (the caller adds the finished depths into its own
-       array when it is done: depth_arrays::add_into); a piece that holds a read above 2^16 bases takes the position-parallel pipeline
-       and is marked from its per-k-mer ids, which gives the same depths -- as does every piece of a minimizer shard. Returns the totals. */
+       array when it is done: depth_arrays::add_into); a piece that holds a long read takes the run kernel over segments (set_read_segments; off: above 2^16 bases the
+       position-parallel pipeline, marked from its per-k-mer ids), which gives the same depths -- every piece of a minimizer shard takes that pipeline. Returns the totals. */
     streaming_report streaming_depth_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, depth_arrays const& depth) const;
     /* The 64-bit sum of a depth array over the ids of every string, device buffers, asynchronous: `d_sums` (num_strings words) and
        `d_total` (one word, nullable) are overwritten. */
@@ -247,7 +264,11 @@ public:
     device_replica const* replica(int device) const;
 
 private:
+    uint64_t segments_for(uint64_t asked) const;  // (streaming.hip)
     std::shared_ptr<host_index> m_idx;
+    std::atomic<uint64_t> m_segment_kmers{SEGMENTS_OFF};  // (opt-in: a new dictionary takes the routes it always took)
+    std::atomic<bool> m_segment_device_calls{false};
+    mutable std::atomic<uint64_t> m_segmented_launches{0};
     /* to_device may run while other host threads query: readers share, the upload's final push_back is exclusive */
     mutable std::shared_mutex m_replicas_mutex;
     std::mutex m_upload_mutex;

@@ -2,7 +2,7 @@
 //
 // Reference: streaming_query<Dict,canonical>::lookup / seed (include/streaming_query.hpp:56-109,
 // 144-197) driven per read by src/query.cpp:78-108. The state machine is sequential inside a
-// read and independent across reads, so reads are the parallel dimension: a lane owns a read and
+// read and independent across reads, so reads are the parallel dimension (long reads are cut into segments first): a lane owns a read and
 // handles its EVENTS -- a seed (one point lookup, through the super-k-mer table when the replica has
 // one), or the run of extensions behind a hit, measured as a longest common prefix of the read and
 // the strings, 32 bases a step (streaming_run_kernel below). With the granule layout the reference's
@@ -27,6 +27,7 @@
 #include "hooks.hpp"
 #include "reads.hpp"
 #include "replica.hpp"
+#include "segments.hpp"
 
 namespace sshash_amd {
 
@@ -56,6 +57,13 @@ __device__ __forceinline__ hit_t seed_lookup(dict_view const& d, skew_part_dev c
 __device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     return v;
+}
+
+/* The continuation rule of a run (include/sshash_amd.h, "WHERE a read hits"), on the results of two neighbouring k-mers of a read: the
+   second, a positive k-mer, continues the run of the first iff that one is positive, lies in the same string and its id moved by its
+   orientation. The one statement of it: the classification, the run marks and the seams of a segmented launch all ask here. */
+__device__ __forceinline__ bool continues_run(uint64_t id_before, uint64_t sid_before, int ori_before, uint64_t id, uint64_t sid) {
+    return id_before != INVALID_U64 && sid_before == sid && id == id_before + uint64_t(int64_t(ori_before));
 }
 
 /* The counters of a workgroup (of 256) reach `report` with ONE set of atomics: the six counters share a cache line, and a set
@@ -308,11 +316,11 @@ enum : int { STREAM_TOTALS = 0, STREAM_ROWS = 1, STREAM_RUN_COUNTS = 2, STREAM_R
 
 /* the record of the run of `n` k-mers whose first (in read order) starts at base `at` of the packed reads and lies at offset `off` of
    the strings, in string `sid`: to place `cursor` of the records, unless that is past what the read or the caller has room for */
-__device__ __forceinline__ void run_record_store(dict_view const& d, run_sink const& sink, const uint64_t* __restrict__ offsets, uint64_t r,
+__device__ __forceinline__ void run_record_store(dict_view const& d, run_sink const& sink, const uint64_t* __restrict__ begins, uint64_t r,
                                                  uint64_t cursor, uint64_t at, uint64_t off, uint32_t sid, int ori, uint64_t n) {
     if (cursor >= sink.capacity || cursor >= sink.run_offsets[r + 1]) return;
     const uint64_t kmer_id = off - uint64_t(sid) * (d.k - 1), in_string = off - d.endpoints[sid];  // (store_result, lookup_device.hpp)
-    const uint32_t read_pos = uint32_t(at - offsets[r]), length = uint32_t(n) | (ori > 0 ? 0u : 0x80000000u);
+    const uint32_t read_pos = uint32_t(at - begins[r]), length = uint32_t(n) | (ori > 0 ? 0u : 0x80000000u);
     uint4* const rec = static_cast<uint4*>(sink.records) + 2 * cursor;
     rec[0] = make_uint4(uint32_t(kmer_id), uint32_t(kmer_id >> 32), sid, 0u);
     rec[1] = make_uint4(uint32_t(in_string), uint32_t(in_string >> 32), read_pos, length);
@@ -352,10 +360,13 @@ __device__ __forceinline__ void depth_mark_run(dict_view const& d, run_sink cons
     if (hi < d.num_kmers) (void)__hip_atomic_fetch_add(deltas + hi, ~0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+/* The reads are given by a begin and an end pointer: read r spans the bases [begins[r], ends[r]) of the packed copy. For whole reads the two
+   are `offsets` and `offsets + 1` -- the two words the kernel has always loaded --; for long reads cut into segments they are the two
+   arrays of the segment table, and a "read" of the kernel is a segment ("long reads: SEGMENTS" below). */
 template <int W, bool CANON, bool SK, int MODE>
 __global__ void __launch_bounds__(256, SSHASH_STREAM_WAVES)
 streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, const uint64_t* __restrict__ packed,
-                     const uint64_t* __restrict__ okay, const uint64_t* __restrict__ offsets, const uint64_t n_reads,
+                     const uint64_t* __restrict__ okay, const uint64_t* __restrict__ begins, const uint64_t* __restrict__ ends, const uint64_t n_reads,
                      const uint64_t reads_per_wave, const uint32_t move_out_every, uint64_t* __restrict__ report, const run_sink sink) {
     constexpr bool PER_READ = MODE == STREAM_ROWS, COUNT_RUNS = MODE == STREAM_RUN_COUNTS, RECORDS = MODE == STREAM_RUN_RECORDS, COVER = MODE == STREAM_COVER,
                    DEPTH = MODE == STREAM_DEPTH;
@@ -456,7 +467,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
             if constexpr (COVER) cover_mark_run(d, sink, off, hit_sid, ori, run + 1);
             if constexpr (DEPTH) depth_mark_run(d, sink, off, hit_sid, ori, run + 1);
             if constexpr (RECORDS) {  // (the hit lies a base before cur)
-                run_record_store(d, sink, offsets, wave_first + my_row, cursor, cur - 1, off, hit_sid, ori, run + 1);
+                run_record_store(d, sink, begins, wave_first + my_row, cursor, cur - 1, off, hit_sid, ori, run + 1);
                 ++cursor;
             } else if (run >> 15) {  // (past what the lane's 32-bit counter may take in one turn: 2^16 turns lie between two move-outs)
                 if constexpr (PER_READ) {  // (into the row at once, behind what the lane has counted for it so far)
@@ -495,8 +506,8 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
             const uint64_t rank = uint64_t(__popcll(wants & ((uint64_t(1) << lane) - 1)));
             if (want && rank < last - next) {
                 const uint64_t r = next + rank;
-                cur = offsets[r];
-                rd_end = offsets[r + 1];
+                cur = begins[r];
+                rd_end = ends[r];
                 if constexpr (PER_READ) {
                     uint64_t* const row = report + r * 6;
                     const uint64_t kmers = rd_end - cur >= k ? rd_end - cur - k + 1 : 0;
@@ -736,7 +747,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                 if constexpr (COUNT_RUNS) ++n_runs;
                 if constexpr (RECORDS) {
                     if (!pending) {  // a run of one
-                        run_record_store(d, sink, offsets, wave_first + my_row, cursor, cur, off, hit_sid, ori, 1);
+                        run_record_store(d, sink, begins, wave_first + my_row, cursor, cur, off, hit_sid, ori, 1);
                         ++cursor;
                     }
                 }
@@ -943,12 +954,151 @@ void inclusive_scan_u32(uint32_t const* in, uint32_t* out, uint64_t n, uint32_t*
     HIP_CHECK(hipGetLastError());
 }
 
+/* ==== long reads: SEGMENTS ==========================================================================================================
+   One lane walks one read, so a batch of few long reads is few lanes, and its time is that of its longest read. A k-mer is positive,
+   negative or invalid whatever lies around it; only whether a positive k-mer is a search or an extension depends on the k-mer before
+   it. So a read of K k-mers is cut into ceil(K / S) SEGMENTS of S k-mers (segments.hpp: neighbours overlap by k - 1 bases of the packed
+   copy, nothing is copied), the run kernel takes the segments for reads -- it is handed a begin and an end pointer, the offsets and the
+   offsets behind them for whole reads, the two arrays of the segment table here --, and the one thing that differs is put right
+   afterwards: a segment's first k-mer, when positive, was counted as a search; in the whole read it is an extension iff it continues
+   the run of the k-mer before it (continues_run) -- the SEAM is then JOINED. The seam kernel looks both k-mers up, one lane a seam, and
+   moves one count from searches to extensions for every joined seam. The cover is the same either way (OR), and so are the depth's
+   deltas: adjacent runs [lo, mid) and [mid, hi) leave what [lo, hi) leaves, the +1 and the -1 at mid cancel.
+   The table is built on the stream: the segments of every read, their exclusive scan (the index of every read's first segment), and
+   one lane per ENTRY that finds its read by bisection over those -- no lane's work grows with a read's length. The host sizes the table
+   from a bound (segment_bound); the entries past the true count are empty segments, which the run kernel takes for reads shorter than k. */
+__global__ void __launch_bounds__(256)
+stream_segment_counts_kernel(const uint64_t* __restrict__ offsets, const uint64_t n_reads, const uint32_t k, const uint64_t S, uint64_t* __restrict__ counts) {
+    const uint64_t r = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (r > n_reads) return;
+    counts[r] = r < n_reads ? segments_of_read(read_kmers(offsets[r + 1] - offsets[r], k), S) : 0;  // (the last: scanned into the number of segments)
+}
+
+constexpr uint64_t SEG_NO_READ = ~uint64_t(0);  // seg_read of an entry past the last segment
+
+__global__ void __launch_bounds__(256)
+stream_segment_fill_kernel(const uint64_t* __restrict__ offsets, const uint64_t n_reads, const uint64_t* __restrict__ first /* n_reads + 1 */, const uint32_t k,
+                           const uint64_t S, const uint64_t bound, uint64_t* __restrict__ seg_begin, uint64_t* __restrict__ seg_end, uint64_t* __restrict__ seg_read) {
+    const uint64_t g = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (g >= bound) return;
+    if (g >= first[n_reads]) {  // an empty segment
+        seg_begin[g] = seg_end[g] = 0;
+        seg_read[g] = SEG_NO_READ;
+        return;
+    }
+    uint64_t lo = 0, hi = n_reads - 1;  // my read: the largest r with first[r] <= g (every read has a segment: `first` goes strictly up)
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (first[mid] <= g) lo = mid;
+        else hi = mid - 1;
+    }
+    const uint64_t begin = offsets[lo], end = offsets[lo + 1], at = begin + (g - first[lo]) * S;
+    seg_begin[g] = at;
+    seg_end[g] = end - at > S + k - 1 ? at + S + k - 1 : end;
+    seg_read[g] = lo;
+}
+
+/* the complete seed() of the k-mer that starts at base p of the packed reads, as the run kernel does it for a lane without a table */
+template <int W, bool CANON>
+__device__ __forceinline__ hit_t seed_at(dict_view const& d, skew_part_dev const* __restrict__ skew, const uint64_t* __restrict__ packed, uint64_t p) {
+    const uint64_t i = p >> 5;
+    const uint32_t sh = 2 * (uint32_t(p) & 31u);
+    kmer_w<W> x = kmer_zero<W>();
+    x.w[0] = funnel_shr(packed[i], packed[i + 1], sh);
+    if constexpr (W == 2) x.w[1] = funnel_shr(packed[i + 1], packed[i + 2], sh);
+    x = kmer_take_chars<W>(x, d.k);
+    const kmer_w<W> x_rc = kmer_revcomp<W>(x, d.k);
+    return seed_lookup<W, CANON>(d, skew, x, x_rc, compute_minimizer<W>(x, d.k, d.m, d.hash_magic), compute_minimizer<W>(x_rc, d.k, d.m, d.hash_magic));
+}
+
+/* One lane a seam: entry g > 0 of the table whose read is that of entry g - 1 begins at a seam, base p = seg_begin[g]; the k-mers
+   that start at p - 1 and at p both lie in the read (segment g holds a k-mer, and p - 1 is a base of segment g - 1). joined[g]
+   (`joined` may be null) = both are valid and positive and the second continues the run of the first. With `report`: its searches
+   minus, its extensions plus the joined seams (modulo 2^64; the run kernel's own counts may arrive before or after), one pair of
+   atomics a workgroup. */
+template <int W, bool CANON>
+__global__ void __launch_bounds__(256)
+stream_seams_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, const uint64_t* __restrict__ packed, const uint64_t* __restrict__ okay,
+                    const uint64_t* __restrict__ seg_begin, const uint64_t* __restrict__ seg_read, const uint64_t* __restrict__ n_segments, const uint64_t bound,
+                    uint8_t* __restrict__ joined, uint64_t* __restrict__ report) {
+    __shared__ uint64_t wave_joined[4];
+    const uint64_t g = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    bool join = false;
+    if (g > 0 && g < bound && g < *n_segments && seg_read[g] == seg_read[g - 1]) {
+        const uint64_t p = seg_begin[g];
+        if (first_invalid_base(okay, p - 1, p + d.k) == p + d.k) {
+            const hit_t before = seed_at<W, CANON>(d, skew, packed, p - 1);
+            if (before.found) {
+                const hit_t here = seed_at<W, CANON>(d, skew, packed, p);
+                const uint64_t k1 = d.k - 1;  // (kmer_id = offset - string * (k - 1): run_record_store)
+                join = here.found && continues_run(before.kmer_offset - uint64_t(before.string_id) * k1, before.string_id, before.orientation,
+                                                   here.kmer_offset - uint64_t(here.string_id) * k1, here.string_id);
+            }
+        }
+    }
+    if (joined && g < bound) joined[g] = join ? 1 : 0;
+    if (!report) return;  // (uniform)
+    const uint64_t in_wave = wave_sum(join ? 1 : 0);
+    if ((threadIdx.x & 63u) == 0) wave_joined[threadIdx.x >> 6] = in_wave;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const unsigned long long J = wave_joined[0] + wave_joined[1] + wave_joined[2] + wave_joined[3];
+    if (J == 0) return;
+    atomicAdd(reinterpret_cast<unsigned long long*>(report + 4), 0ULL - J);
+    atomicAdd(reinterpret_cast<unsigned long long*>(report + 5), J);
+}
+
+/* The rows of the segments into the rows of their reads (zeroed by the caller): one lane a segment, its joined seam moved from its
+   searches to its extensions. The segments of a read are neighbours, thousands of them for a chromosome: the lanes of a wave first sum
+   over their stretches of equal read (a segmented sum, five steps of doubling: after the step of width o a lane holds its own and the
+   next 2 o - 1 of its stretch), and a stretch's first lane adds what is not zero -- at most one atomic per wave, read and counter. */
+__global__ void __launch_bounds__(256)
+stream_segment_rows_kernel(const uint64_t* __restrict__ seg_rows, const uint64_t* __restrict__ seg_read, const uint8_t* __restrict__ joined,
+                           const uint64_t* __restrict__ n_segments, const uint64_t bound, uint64_t* __restrict__ rows) {
+    const uint64_t g = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool has = g < bound && g < *n_segments;
+    const uint64_t read = has ? seg_read[g] : SEG_NO_READ;
+    uint64_t v[6] = {0, 0, 0, 0, 0, 0};
+    if (has) {
+#pragma unroll
+        for (uint32_t c = 0; c < 6; ++c) v[c] = seg_rows[6 * g + c];
+        const uint64_t j = joined[g];
+        v[4] -= j;
+        v[5] += j;
+    }
+    if (__ballot(has) == 0) return;  // (uniform)
+    const uint64_t read_before = __shfl_up(read, 1, 64);
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+        const bool same = __shfl_down(read, o, 64) == read && lane + o < 64;
+#pragma unroll
+        for (uint32_t c = 0; c < 6; ++c) {
+            const uint64_t further = __shfl_down(v[c], o, 64);
+            if (same) v[c] += further;
+        }
+    }
+    if (!has || (lane > 0 && read_before == read)) return;
+    unsigned long long* const row = reinterpret_cast<unsigned long long*>(rows + 6 * read);
+#pragma unroll
+    for (uint32_t c = 0; c < 6; ++c)
+        if (v[c]) atomicAdd(row + c, (unsigned long long)v[c]);
+}
+
+template <int W, bool CANON>
+void launch_seams(device_replica const* rep, dict_view const& d, hipStream_t s, uint64_t const* packed, uint64_t const* okay, uint64_t const* seg_begin,
+                  uint64_t const* seg_read, uint64_t const* n_segments, uint64_t bound, uint8_t* joined, uint64_t* report) {
+    hipLaunchKernelGGL((stream_seams_kernel<W, CANON>), dim3(uint32_t((bound + 255) / 256)), dim3(256), 0, s, d, rep->d_skew, packed, okay, seg_begin, seg_read,
+                       n_segments, bound, joined, report);
+    HIP_CHECK(hipGetLastError());
+}
+
 /* The one place that launches the run kernel: (k > 31, canonical, skew table) -> <W, CANON, SK>, in the form MODE. */
 template <int MODE>
 void launch_run_kernel(device_replica const* rep, dict_view const& d, dim3 grid, dim3 block, hipStream_t s, uint64_t const* packed, uint64_t const* okay,
-                       uint64_t const* offsets, uint64_t n_reads, uint64_t reads_per_wave, uint32_t move_out_every, uint64_t* report, run_sink const& sink) {
+                       uint64_t const* begins, uint64_t const* ends, uint64_t n_reads, uint64_t reads_per_wave, uint32_t move_out_every, uint64_t* report,
+                       run_sink const& sink) {
     auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, block, 0, s, d, rep->d_skew, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, report, sink);
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, d, rep->d_skew, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, report, sink);
         HIP_CHECK(hipGetLastError());
     };
     const bool wide = d.k > 31, canon = d.canonical, sk = d.sk.enabled;
@@ -969,23 +1119,54 @@ void launch_run_kernel(device_replica const* rep, dict_view const& d, dim3 grid,
 enum : int { RUNS_COUNT = 1, RUNS_WRITE = 2, RUNS_COVER = 4, RUNS_DEPTH = 8 };
 void launch_streaming_runs(device_replica const* rep, char const* bases, uint64_t const* offsets, uint64_t n_reads, uint64_t total_bases, uint64_t* report,
                            hipStream_t s, uint64_t* rows = nullptr /* per read: n_reads x 6 words; `report` may then be null */,
-                           run_sink sink = run_sink{nullptr, nullptr, 0}, int run_phases = 0) {
+                           run_sink sink = run_sink{nullptr, nullptr, 0}, int run_phases = 0,
+                           uint64_t S = 0 /* the reads cut into segments of S k-mers (totals, rows, cover, depth; never the run records) */) {
     dict_view const& d = rep->view;
+    const bool segmented = S != 0;
+    if (segmented && (run_phases & (RUNS_COUNT | RUNS_WRITE))) throw error(error_kind::internal, "run records are not segmented");
+    segment_layout L{};
+    if (segmented) {
+        L = segment_scratch(n_reads, total_bases, S, SCAN_TILE, rows != nullptr);
+        if (L.words == 0 || (L.bound + 255) / 256 >> 31) throw error(error_kind::argument, "too many segments for one call");
+    }
     /* two bits and a validity bit a base, in words of 32 and 64 bases; three words of slack behind the last base (a seed and a
        run read up to two words past their first) */
     const uint64_t packed_bytes = ((total_bases + 31) / 32 + 3) * 8, okay_bytes = ((total_bases + 63) / 64 + 2) * 8;
     /* (scratch the replica keeps for this stream, replica.hpp; two host threads that share a stream must not interleave their
        launch sequences, which share it) */
     const uint64_t runs_bytes = run_phases ? (scan_tiles(n_reads + 1) + 6) * 8 : 0;  // (the scan's tile sums; six counters nobody asked for)
+    uint64_t* const caller_report = report;
     std::lock_guard<std::mutex> sequence(rep->launch_mutex);
-    uint64_t* packed = static_cast<uint64_t*>(rep->read_scratch_for(s, packed_bytes + okay_bytes + runs_bytes));
+    uint64_t* packed = static_cast<uint64_t*>(rep->read_scratch_for(s, packed_bytes + okay_bytes + runs_bytes + L.words * 8));
     uint64_t* okay = packed + packed_bytes / 8;
     uint64_t* scan_sums = okay + okay_bytes / 8;
+    uint64_t* const seg = scan_sums + runs_bytes / 8;  // (segmented) the table, the segments' rows, the seam flags: segments.hpp
     if (total_bases) {
         const uint64_t lanes = (total_bases + 7) / 8;
         hipLaunchKernelGGL(stream_pack_kernel, dim3(uint32_t((lanes + 255) / 256)), dim3(256), 0, s, bases, total_bases,
                            reinterpret_cast<uint16_t*>(packed), reinterpret_cast<uint8_t*>(okay));
     }
+    /* what the lanes take for reads: the reads, or their segments -- every entry of the table, the empty ones behind the last included */
+    uint64_t const *begins = offsets, *ends = offsets + 1;
+    const uint64_t n_whole_reads = n_reads;
+    if (segmented) {
+        hipLaunchKernelGGL(stream_segment_counts_kernel, dim3(uint32_t((n_reads + 256) / 256)), dim3(256), 0, s, offsets, n_reads, d.k, S, seg + L.first);
+        exclusive_scan_u64(seg + L.first, n_reads + 1, seg + L.sums, s);
+        hipLaunchKernelGGL(stream_segment_fill_kernel, dim3(uint32_t((L.bound + 255) / 256)), dim3(256), 0, s, offsets, n_reads, seg + L.first, d.k, S, L.bound,
+                           seg + L.begin, seg + L.end, seg + L.read);
+        HIP_CHECK(hipGetLastError());
+        begins = seg + L.begin;
+        ends = seg + L.end;
+        n_reads = L.bound;
+    }
+    /* (segmented, and somebody wants searches and extensions apart: the joined seams; `joined`: the flags, for the rows) */
+    auto seams = [&](uint8_t* joined, uint64_t* into) {
+        uint64_t const* n_segments = seg + L.first + n_whole_reads;
+        if (d.k <= 31 && !d.canonical) launch_seams<1, false>(rep, d, s, packed, okay, begins, seg + L.read, n_segments, L.bound, joined, into);
+        else if (d.k <= 31) launch_seams<1, true>(rep, d, s, packed, okay, begins, seg + L.read, n_segments, L.bound, joined, into);
+        else if (!d.canonical) launch_seams<2, false>(rep, d, s, packed, okay, begins, seg + L.read, n_segments, L.bound, joined, into);
+        else launch_seams<2, true>(rep, d, s, packed, okay, begins, seg + L.read, n_segments, L.bound, joined, into);
+    };
     /* waves: as many as the chip holds at once -- a lane that finishes its read takes the next of its wave's share, and the longer the
        share, the better the lanes of a wave even out --, fewer for a small call (a piece of a query file: some 10^4 reads, many calls
        side by side on their own streams), down to two reads a lane */
@@ -998,33 +1179,46 @@ void launch_streaming_runs(device_replica const* rep, char const* bases, uint64_
     /* the cover, the depth and the counting form count the batch as they go: where nobody asked for the six counters they go into the scratch */
     auto totals = [&]() {
         if (report) return report;
-        uint64_t* spare = scan_sums + scan_tiles(n_reads + 1);
+        uint64_t* spare = scan_sums + scan_tiles(n_whole_reads + 1);
         HIP_CHECK(hipMemsetAsync(spare, 0, 6 * sizeof(uint64_t), s));
         return spare;
     };
     /* the row, counting and record forms keep a lane's read as a 31-bit index into its wave's share -- not the cover and totals forms */
     if ((rows || (run_phases & (RUNS_COUNT | RUNS_WRITE))) && reads_per_wave >> 31) throw error(error_kind::argument, "too many reads for one call");
     if (run_phases & RUNS_COVER) {
-        launch_run_kernel<STREAM_COVER>(rep, d, grid, block, s, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, totals(), sink);
+        launch_run_kernel<STREAM_COVER>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), sink);
+        if (segmented && caller_report) seams(nullptr, caller_report);  // (nobody reads the six counters: no seam is looked at)
     } else if (run_phases & RUNS_DEPTH) {
-        launch_run_kernel<STREAM_DEPTH>(rep, d, grid, block, s, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, totals(), sink);
+        launch_run_kernel<STREAM_DEPTH>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), sink);
+        if (segmented && caller_report) seams(nullptr, caller_report);
     } else if (run_phases) {
         if (run_phases & RUNS_COUNT) {
-            launch_run_kernel<STREAM_RUN_COUNTS>(rep, d, grid, block, s, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, totals(), sink);
+            launch_run_kernel<STREAM_RUN_COUNTS>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), sink);
             HIP_CHECK(hipMemsetAsync(sink.run_offsets + n_reads, 0, sizeof(uint64_t), s));
             exclusive_scan_u64(sink.run_offsets, n_reads + 1, scan_sums, s);
         }
         if (run_phases & RUNS_WRITE)
-            launch_run_kernel<STREAM_RUN_RECORDS>(rep, d, grid, block, s, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, nullptr, sink);
+            launch_run_kernel<STREAM_RUN_RECORDS>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, nullptr, sink);
     } else if (rows) {
-        launch_run_kernel<STREAM_ROWS>(rep, d, grid, block, s, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, rows, sink);
+        if (segmented) {  // a row per segment in the scratch, then the reads' rows out of those and the seams
+            uint8_t* const joined = reinterpret_cast<uint8_t*>(seg + L.joined);
+            launch_run_kernel<STREAM_ROWS>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, seg + L.rows, sink);
+            seams(joined, nullptr);
+            HIP_CHECK(hipMemsetAsync(rows, 0, n_whole_reads * 6 * sizeof(uint64_t), s));
+            hipLaunchKernelGGL(stream_segment_rows_kernel, dim3(uint32_t((L.bound + 255) / 256)), dim3(256), 0, s, seg + L.rows, seg + L.read, joined,
+                               seg + L.first + n_whole_reads, L.bound, rows);
+            HIP_CHECK(hipGetLastError());
+        } else {
+            launch_run_kernel<STREAM_ROWS>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, rows, sink);
+        }
         if (report) {
-            const uint32_t blocks = uint32_t(std::min<uint64_t>((n_reads + 255) / 256, 1024));
-            hipLaunchKernelGGL(stream_rows_sum_kernel, dim3(blocks), dim3(256), 0, s, rows, n_reads, report);
+            const uint32_t blocks = uint32_t(std::min<uint64_t>((n_whole_reads + 255) / 256, 1024));
+            hipLaunchKernelGGL(stream_rows_sum_kernel, dim3(blocks), dim3(256), 0, s, rows, n_whole_reads, report);
             HIP_CHECK(hipGetLastError());
         }
     } else {
-        launch_run_kernel<STREAM_TOTALS>(rep, d, grid, block, s, packed, okay, offsets, n_reads, reads_per_wave, move_out_every, report, sink);
+        launch_run_kernel<STREAM_TOTALS>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, report, sink);
+        if (segmented && report) seams(nullptr, report);
     }
 }
 
@@ -1057,20 +1251,43 @@ void streaming_runs_passes(engine const& eng, int device, char const* d_bases, u
 }  // namespace
 
 void engine::streaming_query_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
-                                    uint64_t total_bases, uint64_t* d_report, void* stream) const {
+                                    uint64_t total_bases, uint64_t* d_report, void* stream, uint64_t segment_kmers) const {
     device_replica const* rep = replica(device);
     if (n_reads == 0) return;
     device_guard guard(device);
     hipStream_t s = hipStream_t(stream);
     total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
     if (total_bases == 0) return;
-    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s);
+    const uint64_t S = segments_for(segment_kmers);
+    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, run_sink{nullptr, nullptr, 0}, 0, S);
+    if (S) ++m_segmented_launches;  // (counted once the launches are made: a call that threw is none)
 }
 
-/* One report per read, by the run kernel whatever the reads' lengths (a caller with device buffers has cut its batch itself, as with
-   streaming_query_device). Every row is written: also when no base is there to look at. */
+/* The setting of sshash_set_read_segments (engine.hpp). */
+void engine::set_read_segments(uint64_t kmers_per_segment, bool device_calls) {
+    if (!segment_setting_valid(kmers_per_segment)) throw error(error_kind::argument, "kmers_per_segment is neither 0, SSHASH_SEGMENTS_OFF nor in 1 .. 2^30");
+    m_segment_kmers = kmers_per_segment ? kmers_per_segment : SEGMENT_KMERS_DEFAULT;
+    m_segment_device_calls = device_calls;
+}
+
+/* What a host call cuts its long reads into: the setting, except on a minimizer shard -- its run kernel follows a run through k-mers
+   it does not own, which a seed at a seam would miss: a shard never segments. 0: no segments. */
+uint64_t engine::host_segments() const {
+    const uint64_t S = m_segment_kmers;
+    return S == SEGMENTS_OFF || m_idx->num_shards > 1 ? 0 : S;
+}
+
+/* What a device entry point launches with: what its caller inside the library says (0, or the S of a piece that holds a long read;
+   SEGMENTS_OFF is 0 as well), or -- SEGMENTS_AS_SET, the C ABI -- the setting where it was made for the device calls as well. */
+uint64_t engine::segments_for(uint64_t asked) const {
+    if (asked == SEGMENTS_AS_SET) return m_segment_device_calls ? host_segments() : 0;
+    return asked == SEGMENTS_OFF ? 0 : asked;
+}
+
+/* One report per read, by the run kernel whatever the reads' lengths (one lane a read, or -- segment_kmers -- one lane a segment).
+   Every row is written: also when no base is there to look at. */
 void engine::streaming_query_per_read_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
-                                             uint64_t total_bases, uint64_t* d_rows, uint64_t* d_report, void* stream) const {
+                                             uint64_t total_bases, uint64_t* d_rows, uint64_t* d_report, void* stream, uint64_t segment_kmers) const {
     device_replica const* rep = replica(device);
     if (n_reads == 0) return;
     if (!d_rows) throw error(error_kind::argument, "per-read output pointer is null");
@@ -1081,7 +1298,9 @@ void engine::streaming_query_per_read_device(int device, char const* d_bases, ui
         HIP_CHECK(hipMemsetAsync(d_rows, 0, n_reads * 6 * sizeof(uint64_t), s));
         return;
     }
-    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, d_rows);
+    const uint64_t S = segments_for(segment_kmers);
+    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, d_rows, run_sink{nullptr, nullptr, 0}, 0, S);
+    if (S) ++m_segmented_launches;  // (counted once the launches are made: a call that threw is none)
 }
 
 /* The runs of every read (sshash_streaming_runs_device): count -> scan -> write, always the run kernel. */
@@ -1097,7 +1316,7 @@ void engine::streaming_runs_device(int device, char const* d_bases, uint64_t con
 
 /* Which k-mers of the dictionary the reads hold (sshash_streaming_cover_device): the cover form of the run kernel, one launch. */
 void engine::streaming_cover_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
-                                    uint64_t* d_cover, uint64_t* d_report, void* stream) const {
+                                    uint64_t* d_cover, uint64_t* d_report, void* stream, uint64_t segment_kmers) const {
     device_replica const* rep = replica(device);  // (not resident: that error first)
     if (n_reads == 0) return;
     if (!d_cover) throw error(error_kind::argument, "cover pointer is null");
@@ -1105,13 +1324,15 @@ void engine::streaming_cover_device(int device, char const* d_bases, uint64_t co
     hipStream_t s = hipStream_t(stream);
     total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
     if (total_bases == 0) return;  // empty reads only: no k-mer
-    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, run_sink{nullptr, d_cover, 0}, RUNS_COVER);
+    const uint64_t S = segments_for(segment_kmers);
+    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, run_sink{nullptr, d_cover, 0}, RUNS_COVER, S);
+    if (S) ++m_segmented_launches;  // (counted once the launches are made: a call that threw is none)
 }
 
 /* How often the reads hold each k-mer of the dictionary (sshash_streaming_depth_device): the depth form of the run kernel, one launch,
    into the deltas; depth_finish_device turns deltas into depths. */
 void engine::streaming_depth_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
-                                    uint32_t* d_deltas, uint64_t* d_report, void* stream) const {
+                                    uint32_t* d_deltas, uint64_t* d_report, void* stream, uint64_t segment_kmers) const {
     device_replica const* rep = replica(device);  // (not resident: that error first)
     if (n_reads == 0) return;
     if (!d_deltas) throw error(error_kind::argument, "deltas pointer is null");
@@ -1122,7 +1343,9 @@ void engine::streaming_depth_device(int device, char const* d_bases, uint64_t co
     hipStream_t s = hipStream_t(stream);
     total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
     if (total_bases == 0) return;  // empty reads only: no k-mer
-    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, run_sink{nullptr, d_deltas, 0}, RUNS_DEPTH);
+    const uint64_t S = segments_for(segment_kmers);
+    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, run_sink{nullptr, d_deltas, 0}, RUNS_DEPTH, S);
+    if (S) ++m_segmented_launches;  // (counted once the launches are made: a call that threw is none)
 }
 
 void engine::depth_finish_device(int device, uint32_t const* d_deltas, uint32_t* d_depth, void* stream) const {
@@ -1309,8 +1532,7 @@ stream_classify_kernel(const uint8_t* __restrict__ flags, const uint64_t total_b
                 if (id[j + 1] == INVALID_U64) {
                     ++c_negative;
                 } else {
-                    const bool extension = !(f[j + 1] & SQ_FIRST) && (f[j] & SQ_VALID) && id[j] != INVALID_U64 && sid[j] == sid[j + 1] &&
-                                           id[j + 1] == id[j] + uint64_t(int64_t(ori[j]));
+                    const bool extension = !(f[j + 1] & SQ_FIRST) && (f[j] & SQ_VALID) && continues_run(id[j], sid[j], ori[j], id[j + 1], sid[j + 1]);
                     c_extension += extension;
                     c_search += !extension;
                 }
@@ -1342,8 +1564,7 @@ stream_classify_rows_kernel(const uint8_t* __restrict__ flags, const uint64_t to
             negative = true;
         } else {
             if (!(f & SQ_FIRST) && p > 0 && (flags[p - 1] & SQ_VALID)) {  // (as stream_classify_kernel)
-                const uint64_t before = kmer_id[p - 1];
-                extension = before != INVALID_U64 && string_id[p - 1] == string_id[p] && id == before + uint64_t(int64_t(orientation[p - 1]));
+                extension = continues_run(kmer_id[p - 1], string_id[p - 1], orientation[p - 1], id, string_id[p]);
             }
             search = !extension;
         }
@@ -1396,8 +1617,7 @@ stream_run_marks_kernel(const uint8_t* __restrict__ flags, const uint64_t total_
             if (id != INVALID_U64) {
                 bool extension = false;
                 if (!(f & SQ_FIRST) && p > 0 && (flags[p - 1] & SQ_VALID)) {  // (as stream_classify_kernel)
-                    const uint64_t before = kmer_id[p - 1];
-                    extension = before != INVALID_U64 && string_id[p - 1] == string_id[p] && id == before + uint64_t(int64_t(orientation[p - 1]));
+                    extension = continues_run(kmer_id[p - 1], string_id[p - 1], orientation[p - 1], id, string_id[p]);
                 }
                 mark = extension ? RUN_CONTINUES : RUN_HEAD;
             }
@@ -1815,8 +2035,9 @@ piece_cuts cut_lane_pieces(uint64_t const* read_offsets, uint64_t n_reads) {
                       test_hook_u64("stream_piece_reads", uint64_t(1) << 20, 1, uint64_t(1) << 20));  // (tests: seams between pieces inside a small batch)
 }
 
-/* One lane walks one read: a read of megabases (a contig, a multiline FASTA record) would keep a single lane busy for minutes; a
-   piece that holds such a read goes through the position-parallel pipeline, which gives the same results. */
+/* One lane walks one read: a read of megabases (a contig, a multiline FASTA record) would keep a single lane busy for minutes. Where the
+   reads are not cut into segments (SSHASH_SEGMENTS_OFF, a minimizer shard, the run records) a piece that holds such a read goes through
+   the position-parallel pipeline, which gives the same results. */
 bool holds_long_read(uint64_t const* offsets, uint64_t n_reads) {
     constexpr uint64_t LONG_READ_BASES = uint64_t(1) << 16;
     for (uint64_t i = 0; i < n_reads; ++i)
@@ -1824,17 +2045,27 @@ bool holds_long_read(uint64_t const* offsets, uint64_t n_reads) {
     return false;
 }
 
+/* With segments of S k-mers: a piece that holds a read of more than S k-mers takes the run kernel over segments (returns S), a piece of
+   short reads exactly the launches it took before there were segments (returns 0). */
+uint64_t piece_segments(uint64_t const* offsets, uint64_t n_reads, uint32_t k, uint64_t S) {
+    if (S == 0) return 0;
+    for (uint64_t i = 0; i < n_reads; ++i)
+        if (read_kmers(offsets[i + 1] - offsets[i], k) > S) return S;
+    return 0;
+}
+
 /* the six counters of one staged piece, added to d_report */
-void piece_totals(engine const& eng, int device, bool long_read, char const* d_bases, uint64_t const* d_offsets, uint64_t n_reads, uint64_t n_bases,
-                  uint64_t* d_report, hipStream_t s) {
-    if (long_read) eng.streaming_lookup_device(device, d_bases, d_offsets, n_reads, n_bases, result_view{}, d_report, s);
-    else eng.streaming_query_device(device, d_bases, d_offsets, n_reads, n_bases, d_report, s);
+void piece_totals(engine const& eng, int device, bool long_read, uint64_t segments, char const* d_bases, uint64_t const* d_offsets, uint64_t n_reads,
+                  uint64_t n_bases, uint64_t* d_report, hipStream_t s) {
+    if (long_read && !segments) eng.streaming_lookup_device(device, d_bases, d_offsets, n_reads, n_bases, result_view{}, d_report, s);
+    else eng.streaming_query_device(device, d_bases, d_offsets, n_reads, n_bases, d_report, s, segments);
 }
 
 /* a piece as a lane hands it to the call's own work: uploaded, nothing launched yet */
 struct staged_piece {
     uint64_t index, first, n, nb;  // which piece; its first read, its reads, its bases
     bool long_read;
+    uint64_t segments;  // S: the piece holds a read of more than S k-mers and the call cuts such reads into segments; 0 otherwise
     int device;
     hipStream_t s;
     char const* d_bases;
@@ -1857,6 +2088,7 @@ streaming_report run_piece_lanes(engine const& eng, char const* bases, uint64_t 
     const uint64_t lane_bytes = extra_bytes ? extra_at + extra_bytes : report_at + 6 * sizeof(uint64_t);
 
     std::atomic<uint64_t> next{0};
+    const uint64_t host_S = eng.host_segments();
     const uint64_t hw = std::max(1u, std::thread::hardware_concurrency());
     const uint64_t lanes_per_device = std::min<uint64_t>({(num_pieces + G - 1) / G, 8, std::max<uint64_t>(1, hw / G)});
     std::vector<int> lane_devs(lanes_per_device * G);
@@ -1887,6 +2119,7 @@ streaming_report run_piece_lanes(engine const& eng, char const* bases, uint64_t 
             HIP_CHECK(hipMemcpyAsync(dp, hp, (p.n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p.s));
             HIP_CHECK(hipMemcpyAsync(dp + bases_at, hp + bases_at, p.nb, hipMemcpyHostToDevice, p.s));
             p.long_read = holds_long_read(offsets, p.n);
+            p.segments = piece_segments(offsets, p.n, eng.index().k, host_S);
             body(p);
         }
         partial[li] = read_back(p.d_report, p.s);
@@ -1913,20 +2146,21 @@ streaming_report engine::streaming_query_per_read_host(char const* bases, uint64
     const piece_cuts pieces = cut_lane_pieces(read_offsets, n_reads);
     const uint64_t row_bytes = 6 * sizeof(uint64_t);
     return run_piece_lanes(*this, bases, read_offsets, pieces, rows ? pieces.max_reads * row_bytes : 0, [&](staged_piece const& p) {
+        const bool per_kmer = p.long_read && !p.segments;  // (no segments: a long read's piece takes the position-parallel pipeline)
         if (rows) {
             uint64_t* d_rows = reinterpret_cast<uint64_t*>(p.d_extra);
-            if (p.long_read || p.nb == 0) HIP_CHECK(hipMemsetAsync(d_rows, 0, p.n * row_bytes, p.s));  // (the classify pass adds to its rows; no bases: no kernel at all)
-            if (p.long_read) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, d_rows);
-            else if (p.nb) streaming_query_per_read_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, d_rows, p.d_report, p.s);
+            if (per_kmer || p.nb == 0) HIP_CHECK(hipMemsetAsync(d_rows, 0, p.n * row_bytes, p.s));  // (the classify pass adds to its rows; no bases: no kernel at all)
+            if (per_kmer) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, d_rows);
+            else if (p.nb) streaming_query_per_read_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, d_rows, p.d_report, p.s, p.segments);
             HIP_CHECK(hipMemcpyAsync(p.h_extra, d_rows, p.n * row_bytes, hipMemcpyDeviceToHost, p.s));  // (through the lane's pinned block: the caller's array is pageable)
         } else if (cover) {
-            if (p.long_read) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, nullptr, nullptr, cover->on(p.device));
-            else if (p.nb) streaming_cover_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, cover->on(p.device), p.d_report, p.s);
+            if (per_kmer) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, nullptr, nullptr, cover->on(p.device));
+            else if (p.nb) streaming_cover_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, cover->on(p.device), p.d_report, p.s, p.segments);
         } else if (depth) {
-            if (p.long_read || m_idx->num_shards > 1) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, nullptr, nullptr, nullptr, depth->on(p.device));
-            else if (p.nb) streaming_depth_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, depth->on(p.device), p.d_report, p.s);
+            if (per_kmer || m_idx->num_shards > 1) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, nullptr, nullptr, nullptr, depth->on(p.device));
+            else if (p.nb) streaming_depth_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, depth->on(p.device), p.d_report, p.s, p.segments);
         } else {
-            piece_totals(*this, p.device, p.long_read, p.d_bases, p.d_offsets, p.n, p.nb, p.d_report, p.s);
+            piece_totals(*this, p.device, p.long_read, p.segments, p.d_bases, p.d_offsets, p.n, p.nb, p.d_report, p.s);
         }
         HIP_CHECK(hipStreamSynchronize(p.s));
         if (rows) std::memcpy(rows + 6 * p.first, p.h_extra, p.n * row_bytes);
@@ -2076,7 +2310,7 @@ streaming_report engine::streaming_runs_host(char const* bases, uint64_t const* 
         const run_sink counting{d_counts, nullptr, 0};
         if (p.nb == 0) HIP_CHECK(hipMemsetAsync(d_counts, 0, (p.n + 1) * sizeof(uint64_t), p.s));
         else if (p.long_read) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, nullptr, &counting);
-        else streaming_runs_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, d_counts, nullptr, 0, p.d_report, p.s);
+        else streaming_runs_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, d_counts, nullptr, 0, p.d_report, p.s);  // (run records are never segmented)
         HIP_CHECK(hipMemcpyAsync(p.h_extra, d_counts, (p.n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, p.s));
         HIP_CHECK(hipStreamSynchronize(p.s));
         const uint64_t total = counts[p.n];
@@ -2134,6 +2368,7 @@ bool engine::streaming_query_fastq_pieces(std::string const& filename, streaming
     for (uint64_t li = 0; li < lane_devs.size(); ++li) lane_devs[li] = devs[li % G];
 
     std::atomic<uint64_t> next{0};
+    const uint64_t host_S = host_segments();
     std::atomic<bool> give_up{false};  // a lane threw, or a piece did not fit: the others take no more pieces
     std::vector<fastq_pieces::parsed> seen(num_pieces);
     std::vector<streaming_report> partial(lane_devs.size());
@@ -2157,7 +2392,7 @@ bool engine::streaming_query_fastq_pieces(std::string const& filename, streaming
             if (got.num_reads == 0) continue;
             HIP_CHECK(hipMemcpyAsync(dp, hp, (got.num_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
             HIP_CHECK(hipMemcpyAsync(dp + bases_at, hp + bases_at, got.num_bases, hipMemcpyHostToDevice, s));
-            piece_totals(*this, device, holds_long_read(offsets, got.num_reads), dp + bases_at, reinterpret_cast<uint64_t const*>(dp), got.num_reads, got.num_bases, d_report, s);
+            piece_totals(*this, device, holds_long_read(offsets, got.num_reads), piece_segments(offsets, got.num_reads, k, host_S), dp + bases_at, reinterpret_cast<uint64_t const*>(dp), got.num_reads, got.num_bases, d_report, s);
             HIP_CHECK(hipStreamSynchronize(s));  // the pinned block is parsed into again
         }
         partial[li] = read_back(d_report, s);
