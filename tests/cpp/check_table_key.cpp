@@ -1,6 +1,7 @@
 // check_table_key.cpp -- host-side properties of the super-k-mer table's key function (csrc/device_layout.hpp):
 // a k-mer and its reverse complement must elect the same m-mer occurrence, or the table could not serve both
-// strands with one slot. Plain g++, no GPU. Prints "OK <checked> <ties>" or the first counter-example.
+// strands with one slot. The second number of a case is the length of the table's KEYS (sk_table_m), which need not be the dictionary's m.
+// Plain g++, no GPU. Prints "OK <checked> <ties>" or the first counter-example.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -121,7 +122,9 @@ int main() {
     std::mt19937_64 rng(12345);
     uint64_t ties = 0, checked = 0;
     const uint32_t cases[][2] = {{31, 21}, {31, 13}, {15, 7}, {21, 21}, {31, 1}, {63, 25}, {63, 31}, {47, 20}, {33, 5},
-                                 {15, 4}, {31, 6}, {31, 12}, {31, 30}, {33, 12}, {35, 30}};  // even m
+                                 {15, 4}, {31, 6}, {31, 12}, {31, 30}, {33, 12}, {35, 30},  // even m
+                                 /* a key length that is not the dictionary's m nor the default (SSHASH_AMD_SK_M; tests/gpu_forms_worker.py: KEY_POINTS) */
+                                 {31, 25}, {31, 17}, {31, 14}, {21, 20}, {15, 14}, {33, 31}, {47, 31}, {63, 12}, {63, 20}, {63, 17}};
     for (auto const& c : cases) {
         const uint64_t trials = 200000;
         const uint64_t before = ties;

@@ -205,14 +205,18 @@ def substituted(kmers, k, W, rng, limit=400):
     return pack(out, W), np.repeat(pick, k)
 
 
-def make_point(k, m, canonical, exe, scratch):
+def make_point(k, m, canonical, exe, scratch, extend=None, key_length=None):
+    """`extend`: strings -> the strings with more behind them (tests/gpu_forms_worker.py adds long ones); `key_length`: the length of
+    the table's keys where it is not the default (SSHASH_AMD_SK_M), for what is measured about table-key ties"""
     from conftest import Case
     from oracle import oracle as O
     from test_gpu_streaming import _synthetic_reads
 
     seqs, planted = make_sequences(k, m, exe)
+    if extend is not None:
+        seqs = extend(seqs)  # (behind the others: `planted` holds indices)
     pt = Point()
-    pt.k, pt.m, pt.canonical, pt.W, pt.key_length, pt.magic = k, m, canonical, 1 if k <= 31 else 2, key_length_of(k, m), O.xxh64_u64(1, 0)
+    pt.k, pt.m, pt.canonical, pt.W, pt.key_length, pt.magic = k, m, canonical, 1 if k <= 31 else 2, key_length or key_length_of(k, m), O.xxh64_u64(1, 0)
     pt.sequences, pt.planted = seqs, planted
     pt.case = case = Case(f"even_k{k}_m{m}_{int(canonical)}", seqs, k, m, canonical, scratch)
     W, n = pt.W, case.gt.num_kmers

@@ -1,0 +1,462 @@
+#!/usr/bin/env python
+"""Worker of tests/test_gpu_forms_sweep.py, and the input generator it shares with tests/test_forms_sweep_inputs.py: EVERY output form
+of the streaming run kernel -- the batch counters, the per-read rows, the run records, the cover bitmap, the depth deltas -- and the
+segment machinery for long reads, at one point (k, m, length of the table's keys, replica layer), regular then canonical. The run forms
+do arithmetic the per-k-mer forms never do (kmer_id = offset - string_id * (k - 1), the first id of a backward run, a segment's end at
++ S + k - 1, the first invalid base of a window, the funnel shift of a two-word seed), and the length of the table's keys is a parameter
+of its own (`hashed`, sk_key_persists); the points of the sweep are where these change: k = 33 (one base in the second word), m = k,
+m < 12, even m (a self-complementary m-mer ties the two strands), a key length on either side of m.
+
+One worker process = one point (the replica layer and the key length are read from the environment when a replica is uploaded; the
+worker sets nothing itself and asserts from device_stats() that the setting took). On the CPU first (gate): the reads hold every kind
+of read, run and seam the kernels have a branch for, and the ids of the oracle's restated state machine equal GroundTruth.lookup of
+every valid k-mer of every read -- two references, neither of them the library's GPU path. Then every form through the host and the
+device entry point, uncut, cut into segments of 1, 7 and 64 k-mers, and uncut again; all comparisons exact. Prints one JSON line; any
+mismatch is an assertion error.
+
+    python tests/gpu_forms_worker.py <k> <m> <key_length or 0> <layer: table|directory> <table_keys binary> <scratch dir> [--cpu-only]"""
+from __future__ import annotations
+
+import functools
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "tests")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+import numpy as np
+
+from gpu_even_m_worker import POINTS as EVEN_POINTS
+from gpu_even_m_worker import FLOOR, assert_floors, canonical_strings, key_length_of, kmers_of, make_point
+from gpu_per_read_worker import COLUMNS, random_dna, revcomp, synthetic_reads
+from gpu_routing_worker import revcomp as packed_revcomp
+
+INVALID = np.uint64(0xFFFFFFFFFFFFFFFF)
+ODD_POINTS = [(21, 11), (23, 23), (27, 9), (29, 17), (31, 7), (31, 27), (31, 31), (33, 13), (35, 31), (41, 21), (47, 15),
+              (55, 19), (61, 29), (63, 31)]  # tests/test_gpu_km_sweep.py: POINTS
+KEY_POINTS = [(31, 21, 25), (31, 21, 17), (31, 13, 12), (31, 13, 30), (31, 20, 14), (21, 11, 20), (15, 7, 14), (33, 13, 31), (47, 15, 31),
+              (63, 25, 12), (63, 31, 20), (63, 17, 17)]  # (k, m, SSHASH_AMD_SK_M)
+DIRECTORY_POINTS = [(23, 23), (31, 12), (33, 13), (35, 30), (55, 19), (63, 16)]
+MATRIX = ([(k, m, 0, "table") for k, m in ODD_POINTS + EVEN_POINTS] + [(k, m, L, "table") for k, m, L in KEY_POINTS]
+          + [(k, m, 0, "directory") for k, m in DIRECTORY_POINTS])  # (k, m, key length or 0, layer): one worker each
+LAYERS = {  # name -> (environment, what device_stats() must show)
+    "table": ({}, lambda st: st["sk_slots"] > 0),
+    "directory": ({"SSHASH_AMD_SKTABLE": "0", "SSHASH_AMD_DIRECTORY": "1"}, lambda st: st["sk_slots"] == 0 and st["directory_sectors"] > 0),
+}
+SEGMENT_SIZES = (1, 7, 64)
+LONG_STRINGS, LONG_LENGTHS = 12, (800, 1501)  # reads of 300 - 600 bases are cut out of these at every k
+REPEATS = 4096
+# a planted m-mer needs k - m >= ROOM bases around it: conftest.skewed_sequences redraws the flanks of every copy until its k-mers are new, and a
+# hundred copies of one m-mer cannot be a hundred distinct k-mers at every place in the window when 4^(k - m) is small (it never returns at k - m = 1)
+ROOM = 4
+JUMP = 12  # k-mers on either side of the jump of a jump read
+# (k, m, key length or 0) of the table layer where device_stats()["sk_heavy_kmers"] > 0: k-mers under a key with more occurrences than
+# the table lists, answered by the complete path. Found on the first run on an MI355X and held since.
+HEAVY = {(21, 11, 0), (27, 9, 0), (29, 17, 0), (31, 7, 0), (31, 27, 0), (33, 13, 0), (35, 31, 0), (41, 21, 0), (47, 15, 0), (61, 29, 0), (63, 31, 0),
+         (15, 4, 0), (31, 6, 0), (31, 8, 0), (47, 20, 0), (63, 30, 0), (31, 21, 25), (31, 21, 17), (31, 13, 12), (31, 20, 14), (47, 15, 31), (63, 25, 12),
+         (63, 31, 20)}
+
+
+def environment_of(key_length, layer):
+    """what the test puts into the worker's environment (every other SSHASH_AMD_* setting is taken out first)"""
+    env = dict(LAYERS[layer][0])
+    if key_length:
+        env["SSHASH_AMD_SK_M"] = str(key_length)
+    return env
+
+
+# ---- the dictionary's strings ----------------------------------------------------------------------------------------------------------
+def _adder(seqs, k):
+    """-> add(t): appends t to seqs if its canonical k-mers are pairwise distinct and new (no dictionary may hold a k-mer twice)"""
+    seen = set()
+    for s in seqs:
+        seen |= canonical_strings(s, k)
+
+    def add(t):
+        mine = canonical_strings(t, k)
+        if len(mine) != len(t) - k + 1 or (mine & seen):
+            return False
+        seen.update(mine)
+        seqs.append(t)
+        return True
+
+    return add
+
+
+def jump_string(k, seed):
+    """-> (A + R + B + R + C, where the two R start): one string that holds the same k - 1 bases R twice. Its k-mers are distinct (the bases
+    around the two R differ), but a read can step from the k-mer that ends with the first R to the k-mer that starts with the second:
+    two neighbours in the read, both in the dictionary and in the same string, that are NOT neighbours in the string -- the one place
+    where whether a k-mer extends a run is decided by the ids and not by whether the k-mer before it was found"""
+    rng = np.random.default_rng(seed + 77)
+    while True:
+        a, r, b, c = (random_dna(rng, n) for n in (k + JUMP, k - 1, k + JUMP, k + JUMP))
+        if len({a[-1], b[-1]}) == 2 and len({b[0], c[0]}) == 2:  # (or the k-mers around the two R were the same)
+            return a + r + b + r + c, (len(a), len(a) + len(r) + len(b))
+
+
+def jump_reads(k, seed):
+    """the reads that jump inside jump_string: forward from the first R to behind the second, back from the second to behind the first,
+    and both on the other strand"""
+    s, (first, second) = jump_string(k, seed)
+    there = s[first - JUMP:first + k - 1] + s[second + k - 1:second + k - 1 + JUMP]
+    back = s[second - JUMP:second + k - 1] + s[first + k - 1:first + k - 1 + JUMP]
+    return [there, back, revcomp(there), revcomp(back)]
+
+
+def with_long_strings(seqs, k, seed):
+    """seqs and, behind them, LONG_STRINGS random strings of 800 - 1500 bases and the jump string"""
+    rng = np.random.default_rng(seed)
+    seqs = list(seqs)
+    add = _adder(seqs, k)
+    for n in rng.integers(LONG_LENGTHS[0], LONG_LENGTHS[1], LONG_STRINGS):
+        while not add(random_dna(rng, int(n))):
+            pass
+    assert add(jump_string(k, seed)[0]), "the jump string holds a k-mer twice, or one of another string"
+    return seqs
+
+
+_ODD = {}
+
+
+@functools.lru_cache(maxsize=None)
+def _skewed(k, m, n_heavy, n_mid):
+    from conftest import skewed_sequences
+
+    return skewed_sequences(k, m, seed=k + m, n_heavy=n_heavy, n_mid=n_mid, n_plain=0)
+
+
+def odd_sequences(k, m, key_length):
+    """an odd m: random strings of ragged lengths, the shortest exactly one k-mer long (tests/test_gpu_km_sweep.py, at the size of the
+    even-m inputs), the long strings, and what conftest.skewed_sequences plants where it applies: m-mers that win the minimizer election
+    of any window (MIDLOAD and HEAVYLOAD buckets; m < k, or the copies of one m-mer were copies of one k-mer) and m-mers that win the
+    table's key election (keys with a list of occurrences, and with more than the table lists) -- the latter again at the length of the
+    table's keys where that is not m. Deterministic, the same for both flavours."""
+    if (k, m, key_length) in _ODD:
+        return _ODD[(k, m, key_length)]
+    rng = np.random.default_rng(9000 * k + m)
+    seqs = []
+    add = _adder(seqs, k)
+    target = 1500 if k <= 15 else 3500
+    for n in [k, k + 1, 2 * k - 1, 2 * k] + [int(x) for x in rng.integers(k, 6 * k, max(12, target // (5 * k // 2)))]:
+        while not add(random_dna(rng, n)):
+            pass
+    seqs[:] = with_long_strings(seqs, k, 9100 * k + m)
+    add = _adder(seqs, k)
+    planted = 0
+    if k - m >= ROOM:
+        for t in _skewed(k, m, 70, 7):
+            planted += add(t)
+    L = key_length or key_length_of(k, m)
+    if L != m and k - L >= ROOM:
+        more = _skewed(k, L, 0, 0)
+        # what is left of the minimizer part with no heavy and no mid-load copies: the two strings of the third motif and the single k-mer;
+        # behind them the 100 + 9 + 2 copies of the three table motifs
+        assert [len(t) for t in more[:3]] == [k + 3 + L + 2 * k] * 2 + [k] and len(more) == 3 + 111, [len(t) for t in more[:4]]
+        assert any(more[3][at:at + L] in more[4] for at in range(k + 3, k + 30)), "the strings behind them share a motif of the key's length"
+        table = sum(add(t) for t in more[3:])
+        assert table >= 100, (k, L, table)
+        planted += table
+    assert k - m < ROOM or planted >= 100, (k, m, planted)
+    _ODD[(k, m, key_length)] = seqs
+    return seqs
+
+
+class Point:
+    """one dictionary with its reads and everything the references say about them (on the CPU)"""
+
+
+def long_read_of(sequences, with_n):
+    """the dictionary's strings back to back on alternating strands, again and again until the read has more than 2^16 bases"""
+    parts, size, i = [], 0, 0
+    while size <= (1 << 16) + 500:
+        s = sequences[i % len(sequences)]
+        parts.append(revcomp(s) if (i + i // len(sequences)) % 2 else s)  # (a string comes on both strands as the rounds go)
+        size += len(s) + int(with_n)
+        i += 1
+    return ("N" if with_n else "").join(parts)
+
+
+def make_inputs(k, m, key_length, canonical, exe, scratch):
+    """-> Point: the dictionary (conftest.Case), the reads, the long reads and the repeated read"""
+    from conftest import Case
+    from gpu_segments_worker import make_reads
+
+    pt = Point()
+    pt.k, pt.m, pt.canonical, pt.W, pt.floors = k, m, canonical, 1 if k <= 31 else 2, None
+    if m % 2 == 0:
+        even = make_point(k, m, canonical, exe, scratch, extend=lambda seqs: with_long_strings(seqs, k, 9100 * k + m), key_length=key_length or None)
+        pt.floors = assert_floors(even)  # at least FLOOR tying k-mers that the reads hold and the dictionary contains, of every kind
+        pt.case, own = even.case, even.reads
+    else:
+        seqs = odd_sequences(k, m, key_length)
+        pt.case, own = Case(f"forms_k{k}_m{m}_{int(canonical)}", seqs, k, m, canonical, scratch), []
+    seqs = pt.sequences = pt.case.sequences
+    pt.jumps = jump_reads(k, 9100 * k + m)
+    reads = make_reads(seqs, k) + synthetic_reads(seqs, k, 160, seed=k + m, read_len=3 * k) + own + pt.jumps
+    for s in seqs:
+        reads += [s, revcomp(s)]
+    pt.reads = reads
+    pt.long_reads = [long_read_of(seqs, False), long_read_of(seqs, True)]
+    assert all(len(r) > (1 << 16) for r in pt.long_reads)
+    hot = next(s for s in seqs if len(s) >= 800)[40:40 + k + 100]
+    pt.repeated = [hot] * REPEATS
+    return pt
+
+
+# ---- the references ----------------------------------------------------------------------------------------------------------------------
+def classify(oracle, reads, k):
+    from gpu_segments_worker import per_kmer
+
+    per = [per_kmer(oracle, r, k) for r in reads]
+    return [p[0] for p in per], [p[1] for p in per], [p[2] for p in per]
+
+
+def rows_of(kinds):
+    return np.array([[kd.size, (kd >= 2).sum(), (kd == 1).sum(), (kd == 0).sum(), (kd == 2).sum(), (kd == 3).sum()] for kd in kinds], dtype=np.uint64).reshape(-1, 6)
+
+
+_TRUTH = {}
+
+
+def truth_ids(gt, sequences, reads, kinds, k):
+    """GroundTruth.lookup (the input strings, sorted) of every valid k-mer of every read, in order -> the ids. The two flavours of a point
+    have the same strings and the same reads, so the same truth: it is looked up once per process."""
+    key = (k, hash(tuple(sequences)), hash(tuple(reads)))
+    if key not in _TRUTH:
+        _TRUTH.clear()
+        _TRUTH[key] = _truth_ids(gt, reads, k)
+    ids, valid_per_read = _TRUTH[key]
+    assert valid_per_read == [int((kd != 0).sum()) for kd in kinds]  # (the oracle's idea of a valid k-mer is the input's)
+    return ids
+
+
+def _truth_ids(gt, reads, k):
+    ok = np.zeros(256, dtype=bool)
+    ok[list(b"ACGTacgt")] = True
+    stretches, valid_per_read = [], []
+    for r in reads:
+        b = np.frombuffer(r.encode("ascii", "replace"), dtype=np.uint8)
+        bad = np.flatnonzero(~ok[b])
+        edges = np.concatenate([[-1], bad, [b.size]])
+        mine = [r[int(a) + 1:int(e)] for a, e in zip(edges[:-1], edges[1:]) if e - a - 1 >= k]
+        valid_per_read.append(sum(len(s) - k + 1 for s in mine))
+        stretches += mine
+    W = 1 if k <= 31 else 2
+    q = kmers_of(stretches, k).reshape(-1, W)
+    uniq, inverse = np.unique(q, axis=0, return_inverse=True)
+    uniq = np.ascontiguousarray(uniq).reshape(-1)
+    there = gt.lookup(uniq, False)["kmer_id"]  # (strand by strand, the other strand by numpy: GroundTruth turns a two-word k-mer base by base)
+    back = gt.lookup(packed_revcomp(uniq, k, W), False)["kmer_id"]
+    return np.where(there != INVALID, there, back)[inverse.reshape(-1)], valid_per_read
+
+
+def string_of_ids(gt, k):
+    """id -> string, from the strings' lengths alone"""
+    sizes = (np.diff(gt.endpoints).astype(np.int64) - (k - 1))
+    return np.repeat(np.arange(sizes.size), sizes), sizes
+
+
+def gate(pt):
+    """on the CPU, before any device call: every kind of read, run and seam is there, and the oracle's ids are the input's"""
+    from gpu_cover_worker import bitmap_of
+    from gpu_depth_worker import depth_of, runs_of
+    from gpu_segments_worker import kinds_of
+
+    case, k, reads = pt.case, pt.k, pt.reads
+    n_kmers = case.gt.num_kmers
+    pt.kinds, pt.oris, pt.ids = classify(case.oracle, reads, k)
+    found = kinds_of(reads, pt.kinds, pt.oris, k)  # (asserts every count positive: the kinds of reads and, for S of 1, 2, 7, 64, of seams)
+    all_ids = np.concatenate(pt.ids)
+    valid = np.concatenate(pt.kinds) != 0
+    truth = truth_ids(case.gt, pt.sequences, reads, pt.kinds, k)
+    bad = np.flatnonzero(all_ids[valid] != truth)
+    assert bad.size == 0, ("the oracle's ids against GroundTruth.lookup", bad[:5].tolist(), all_ids[valid][bad[:5]].tolist(), truth[bad[:5]].tolist())
+    assert (all_ids[~valid] == INVALID).all()
+    lo, n, backward, read_of_run = runs_of(pt.ids)
+    lengths = np.array([len(r) for r in reads])
+    hits = np.array([int((ids != INVALID).sum()) for ids in pt.ids])
+    kinds = {"forward": int((~backward & (n > 1)).sum()), "backward": int(backward.sum()), "runs_of_one": int((n == 1).sum()),
+             "runs_of_64_and_more": int((n >= 64).sum()), "runs_from_id_0": int((lo == 0).sum()), "runs_to_the_last_id": int((lo + n == n_kmers).sum()),
+             "reads_shorter_than_k": int(((lengths < k) & (lengths > 0)).sum()), "empty_reads": int((lengths == 0).sum()),
+             "reads_without_a_hit": int(((lengths >= k) & (hits == 0)).sum()), "reads_with_N": sum("N" in r for r in reads)}
+    assert all(v > 0 for v in kinds.values()), kinds
+    # the jump reads: two neighbours in the read that are both found, in the same string, and not neighbours there -- a search, no extension
+    jumps = 0
+    for r in pt.jumps:
+        res = case.oracle.streaming_read(r)
+        ids, sid, ori = res["kmer_id"], res["string_id"], res["kmer_orientation"]
+        assert (ids != INVALID).all() and (sid == sid[0]).all() and res.size == 2 * JUMP, "a jump read lies in one string"
+        step = ids[1:].astype(np.int64) - ids[:-1].astype(np.int64)
+        assert (step != ori[:-1]).sum() == 1 and abs(int(step[JUMP - 1])) > 1, "a jump read jumps once, behind its first JUMP k-mers"
+        assert case.oracle.streaming_query([r])["num_searches"] == 2
+        jumps += 1
+    kinds["jumps_inside_a_string"] = jumps
+    kinds["seams"] = {name: v for name, v in found.items() if "@" in name}
+    # the expected answers of every form, from the oracle's per-k-mer results
+    pt.want_rows = rows_of(pt.kinds)
+    pt.want_totals = pt.want_rows.sum(0)
+    rep = case.oracle.streaming_query(reads)
+    assert [rep[c] for c in COLUMNS] == pt.want_totals.tolist(), "the oracle's report against its per-k-mer results"
+    pt.cover_words = (n_kmers + 63) // 64
+    pt.want_cover, pt.want_depth = bitmap_of(all_ids, pt.cover_words), depth_of(all_ids, n_kmers)
+    # the long reads: the same references
+    lk, lo_, lids = classify(case.oracle, pt.long_reads, k)
+    assert (np.concatenate(lids)[np.concatenate(lk) != 0] == truth_ids(case.gt, pt.sequences, pt.long_reads, lk, k)).all(), "the long reads: the oracle's ids against GroundTruth.lookup"
+    pt.long_kinds, pt.long_ids = lk, lids
+    assert (lk[0] != 0).all() and (lk[1] == 0).sum() >= k and min(int((x >= 2).sum()) for x in lk) > 20000
+    # the repeated read: one run
+    hk, _, hids = classify(case.oracle, pt.repeated[:1], k)
+    assert (hk[0] == np.array([2] + [3] * 100)).all(), "the repeated read is one run of 101 k-mers"
+    pt.hot_ids = hids[0]
+    return {"kmers": n_kmers, "strings": len(pt.sequences), "reads": len(reads), "read_kmers": int(pt.want_totals[0]), "runs": int(pt.want_totals[4]),
+            "seams_joined": {str(S): found[f"seam_in_forward_run@{S}"] + found[f"seam_in_backward_run@{S}"] for S in SEGMENT_SIZES}, "kinds": kinds,
+            "floors": pt.floors}
+
+
+# ---- the device --------------------------------------------------------------------------------------------------------------------------
+def check_flavour(pt, key_length, layer):
+    import sshash_amd
+    from gpu_cover_worker import bitmap_of, device_string_counts
+    from gpu_depth_worker import depth_of, device_depth, device_string_sums
+    from gpu_per_read_worker import oracle_rows
+    from gpu_runs_worker import check_both, oracle_runs
+    from gpu_segments_worker import accumulated, everything, launches, same
+    from test_gpu_streaming import _as_dict
+
+    case, k, m, reads = pt.case, pt.k, pt.m, pt.reads
+    what = f"{layer} k={k} m={m} key={key_length} {'canonical' if pt.canonical else 'regular'}"
+    d = case.dict.to_device(0)
+    st = d.device_stats(0)
+    assert LAYERS[layer][1](st), f"{what}: the replica is not the {layer} layer: {st}"
+    assert st["sk_key_length"] == (key_length or key_length_of(k, m)), (what, st["sk_key_length"])
+    n_kmers = case.gt.num_kmers
+    assert d.num_kmers() == n_kmers and d.cover_words() == pt.cover_words
+    totals, rows, cover, depth = pt.want_totals, pt.want_rows, pt.want_cover, pt.want_depth
+    want_host = {"totals": totals, "rows": rows, "rows_report": totals, "cover": cover, "cover_report": totals, "depth": depth, "depth_report": totals}
+    want_device = dict(want_host, rows_no_report=rows, cover_no_report=cover, depth_no_report=depth)
+
+    # ---- uncut: the five forms, host and device (rows into a prefilled array between guard rows) ----
+    assert d.read_segments()["kmers"] == sshash_amd.SEGMENTS_OFF, "a new dictionary does not segment"
+    d.set_read_segments(sshash_amd.SEGMENTS_OFF, device_calls=True)
+    assert _as_dict(d.streaming_query(reads)) == case.oracle.streaming_query(reads), f"{what}: streaming_query"
+    assert (oracle_rows(case.oracle, reads) == rows).all()
+    same(everything(d, reads, False), want_host, f"{what}: uncut, host calls")
+    same(everything(d, reads, True), want_device, f"{what}: uncut, device calls")
+    want_offsets, want_runs = oracle_runs(case.oracle, reads)
+    assert int(want_offsets[-1]) == int(totals[4])
+    check_both(d, reads, want_offsets, want_runs, what)
+    per_read, report = d.streaming_lookup(reads, full=True)
+    assert _as_dict(report) == case.oracle.streaming_query(reads), f"{what}: streaming_lookup report"
+    for r, (got, ids) in enumerate(zip(per_read, pt.ids)):
+        assert (got.kmer_id == ids).all(), f"{what}: streaming_lookup, read {r}"
+    run_offsets, runs, _ = d.streaming_runs(reads)
+    for r, (back, got) in enumerate(zip(sshash_amd.expand_runs(run_offsets, runs, [len(x) for x in reads], k), per_read)):
+        hit = got.kmer_id != INVALID
+        for f in ("kmer_id", "kmer_id_in_string", "string_id"):
+            assert (getattr(back, f) == getattr(got, f)).all(), f"{what}: expand_runs against streaming_lookup, read {r}, {f}"
+        assert (back.kmer_orientation[hit] == got.kmer_orientation[hit]).all(), f"{what}: expand_runs orientation, read {r}"
+    # ---- cover and depth per string, against numpy over the strings' lengths ----
+    string_of, sizes = string_of_ids(case.gt, k)
+    held = np.flatnonzero(depth)
+    want_counts = np.bincount(string_of[held], minlength=sizes.size).astype(np.uint64)
+    want_sums = np.bincount(string_of, weights=depth.astype(np.float64), minlength=sizes.size).astype(np.uint64)
+    for counts, total in (d.cover_string_counts(cover), device_string_counts(d, cover)):
+        assert (counts == want_counts).all() and total == held.size, f"{what}: cover_string_counts"
+    for sums, total in (d.depth_string_sums(depth), device_string_sums(d, depth)):
+        assert (sums == want_sums).all() and total == int(depth.sum(dtype=np.uint64)), f"{what}: depth_string_sums"
+    # ---- depth: the deltas, finished in place and out of place, arrays at an address that is no multiple of 16 ----
+    for in_place in (True, False):
+        got, deltas, _ = device_depth(d, reads, in_place=in_place, skew=1)
+        assert (got == depth).all(), f"{what}: depth, device call, skew 1, in place {in_place}"
+        assert (np.cumsum(deltas, dtype=np.uint32) == depth).all(), f"{what}: the deltas' prefix sum"
+        assert (deltas != 0).sum() <= 2 * int(totals[4]), f"{what}: at most two deltas a run"
+    want_hot = depth_of(pt.hot_ids, n_kmers) * np.uint32(REPEATS)
+    got, deltas, _ = device_depth(d, pt.repeated)
+    assert (got == want_hot).all(), f"{what}: one read {REPEATS} times"
+    hi = int(pt.hot_ids.max())
+    assert sorted(deltas[deltas != 0].tolist()) == ([REPEATS] if hi == n_kmers - 1 else [REPEATS, (1 << 32) - REPEATS]), f"{what}: the deltas of the repeated read"
+    got, _ = d.streaming_depth(pt.repeated)
+    assert (got == want_hot).all(), f"{what}: one read {REPEATS} times, host call"
+
+    # ---- reads above 2^16 bases: the host calls (the position-parallel route), the device calls (one lane each) ----
+    batch = reads[:20] + [pt.long_reads[0], ""] + reads[20:40] + [pt.long_reads[1]]
+    bk, bids = pt.kinds[:20] + [pt.long_kinds[0], pt.kinds[0][:0]] + pt.kinds[20:40] + [pt.long_kinds[1]], pt.ids[:20] + pt.long_ids[:1] + pt.ids[20:40] + pt.long_ids[1:]
+    brows = rows_of(bk)
+    assert (brows == oracle_rows(case.oracle, batch)).all()
+    bcover, bdepth = bitmap_of(np.concatenate(bids), pt.cover_words), depth_of(np.concatenate(bids), n_kmers)
+    long_host = {"totals": brows.sum(0), "rows": brows, "rows_report": brows.sum(0), "cover": bcover, "cover_report": brows.sum(0), "depth": bdepth,
+                 "depth_report": brows.sum(0)}
+    long_device = dict(long_host, rows_no_report=brows, cover_no_report=bcover, depth_no_report=bdepth)
+    same(everything(d, batch, False), long_host, f"{what}: the long reads uncut, host calls")
+    same(everything(d, batch, True), long_device, f"{what}: the long reads uncut, device calls")
+    assert launches(d) == 0, "SEGMENTS_OFF launched over segments"
+
+    # ---- segments of S k-mers: byte for byte the uncut answers, also into arrays that hold values ----
+    rng = np.random.default_rng(5)
+    before_cover = rng.integers(0, 1 << 63, pt.cover_words, dtype=np.uint64) & rng.integers(0, 1 << 63, pt.cover_words, dtype=np.uint64)
+    before_cover[-1] &= np.uint64((1 << (n_kmers % 64 or 64)) - 1)
+    before_depth = rng.integers(0, 1 << 32, n_kmers, dtype=np.uint64).astype(np.uint32)
+    start = np.arange(1, 7, dtype=np.uint64) * np.uint64(1000003)
+    acc_host = {"cover": cover | before_cover, "depth": depth + before_depth}
+    acc_device = dict(cover=acc_host["cover"], depth=depth + np.cumsum(before_depth, dtype=np.uint32), totals=totals + start, rows_report=totals + start,
+                      cover_report=totals + start, depth_report=totals + start)  # (the device call adds to DELTAS: what they held is scanned with them)
+    segmented = {}
+    for S in SEGMENT_SIZES:
+        d.set_read_segments(S, device_calls=True)
+        assert d.read_segments()["kmers"] == S
+        at = launches(d)
+        same(everything(d, reads, False), want_host, f"{what}: S = {S}, host calls")
+        assert launches(d) >= at + 4, f"{what}: S = {S}: the host calls did not launch over segments"
+        at = launches(d)
+        same(everything(d, reads, True), want_device, f"{what}: S = {S}, device calls")
+        assert launches(d) > at, f"{what}: S = {S}: the device calls did not launch over segments"
+        same(accumulated(d, reads, False, before_cover, before_depth), acc_host, f"{what}: S = {S}, host calls into arrays that hold values")
+        same(accumulated(d, reads, True, before_cover, before_depth), acc_device, f"{what}: S = {S}, device calls into arrays that hold values")
+        segmented[str(S)] = launches(d)
+    # ---- the long reads at the default S ----
+    d.set_read_segments(device_calls=True)
+    S = d.read_segments()["kmers"]
+    assert 1 < S < (1 << 14), S
+    at = launches(d)
+    same(everything(d, batch, False), long_host, f"{what}: the long reads at the default S, host calls")
+    same(everything(d, batch, True), long_device, f"{what}: the long reads at the default S, device calls")
+    assert launches(d) > at
+    # ---- and off again ----
+    d.set_read_segments(sshash_amd.SEGMENTS_OFF, device_calls=True)
+    at = launches(d)
+    same(everything(d, reads, False), want_host, f"{what}: SEGMENTS_OFF again, host calls")
+    same(everything(d, reads, True), want_device, f"{what}: SEGMENTS_OFF again, device calls")
+    assert launches(d) == at, "SEGMENTS_OFF launched over segments"
+    d.close()
+    return {"sk_slots": st["sk_slots"], "directory_sectors": st["directory_sectors"], "sk_key_length": st["sk_key_length"], "sk_heavy_kmers": st["sk_heavy_kmers"],
+            "default_S": S, "segmented_launches": segmented}
+
+
+def main():
+    import tempfile
+
+    k, m, key_length, layer, exe, scratch = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3]), sys.argv[4], sys.argv[5], sys.argv[6]
+    cpu_only = "--cpu-only" in sys.argv[7:]
+    assert layer in LAYERS
+    out, seconds = {}, {}
+    with tempfile.TemporaryDirectory(dir=scratch) as tmp:
+        for canonical in (False, True):
+            name = "canonical" if canonical else "regular"
+            t0 = time.time()
+            pt = make_inputs(k, m, key_length, canonical, exe, tmp)
+            out[name] = gate(pt)
+            t1 = time.time()
+            if not cpu_only:
+                out[name].update(check_flavour(pt, key_length, layer))
+                if layer == "table" and (k, m, key_length) in HEAVY:
+                    assert out[name]["sk_heavy_kmers"] > 0, (k, m, key_length, name, "no k-mer under a heavy key")
+            seconds[name] = [round(t1 - t0, 2), round(time.time() - t1, 2)]  # (inputs and references on the CPU, calls on the device)
+    print(json.dumps({"ok": True, "k": k, "m": m, "key_length": key_length, "layer": layer, "cpu_only": cpu_only, "dictionaries": out, "seconds": seconds}))
+
+
+if __name__ == "__main__":
+    main()

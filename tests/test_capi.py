@@ -124,7 +124,8 @@ def test_product_does_not_touch_the_oracle():
 def test_table_key_function_is_strand_symmetric(tmp_path):
     """The super-k-mer table serves a k-mer and its reverse complement from one slot: its key function
     (csrc/device_layout.hpp, host+device code) must elect the same m-mer occurrence for both strands.
-    tests/cpp/check_table_key.cpp checks that with g++ on the host, k <= 31 and k <= 63."""
+    tests/cpp/check_table_key.cpp checks that with g++ on the host, k <= 31 and k <= 63, at 25 pairs (k, length of the table's keys): the
+    dictionary's m, the default k - 32, and the lengths that SSHASH_AMD_SK_M sets on either side of m in tests/test_gpu_forms_sweep.py."""
     import shutil
     import subprocess
 
@@ -134,6 +135,9 @@ def test_table_key_function_is_strand_symmetric(tmp_path):
     subprocess.check_call(["g++", "-O2", "-std=c++17", os.path.join(ROOT, "tests", "cpp", "check_table_key.cpp"), "-o", exe])
     p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0 and p.stdout.startswith("OK "), p.stdout + p.stderr
+    assert int(p.stdout.split()[1]) == 25 * 200000, p.stdout  # every pair ran its 200 000 k-mers
+    for k, key_length in ((31, 25), (31, 17), (31, 14), (21, 20), (15, 14), (33, 31), (47, 31), (63, 12), (63, 20), (63, 17)):
+        assert f"sk_key_persists k={k} m={key_length}:" in p.stderr, (k, key_length)
 
 
 def test_lookup_output_buffer_is_checked_before_anything_runs(case_skew_regular):

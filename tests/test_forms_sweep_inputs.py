@@ -1,0 +1,38 @@
+"""CPU: the inputs of tests/test_gpu_forms_sweep.py and the references it trusts, before a device is involved -- the gate that
+tests/gpu_forms_worker.py runs ahead of its first device call, for every row of the matrix and both flavours: the reads hold every kind
+of read and of run (forward, backward, of one k-mer, of 64 and more, from id 0, to the last id, reads shorter than k, empty, without a
+hit, with N's), seams of every kind fall where segments of 1, 2, 7 and 64 k-mers are cut, the ids of the oracle's restated state machine
+equal GroundTruth.lookup of every valid k-mer of every read (the long reads above 2^16 bases among them), the repeated read is one run,
+and at an even m the reads walk over at least FLOOR tying k-mers of the dictionary."""
+from __future__ import annotations
+
+import pytest
+
+from gpu_even_m_worker import FLOOR, build_host_tool
+from gpu_forms_worker import MATRIX, SEGMENT_SIZES, gate, make_inputs
+
+
+@pytest.fixture(scope="module")
+def table_keys_exe(tmp_path_factory):
+    return build_host_tool("table_keys", tmp_path_factory.mktemp("table_keys"))
+
+
+def test_the_matrix_is_the_one_the_sweep_promises():
+    assert len(MATRIX) == len(set(MATRIX)) == 44
+    assert sum(layer == "directory" for _, _, _, layer in MATRIX) == 6 and sum(L != 0 for _, _, L, _ in MATRIX) == 12
+    assert all(L == 0 or layer == "table" for _, _, L, layer in MATRIX)
+
+
+@pytest.mark.parametrize("canonical", [False, True], ids=["regular", "canonical"])
+@pytest.mark.parametrize("k,m,key_length,layer", MATRIX, ids=[f"{layer}-k{k}m{m}" + (f"key{L}" if L else "") for k, m, L, layer in MATRIX])
+def test_gate(k, m, key_length, layer, canonical, table_keys_exe, tmp_path):
+    pt = make_inputs(k, m, key_length, canonical, table_keys_exe, str(tmp_path))
+    got = gate(pt)  # (asserts every kind and both references)
+    print(f"k={k} m={m} key={key_length} canonical={canonical}: {got['kmers']} k-mers in {got['strings']} strings, {got['reads']} reads, {got['runs']} runs, "
+          f"seams joined {got['seams_joined']}")
+    assert 5000 <= got["kmers"] <= 80000 and all(got["seams_joined"][str(S)] > 0 for S in SEGMENT_SIZES)
+    assert all(len(r) > (1 << 16) for r in pt.long_reads) and len(pt.repeated) == 4096
+    if m % 2 == 0:
+        assert all(c["read_kmers_found"] >= FLOOR for c in got["floors"].values()), got["floors"]
+    else:
+        assert got["floors"] is None
