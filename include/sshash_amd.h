@@ -259,18 +259,18 @@ sshash_status sshash_streaming_query_device(const sshash_dict* d, int device, co
  *      invalid whatever lies around it, so such a read can be cut: with S = kmers_per_segment a read of K k-mers becomes ceil(K / S)
  *      SEGMENTS of S k-mers (neighbours overlap by k - 1 bases; nothing is copied), one lane each. What differs is put right on the
  *      device: a segment's first k-mer counts as a search where in the whole read it may be an extension -- the rule of the runs
- *      below --, and a pass over the seams moves those back. The six counters, every per-read row, the cover and the depth are
- *      word for word what the uncut reads give.
+ *      below --, and a pass over the seams moves those back. The six counters, every per-read row, the cover, the depth and the sums
+ *      are word for word what the uncut reads give.
  *      Segmenting is OPT-IN: a new dictionary is at SSHASH_SEGMENTS_OFF with device_calls = 0 and takes the routes it always took.
  *      kmers_per_segment: 0 = the library's default S (256, RESULTS.md: best of 256, 1024, 4096 through the host call; the device calls
  *      favour 1024 slightly); SSHASH_SEGMENTS_OFF = never segment; otherwise 1 .. 2^30 (tiny values are allowed and only slow: tests
  *      put seams into small reads with them). Anything else, or a NULL dictionary, is SSHASH_ERR_ARGUMENT. Needs no device. Not to be changed while a call
  *      on the dictionary is in flight.
- *      Host and file calls (sshash_streaming_query, _per_read, _cover, _depth and their _from_file forms), once an S is set: a piece of
+ *      Host and file calls (sshash_streaming_query, _per_read, _cover, _depth, _sums and their _from_file forms), once an S is set: a piece of
  *      the batch that holds a read of more than S k-mers takes the run kernel over segments; pieces of shorter reads take exactly the launches they took
  *      before. With SSHASH_SEGMENTS_OFF a piece that holds a read above 2^16 bases goes through the position-parallel pipeline of
  *      sshash_streaming_lookup instead (one point lookup per k-mer, the same results).
- *      Device calls (sshash_streaming_query_device, _per_read_device, _cover_device, _depth_device): segment only with device_calls != 0
+ *      Device calls (sshash_streaming_query_device, _per_read_device, _cover_device, _depth_device, _sums_device): segment only with device_calls != 0
  *      -- they cannot see the reads' lengths without a synchronisation, and building the table costs a batch of short reads three small
  *      launches and a scan. With it: scratch of 24 bytes per segment (72 with rows) for at most num_reads + total_bases / S segments,
  *      sized from that bound without a synchronisation; the entries past the true count are empty and lie behind the last segment, so
@@ -447,6 +447,60 @@ sshash_status sshash_streaming_depth_from_file(const sshash_dict* d, const char*
 sshash_status sshash_depth_string_sums_device(const sshash_dict* d, int device, const uint32_t* depth, uint64_t* sums, uint64_t* total,
                                               void* hip_stream);
 sshash_status sshash_depth_string_sums(const sshash_dict* d, const uint32_t* depth, uint64_t* sums, uint64_t* total);
+
+/* ---- SCORING reads against a value per k-mer: per read, the sum of values[id] over the read's positive k-mers, and their number (no
+ *      reference counterpart as a call). `values` holds num_kmers words of uint32_t, word i for k-mer id i: a depth array
+ *      (sshash_streaming_depth), the weights of a weighted build expanded per id, or anything else. Row r of the output belongs to
+ *      read r of the call:
+ *          sums[r].sum            = the sum of value(id) over every place of read r where sshash_streaming_lookup returns a k-mer id,
+ *          sums[r].positive_kmers = the number of those places (num_positive_kmers of the read's row of sshash_streaming_query_per_read);
+ *      every strand counts, every occurrence counts. sum / positive_kmers is the mean value over the read's hits. A read shorter than
+ *      k, an empty read and a read without a hit have the row {0, 0}. Rows are OVERWRITTEN, every one of them. All arithmetic is modulo
+ *      2^64 (num_kmers values below 2^32 cannot reach it in a prefix; a read of 2^32 k-mers of value 2^32 - 1 could in a sum).
+ *      The device side works on the 64-bit exclusive PREFIX SUMS P of the values, num_kmers + 1 words: a maximal run of consecutive ids
+ *      [lo, hi) is worth P[hi] - P[lo], two 8-byte reads whatever its length. With at_least >= 1 the prefix counts instead of summing
+ *      -- value(id) = 1 if values[id] >= at_least, else 0 --, so that `sum` is the number of the read's SOLID k-mers (depth >= t).
+ *      A row is 16 bytes; 8-byte alignment is all that is asked of `sums`.
+ *      Preconditions and status codes as the depth calls: a null dictionary, or null bases / read_offsets / prefix (values) / sums with
+ *      num_reads > 0, is SSHASH_ERR_ARGUMENT before anything runs; num_reads == 0 succeeds and touches nothing; a dictionary that is not
+ *      resident is SSHASH_ERR_NO_DEVICE. A minimizer shard (num_shards > 1) adds the k-mers it owns and no others, so the shards' rows
+ *      added together are the rows of the whole index; for that a shard's host and file calls look every k-mer up on its own (the
+ *      pipeline of sshash_streaming_lookup), and sshash_streaming_sums_device, which is the run kernel, is SSHASH_ERR_ARGUMENT on a
+ *      minimizer shard -- as sshash_streaming_depth_device and for its reason.
+ *      Segments (sshash_set_read_segments): the host and file calls segment a piece that holds a read of more than S k-mers, the device
+ *      call with device_calls != 0; many lanes then add into one row, and the rows are word for word what the uncut reads give. ---- */
+typedef struct sshash_read_sum {
+    uint64_t sum;            /* of value(kmer_id) over the read's positive k-mers, modulo 2^64 */
+    uint64_t positive_kmers; /* how many those are */
+} sshash_read_sum;
+/* values -> prefix (device pointers, asynchronous on hip_stream): prefix[0] = 0, prefix[i] = values[0] + .. + values[i - 1] -- at_least
+ * >= 1: the number of j < i with values[j] >= at_least --, prefix[num_kmers] the total; num_kmers + 1 uint64, OVERWRITTEN; values is
+ * only read. One widening launch and a three-launch 64-bit scan in place; the scratch for the tile sums (8 bytes per 4096 k-mers) is
+ * sized, allocated and freed by the call itself, stream-ordered on hip_stream, out of the replica's own memory pool. NULL dictionary,
+ * values or prefix: SSHASH_ERR_ARGUMENT. */
+sshash_status sshash_value_prefix_device(const sshash_dict* d, int device, const uint32_t* values, uint32_t at_least, uint64_t* prefix,
+                                         void* hip_stream);
+/* device buffers, asynchronous on hip_stream. prefix: num_kmers + 1 uint64 from sshash_value_prefix_device, only read. sums: num_reads
+ * rows, OVERWRITTEN; nothing outside sums[0 .. num_reads) is written. report and total_bases as for sshash_streaming_depth_device.
+ * Always the run kernel: the rows are zeroed (one memset) and ONE launch adds every run's P[hi] - P[lo] and its length to its read's
+ * row, two 64-bit atomic adds that nothing waits for; no scratch beyond that of sshash_streaming_query_device. */
+sshash_status sshash_streaming_sums_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
+                                           uint64_t num_reads, uint64_t total_bases, const uint64_t* prefix, sshash_read_sum* sums,
+                                           uint64_t* report, void* hip_stream);
+/* host buffers, sharded over all resident replicas like sshash_streaming_depth. values: host, num_kmers uint32, uploaded once per call to
+ * every resident replica, which builds the prefix and frees the 4-byte copy again: 8 bytes per k-mer (+ 8) stay in the HBM of every
+ * replica for the length of the call, 12 per k-mer at the peak. A piece that holds a read above 2^16 bases, with segments off, goes
+ * through the position-parallel pipeline of sshash_streaming_lookup and is summed from its per-k-mer ids, which gives the same rows.
+ * report may be NULL. */
+sshash_status sshash_streaming_sums(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
+                                    const uint32_t* values, uint32_t at_least, sshash_read_sum* sums, sshash_streaming_report* report);
+/* a query file: the contract of sshash_streaming_query_from_file_per_read -- rows are handed over in batches, IN FILE ORDER, one row for
+ * EVERY record of the file, one call of `fn` at a time; a non-zero return of `fn` stops the query (SSHASH_ERR_ARGUMENT,
+ * sshash_last_error() carries the value). The prefix is built once and stays in the HBM of every replica (8 bytes per k-mer) for the
+ * whole file. report may be NULL. */
+typedef int (*sshash_read_sums_fn)(void* ctx, uint64_t first_read, uint64_t n, const sshash_read_sum* sums);
+sshash_status sshash_streaming_sums_from_file(const sshash_dict* d, const char* filename, int multiline, const uint32_t* values,
+                                              uint32_t at_least, sshash_read_sums_fn fn, void* ctx, sshash_streaming_report* report);
 
 /* ---- streaming_query<Dict,canonical>::lookup for EVERY k-mer of every read (include/streaming_query.hpp:56-109),
  *      batched: what the reference returns k-mer by k-mer while it streams a read. Every non-NULL array of `out` has one

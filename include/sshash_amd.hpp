@@ -405,6 +405,48 @@ public:
         check(sshash_depth_string_sums_device(m_h, device, d_depth, d_sums, d_total, hip_stream));
     }
 
+    /* SCORING reads against a value per k-mer (sshash_streaming_sums; the definitions are in include/sshash_amd.h): per read, the sum of
+       values[id] over the read's positive k-mers -- at_least >= 1: the number of those with values[id] >= at_least -- and their number.
+       `values`: num_kmers() words; `sums` is sized to num_reads and overwritten. Returns the batch's report. */
+    streaming_query_report streaming_sums(char const* bases, uint64_t const* read_offsets, uint64_t num_reads, std::vector<uint32_t> const& values,
+                                          uint32_t at_least, std::vector<sshash_read_sum>& sums) const {
+        if (values.size() < num_kmers()) throw std::invalid_argument("values has fewer than num_kmers() words");
+        sums.assign(num_reads, sshash_read_sum{0, 0});
+        std::vector<uint32_t> no_values(1);
+        sshash_streaming_report s;
+        check(sshash_streaming_sums(m_h, bases, read_offsets, num_reads, values.empty() ? no_values.data() : values.data(), at_least, sums.data(), &s));
+        return to_report(s);
+    }
+    /* device buffers, asynchronous on hip_stream: d_prefix (num_kmers() + 1 uint64) out of d_values (sshash_value_prefix_device), and the
+       rows out of d_prefix (sshash_streaming_sums_device): d_sums -- num_reads rows -- is overwritten, d_report -- may be null -- six
+       counters (accumulated into) */
+    void value_prefix_device(int device, uint32_t const* d_values, uint32_t at_least, uint64_t* d_prefix, void* hip_stream) const {
+        check(sshash_value_prefix_device(m_h, device, d_values, at_least, d_prefix, hip_stream));
+    }
+    void streaming_sums_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t num_reads, uint64_t total_bases,
+                               uint64_t const* d_prefix, sshash_read_sum* d_sums, uint64_t* d_report, void* hip_stream) const {
+        check(sshash_streaming_sums_device(m_h, device, d_bases, d_read_offsets, num_reads, total_bases, d_prefix, d_sums, d_report, hip_stream));
+    }
+    /* a query file, one row per record, handed over in file order: fn(first_read, sums, n) for one batch after the other; a non-zero
+       return stops the query (std::runtime_error). Fn: int(uint64_t, sshash_read_sum const*, uint64_t). */
+    template <typename Fn>
+    streaming_query_report streaming_sums_from_file(std::string const& filename, bool multiline, std::vector<uint32_t> const& values, uint32_t at_least,
+                                                    Fn&& fn) const {
+        if (values.size() < num_kmers()) throw std::invalid_argument("values has fewer than num_kmers() words");
+        struct context {
+            std::remove_reference_t<Fn>* fn;
+        } ctx{&fn};
+        std::vector<uint32_t> no_values(1);
+        sshash_streaming_report s;
+        check(sshash_streaming_sums_from_file(
+            m_h, filename.c_str(), multiline, values.empty() ? no_values.data() : values.data(), at_least,
+            [](void* c, uint64_t first_read, uint64_t n, const sshash_read_sum* rows) -> int {
+                return int((*static_cast<context*>(c)->fn)(first_read, rows, n));
+            },
+            &ctx, &s));
+        return to_report(s);
+    }
+
     /* a query file, one row per record, handed over in file order: fn(first_read, rows, n) for one batch after the other; a
        non-zero return stops the query (std::runtime_error). Fn: int(uint64_t, streaming_query_report const*, uint64_t). */
     template <typename Fn>

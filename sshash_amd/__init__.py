@@ -12,6 +12,7 @@ Method names and argument meaning follow ``sshash::dictionary`` (reference
 """
 from ._binding import (  # noqa: F401
     INVALID_U64,
+    READ_SUM_DTYPE,
     SEGMENTS_OFF,
     RUN_BACKWARD,
     RUN_DTYPE,
@@ -30,6 +31,7 @@ from ._binding import (  # noqa: F401
 
 __all__ = [
     "INVALID_U64",
+    "READ_SUM_DTYPE",
     "SEGMENTS_OFF",
     "RUN_BACKWARD",
     "RUN_DTYPE",

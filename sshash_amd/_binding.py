@@ -110,6 +110,8 @@ _lib: Optional[C.CDLL] = None
 
 # sshash_per_read_fn: (ctx, first_read, n, rows) -> 0 to go on
 _PerReadFn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p)
+# sshash_read_sum (include/sshash_amd.h): a read's row of streaming_sums
+READ_SUM_DTYPE = np.dtype([("sum", "<u8"), ("positive_kmers", "<u8")])
 
 
 def _preload_hip_runtime() -> None:
@@ -208,6 +210,10 @@ def _load() -> C.CDLL:
         "sshash_streaming_depth_from_file": (C.c_int, [P, C.c_char_p, C.c_int, P, C.POINTER(_Report)]),
         "sshash_depth_string_sums_device": (C.c_int, [P, C.c_int, P, P, P, P]),
         "sshash_depth_string_sums": (C.c_int, [P, P, P, C.POINTER(C.c_uint64)]),
+        "sshash_value_prefix_device": (C.c_int, [P, C.c_int, P, C.c_uint32, P, P]),
+        "sshash_streaming_sums_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, P, P, P]),
+        "sshash_streaming_sums": (C.c_int, [P, P, P, C.c_uint64, P, C.c_uint32, P, C.POINTER(_Report)]),
+        "sshash_streaming_sums_from_file": (C.c_int, [P, C.c_char_p, C.c_int, P, C.c_uint32, _PerReadFn, P, C.POINTER(_Report)]),
         "sshash_route_packed_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P, P]),
         "sshash_route_bucket_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, C.c_int, P, P, P, P]),
         "sshash_route_bucket_by_key_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P, P, P]),
@@ -238,6 +244,7 @@ C_ABI_SYMBOLS = (
     "sshash_cover_string_counts sshash_cover_string_counts_device "
     "sshash_streaming_depth sshash_streaming_depth_device sshash_depth_finish_device sshash_streaming_depth_from_file "
     "sshash_depth_string_sums sshash_depth_string_sums_device sshash_set_read_segments sshash_get_read_segments "
+    "sshash_value_prefix_device sshash_streaming_sums sshash_streaming_sums_device sshash_streaming_sums_from_file "
     "sshash_streaming_lookup sshash_streaming_lookup_device sshash_sharded_lookup_device sshash_sharded_lookup_rccl "
     "sshash_route_packed_device sshash_route_bucket_device sshash_route_bucket_by_key_device sshash_route_combine_device "
     "sshash_iterate_packed sshash_iterate_packed_device sshash_check_device"
@@ -894,6 +901,95 @@ class Dictionary:
         """Device buffers: d_sums (num_strings uint64) and d_total (0: none; one uint64) are overwritten."""
         _check(_load().sshash_depth_string_sums_device(self._h, int(device), C.c_void_p(d_depth), C.c_void_p(d_sums), C.c_void_p(d_total),
                                                        C.c_void_p(stream)))
+
+    # ---- streaming sums: reads scored against a value per k-mer --------------------------------------
+    def _values_array(self, values) -> np.ndarray:
+        """`values` as the calls want it (num_kmers() uint32, contiguous); None: the weights of a weighted dictionary, expanded per
+        k-mer id through weight(), a chunk of ids at a time."""
+        n = self.num_kmers()
+        if values is None:
+            if not self.weighted():
+                raise ValueError("values=None asks for the dictionary's weights, and this dictionary stores none")
+            out = np.empty(n, dtype=np.uint32)
+            chunk = 1 << 22
+            for at in range(0, n, chunk):
+                w = self.weight(np.arange(at, min(n, at + chunk), dtype=np.uint64))
+                if w.size and int(w.max()) >> 32:
+                    raise ValueError("a weight does not fit 32 bits")
+                out[at:at + w.size] = w
+            return out
+        values = np.asarray(values)
+        if values.ndim != 1 or values.size != n or values.dtype.kind not in "ui":
+            raise ValueError(f"values: {n} unsigned integers, one per k-mer id")
+        if values.dtype != np.uint32:
+            if values.size and (int(values.min()) < 0 or int(values.max()) >> 32):
+                raise ValueError("values: every one of them within 32 bits")
+            values = values.astype(np.uint32)
+        return np.ascontiguousarray(values)
+
+    def value_prefix_device(self, device: int, d_values: int, d_prefix: int, at_least: int = 0, stream: int = 0) -> None:
+        """Device buffers: d_prefix (num_kmers() + 1 uint64, overwritten) becomes the exclusive prefix sums of d_values (num_kmers()
+        uint32) -- at_least >= 1: of whether d_values[i] >= at_least --, d_prefix[num_kmers()] the total. What streaming_sums_device reads."""
+        _check(_load().sshash_value_prefix_device(self._h, int(device), C.c_void_p(d_values), int(at_least), C.c_void_p(d_prefix), C.c_void_p(stream)))
+
+    def streaming_sums_device(self, device: int, d_bases: int, d_read_offsets: int, num_reads: int, d_prefix: int, d_sums: int,
+                              d_report: int = 0, stream: int = 0, total_bases: int = 0) -> None:
+        """Device buffers: d_sums receives num_reads rows of READ_SUM_DTYPE (overwritten; 8-byte aligned), out of d_prefix
+        (value_prefix_device; only read); d_report (0: none) six counters (accumulated into). `total_bases` as for streaming_query_device."""
+        _check(_load().sshash_streaming_sums_device(self._h, int(device), C.c_void_p(d_bases), C.c_void_p(d_read_offsets), int(num_reads),
+                                                    int(total_bases), C.c_void_p(d_prefix), C.c_void_p(d_sums), C.c_void_p(d_report), C.c_void_p(stream)))
+
+    def streaming_sums(self, reads: Sequence[Union[str, bytes]], values=None, at_least: int = 0):
+        """Reads scored against a value per k-mer -> (sums, StreamingQueryReport): sums is a READ_SUM_DTYPE array, row r for read r:
+        `sum` = the sum of values[id] over the places of the read where streaming_lookup returns a k-mer id (either strand, every
+        occurrence; modulo 2^64) -- at_least >= 1: the number of those with values[id] >= at_least --, `positive_kmers` = the number of
+        those places. `values`: num_kmers() integers within 32 bits (a depth array, say); None: the weights of a weighted dictionary."""
+        values = self._values_array(values)
+        chunks = [s.encode("ascii", "replace") if isinstance(s, str) else bytes(s) for s in reads]
+        offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
+        if chunks:
+            offsets[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
+        bases = np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8)
+        sums = np.zeros(len(chunks), dtype=READ_SUM_DTYPE)
+        r = _Report()
+        _check(_load().sshash_streaming_sums(self._h, bases.ctypes.data, offsets.ctypes.data, len(chunks),
+                                             values.ctypes.data if values.size else bases.ctypes.data, int(at_least),
+                                             sums.ctypes.data if len(chunks) else None, C.byref(r)))
+        return sums, self._report(r)
+
+    def streaming_sums_from_file(self, filename: str, values=None, at_least: int = 0, multiline: bool = False,
+                                 per_read: Optional[Callable[[int, np.ndarray], Optional[int]]] = None):
+        """A query file scored like streaming_sums. per_read(first_read, sums) is called for one batch of the file after the other, in
+        file order, sums a READ_SUM_DTYPE array with row i for record first_read + i (every record has a row); a return value other
+        than None / 0 stops the query (SSHashError), an exception raised by the callable stops it too and is raised again here.
+        per_read=None: -> (sums of the whole file, StreamingQueryReport); otherwise -> StreamingQueryReport."""
+        values = self._values_array(values)
+        r = _Report()
+        raised, kept = [], []
+
+        def hand_over(_ctx, first_read, n, rows):
+            try:
+                words = np.ctypeslib.as_array(C.cast(rows, C.POINTER(C.c_uint64)), shape=(int(n), 2)).copy()
+                block = words.view(READ_SUM_DTYPE).reshape(int(n))
+                if per_read is None:
+                    kept.append(block)
+                    return 0
+                stop = per_read(int(first_read), block)
+                return int(stop) if stop else 0
+            except BaseException as e:  # (must not travel through the C frames)
+                raised.append(e)
+                return -1
+
+        fn = _PerReadFn(hand_over)
+        spare = np.zeros(1, dtype=np.uint32)
+        status = _load().sshash_streaming_sums_from_file(self._h, os.fsencode(filename), 1 if multiline else 0,
+                                                         values.ctypes.data if values.size else spare.ctypes.data, int(at_least), fn, None, C.byref(r))
+        if raised:
+            raise raised[0]
+        _check(status)
+        if per_read is None:
+            return (np.concatenate(kept) if kept else np.zeros(0, dtype=READ_SUM_DTYPE)), self._report(r)
+        return self._report(r)
 
     def streaming_lookup(self, reads: Sequence[Union[str, bytes]], full: bool = False):
         """streaming_query::lookup for every k-mer of every read (reference include/streaming_query.hpp:56-109), batched.

@@ -717,6 +717,63 @@ sshash_status sshash_depth_string_sums(const sshash_dict* d, const uint32_t* dep
     });
 }
 
+static_assert(sizeof(sshash_read_sum) == 2 * sizeof(uint64_t), "a row of sums is two words");
+
+sshash_status sshash_value_prefix_device(const sshash_dict* d, int device, const uint32_t* values, uint32_t at_least, uint64_t* prefix,
+                                         void* hip_stream) {
+    if (!d || !values || !prefix) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] { d->eng->value_prefix_device(device, values, at_least, prefix, hip_stream); });
+}
+
+sshash_status sshash_streaming_sums_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
+                                           uint64_t num_reads, uint64_t total_bases, const uint64_t* prefix, sshash_read_sum* sums,
+                                           uint64_t* report, void* hip_stream) {
+    if (!d || (num_reads && (!bases || !read_offsets || !prefix || !sums))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] {
+        d->eng->streaming_sums_device(device, bases, read_offsets, num_reads, total_bases, prefix, reinterpret_cast<uint64_t*>(sums), report, hip_stream);
+    });
+}
+
+sshash_status sshash_streaming_sums(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
+                                    const uint32_t* values, uint32_t at_least, sshash_read_sum* sums, sshash_streaming_report* report) {
+    if (!d || (num_reads && (!bases || !read_offsets || !values || !sums))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (report) std::memset(report, 0, sizeof(*report));
+    return guarded([&] {
+        if (num_reads == 0) return;
+        const value_prefixes on_devices(*d->eng, values, at_least);
+        const streaming_report r = d->eng->streaming_sums_host(bases, read_offsets, num_reads, on_devices, reinterpret_cast<uint64_t*>(sums));
+        if (report) fill_report(report, r);
+    });
+}
+
+sshash_status sshash_streaming_sums_from_file(const sshash_dict* d, const char* filename, int multiline, const uint32_t* values,
+                                              uint32_t at_least, sshash_read_sums_fn fn, void* ctx, sshash_streaming_report* report) {
+    if (!d || !filename || !values || !fn) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (report) std::memset(report, 0, sizeof(*report));
+    return guarded([&] {
+        read_stream in(filename, multiline != 0, d->idx->k, true);  // (every record of the file: row i is record i)
+        if (!in.supported()) {
+            fprintf(stderr, "unsupported query file format\n");
+            return;
+        }
+        /* the sequential reader, as sshash_streaming_query_from_file_per_read; the prefix stays on the devices from the first batch to the last */
+        const value_prefixes on_devices(*d->eng, values, at_least);
+        streaming_report total;
+        uint64_t first_read = 0;
+        std::vector<sshash_read_sum> rows;
+        for_each_batch(in, [&](read_batch const& batch) {
+            const uint64_t n = batch.num_reads();
+            if (n == 0) return;
+            rows.resize(n);
+            total += d->eng->streaming_sums_host(batch.bases.data(), batch.offsets.data(), n, on_devices, reinterpret_cast<uint64_t*>(rows.data()));
+            if (report) fill_report(report, total);
+            const int stop = fn(ctx, first_read, n, rows.data());
+            if (stop) throw error(error_kind::argument, "the per-read callback returned " + std::to_string(stop));
+            first_read += n;
+        });
+    });
+}
+
 sshash_status sshash_streaming_lookup_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
                                              uint64_t num_reads, uint64_t total_bases, const sshash_results* out, uint64_t* report,
                                              void* hip_stream) {

@@ -43,11 +43,15 @@ struct streaming_report {  // streaming_query_report, include/util.hpp:21-36
 };
 
 /* where the runs of a streaming call go (streaming.hip), device pointers: run_offsets -- n_reads + 1 words, CSR --, the records
-   (sshash_streaming_run, include/sshash_amd.h) and how many of them there is room for */
+   (sshash_streaming_run, include/sshash_amd.h) and how many of them there is room for. The sums form alone reads the two members
+   behind them: the prefix sums of the values (num_kmers + 1 words) -- its rows, two words a read, are at `records` -- and, for reads cut
+   into segments, the read of every entry of the segment table (null: an entry is a read). */
 struct run_sink {
     uint64_t* run_offsets;
     void* records;
     uint64_t capacity;
+    uint64_t const* values_prefix;
+    uint64_t const* read_of;
 };
 
 class engine;
@@ -83,6 +87,22 @@ private:
     uint64_t m_kmers;
     std::vector<int> m_devices;
     std::vector<uint32_t*> m_deltas;
+};
+
+/* The 64-bit exclusive prefix sums of one array of values (num_kmers + 1 words, 8 bytes per k-mer) in the HBM of every resident replica,
+   for the length of a host call or of a whole query file (streaming.hip): `h_values` (host, num_kmers words of 32 bits) is uploaded to
+   every replica, the prefix is built there (engine::value_prefix_device) and the 4-byte copy is freed again; throws no_device when no
+   replica is resident. */
+class value_prefixes {
+public:
+    value_prefixes(engine const& eng, uint32_t const* h_values, uint32_t at_least);
+    ~value_prefixes();
+    value_prefixes(value_prefixes const&) = delete;
+    value_prefixes& operator=(value_prefixes const&) = delete;
+    uint64_t const* on(int device) const;  // the prefix on `device` (device pointer)
+private:
+    std::vector<int> m_devices;
+    std::vector<uint64_t*> m_prefix;
 };
 
 class engine {
@@ -168,7 +188,8 @@ public:
        segments (set_read_segments; off: above 2^16 bases the position-parallel pipeline), the others the run kernel; all give the same rows. */
     streaming_report streaming_query_per_read_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* rows,
                                                    cover_bitmaps const* cover = nullptr /* streaming_cover_host */,
-                                                   depth_arrays const* depth = nullptr /* streaming_depth_host */) const;
+                                                   depth_arrays const* depth = nullptr /* streaming_depth_host */,
+                                                   value_prefixes const* prefix = nullptr, uint64_t* sums = nullptr /* streaming_sums_host */) const;
     /* An uncompressed FASTQ file, read and parsed by the lanes themselves (reads.hpp: fastq_pieces): every lane takes pieces of
        the file from a shared counter, parses a piece straight into its pinned block, uploads it and runs the streaming
        kernels -- no single reader thread, no intermediate batch. Returns false when the file turned out not to be four lines
@@ -188,8 +209,8 @@ public:
                                          uint64_t segment_kmers = SEGMENTS_AS_SET) const;
 
     /* Long reads (sshash_set_read_segments in include/sshash_amd.h): `kmers_per_segment` 0 = the default S, SEGMENTS_OFF = never -- the state of
-       a new dictionary --, else 1 .. 2^30 (throws otherwise). The host and file calls -- counters, rows, cover, depth -- send a piece that holds a read of more
-       than S k-mers through the run kernel over segments; `device_calls`: the four device entry points segment as well. Never on a
+       a new dictionary --, else 1 .. 2^30 (throws otherwise). The host and file calls -- counters, rows, cover, depth, sums -- send a piece that holds a read of more
+       than S k-mers through the run kernel over segments; `device_calls`: the five device entry points segment as well. Never on a
        minimizer shard, never the run records. Not to be changed while a call is in flight. */
     void set_read_segments(uint64_t kmers_per_segment, bool device_calls);
     uint64_t read_segment_kmers() const { return m_segment_kmers; }  // S, or SEGMENTS_OFF
@@ -238,6 +259,24 @@ public:
        `d_total` (one word, nullable) are overwritten. */
     void depth_string_sums_device(int device, uint32_t const* d_depth, uint64_t* d_sums, uint64_t* d_total, void* stream) const;
 
+    /* The 64-bit exclusive prefix sums of a value per k-mer (sshash_value_prefix_device in include/sshash_amd.h): d_prefix[i] = the sum of
+       d_values[j], j < i -- or, at_least >= 1, the number of j < i with d_values[j] >= at_least --, num_kmers + 1 words, overwritten.
+       Asynchronous: one widening launch, then the 64-bit scan in place; its tile sums are allocated and freed by the call,
+       stream-ordered, from the replica's pool. */
+    void value_prefix_device(int device, uint32_t const* d_values, uint32_t at_least, uint64_t* d_prefix, void* stream) const;
+    /* PER READ, the sum of a value per k-mer over the read's positive k-mers and their number (sshash_streaming_sums[_device]): row r of
+       `d_sums` (two words a read) is overwritten, `d_prefix` (value_prefix_device) is only read. Device buffers, asynchronous, always
+       the run kernel, its sums form: a memset and one launch; `d_report` (nullable) is accumulated into. Throws on a minimizer shard. */
+    void streaming_sums_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
+                               uint64_t const* d_prefix, uint64_t* d_sums, uint64_t* d_report, void* stream,
+                               uint64_t segment_kmers = SEGMENTS_AS_SET) const;
+    /* Host buffers, over all resident replicas, out of the prefixes `prefix` keeps on them; `sums` (host, n_reads x 2 words) is
+       overwritten. A piece that holds a long read takes the run kernel over segments (set_read_segments; off: above 2^16 bases the
+       position-parallel pipeline, summed from its per-k-mer ids), which gives the same rows -- every piece of a minimizer shard takes
+       that pipeline. Returns the totals. */
+    streaming_report streaming_sums_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, value_prefixes const& prefix,
+                                         uint64_t* sums) const;
+
     /* Per-k-mer results of the streaming query (streaming_query::lookup for every k-mer of every read,
        include/streaming_query.hpp:56-109): entry read_offsets[r] + j of every non-null array of `d_out` = the k-mer
        starting at base j of read r; places where no k-mer starts are left untouched. `d_report` (nullable): the six
@@ -248,7 +287,9 @@ public:
                                  run_sink const* d_runs = nullptr /* the reads' runs, compacted out of the per-k-mer results: run_offsets overwritten,
                                                                       records below its capacity written */,
                                  uint64_t* d_cover = nullptr /* a cover bitmap: the ids of the positive k-mers ORed into it */,
-                                 uint32_t* d_deltas = nullptr /* the deltas of a depth array: +1 / -1 around every positive k-mer's id added to them */) const;
+                                 uint32_t* d_deltas = nullptr /* the deltas of a depth array: +1 / -1 around every positive k-mer's id added to them */,
+                                 uint64_t const* d_prefix = nullptr, uint64_t* d_sums = nullptr /* with the prefix sums of a value per k-mer: the value of
+                                                                      every positive k-mer and 1 ADDED to the two words of its read's row */) const;
     streaming_report streaming_lookup_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads,
                                            result_view const& h_out) const;
 

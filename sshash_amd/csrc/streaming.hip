@@ -311,8 +311,15 @@ __device__ __forceinline__ void row_flush(uint64_t* __restrict__ row, bool parti
      STREAM_DEPTH        the six counters of the batch as STREAM_TOTALS, and HOW OFTEN the reads hold each k-mer of the dictionary, as a difference
                          array: where the cover form marks a run's range of ids [lo, hi) this one adds +1 to word lo and -1 to word hi of the
                          32-bit deltas at sink.records (depth_mark_run; hi = num_kmers: no word, nothing added) -- one or two atomics a run,
-                         whatever its length; the inclusive prefix sum of the deltas (inclusive_scan_u32) is the depth. One launch, as the cover. */
-enum : int { STREAM_TOTALS = 0, STREAM_ROWS = 1, STREAM_RUN_COUNTS = 2, STREAM_RUN_RECORDS = 3, STREAM_COVER = 4, STREAM_DEPTH = 5 };
+                         whatever its length; the inclusive prefix sum of the deltas (inclusive_scan_u32) is the depth. One launch, as the cover.
+     STREAM_SUMS         the six counters of the batch as STREAM_TOTALS, and PER READ the sum of a value per k-mer over the read's positive
+                         k-mers, and their number: over the 64-bit exclusive prefix sums P of the values at sink.values_prefix a run of ids
+                         [lo, hi) is worth P[hi] - P[lo], two loads whatever its length. Where the depth form adds its +1 / -1 this one adds
+                         that difference and the run's length to the two words of the read's row at sink.records (sums_add: two 64-bit
+                         atomics without return into rows the caller zeroed). The lane keeps the index of its row, one register, counted
+                         from the row of its wave's first read (sink.read_of: the read of every segment, for reads cut into segments,
+                         whose lanes then share rows -- addition commutes). One launch, as the depth. */
+enum : int { STREAM_TOTALS = 0, STREAM_ROWS = 1, STREAM_RUN_COUNTS = 2, STREAM_RUN_RECORDS = 3, STREAM_COVER = 4, STREAM_DEPTH = 5, STREAM_SUMS = 6 };
 
 /* the record of the run of `n` k-mers whose first (in read order) starts at base `at` of the packed reads and lies at offset `off` of
    the strings, in string `sid`: to place `cursor` of the records, unless that is past what the read or the caller has room for */
@@ -360,6 +367,26 @@ __device__ __forceinline__ void depth_mark_run(dict_view const& d, run_sink cons
     if (hi < d.num_kmers) (void)__hip_atomic_fetch_add(deltas + hi, ~0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+/* the same run into the row of its read (two words of 64 bits, arithmetic modulo 2^64): what the values of its ids [lo, hi) sum to --
+   P[hi] - P[lo] -- and its length. The `anchor` is the one of the two words that does not depend on the run's length, P[lo] forward and
+   P[hi] backward: asked for before the run is measured. Nothing comes back from the adds: the lane does not wait for either. */
+__device__ __forceinline__ uint64_t sums_run_anchor(dict_view const& d, run_sink const& sink, uint64_t off, uint32_t sid, int ori) {
+    const uint64_t kmer_id = off - uint64_t(sid) * (d.k - 1);
+    return sink.values_prefix[ori > 0 ? kmer_id : kmer_id + 1];
+}
+/* the other of the two: P[hi] forward, P[lo] backward, known once the run is measured */
+__device__ __forceinline__ uint64_t sums_run_far(dict_view const& d, run_sink const& sink, uint64_t off, uint32_t sid, int ori, uint64_t n) {
+    const uint64_t kmer_id = off - uint64_t(sid) * (d.k - 1);
+    return sink.values_prefix[ori > 0 ? kmer_id + n : kmer_id + 1 - n];  // (at most num_kmers: P holds num_kmers + 1 words)
+}
+/* `above` - `below` (P[hi] - P[lo]) and the run's length n into the row */
+__device__ __forceinline__ void sums_add(run_sink const& sink, uint64_t row, uint64_t above, uint64_t below, uint64_t n) {
+    const uint64_t sum = above - below;
+    unsigned long long* const words = static_cast<unsigned long long*>(sink.records) + 2 * row;
+    if (sum) (void)__hip_atomic_fetch_add(words, (unsigned long long)sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)__hip_atomic_fetch_add(words + 1, (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 /* The reads are given by a begin and an end pointer: read r spans the bases [begins[r], ends[r]) of the packed copy. For whole reads the two
    are `offsets` and `offsets + 1` -- the two words the kernel has always loaded --; for long reads cut into segments they are the two
    arrays of the segment table, and a "read" of the kernel is a segment ("long reads: SEGMENTS" below). */
@@ -369,7 +396,12 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                      const uint64_t* __restrict__ okay, const uint64_t* __restrict__ begins, const uint64_t* __restrict__ ends, const uint64_t n_reads,
                      const uint64_t reads_per_wave, const uint32_t move_out_every, uint64_t* __restrict__ report, const run_sink sink) {
     constexpr bool PER_READ = MODE == STREAM_ROWS, COUNT_RUNS = MODE == STREAM_RUN_COUNTS, RECORDS = MODE == STREAM_RUN_RECORDS, COVER = MODE == STREAM_COVER,
-                   DEPTH = MODE == STREAM_DEPTH;
+                   DEPTH = MODE == STREAM_DEPTH, SUMS = MODE == STREAM_SUMS;
+    /* (SUMS) when a measured run's two words of P are added to its row: at the end of the turn -- by then the seed's own loads have been
+       waited for, and these with them -- or where the run is measured, which makes the wave wait for them there. Late costs seven
+       registers across the turn. Measured, 2 x 10^7 reads of 150 bases with the table: at k <= 31 late 15.85 ms against 16.56, at
+       k <= 63, where the kernel spills as it is (72 bytes of scratch; late: 92), 13.76 against 12.58. */
+    constexpr bool LATE_SUMS = SUMS && W == 1;
     __shared__ uint4 stage[SK ? 4 * 256 : 1];  // a wave's 64 bucket lines on their way from the quads that fetch them to the lanes that own them
     uint4* const wave_stage = stage + (SK ? (threadIdx.x >> 6) * 256 : 0);
     /* the counters are 32 bits wide in the lanes (six registers fewer than five 64-bit ones: with them the k <= 63 kernel fits five waves a
@@ -421,6 +453,15 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
     uint32_t n_runs = 0, hit_sid = 0;
     uint64_t cursor = 0;
     const uint64_t wave_first = wave * reads_per_wave;
+    /* (SUMS) the row of the wave's first read: the read itself, or -- segments -- the read of that segment (an empty entry of the table,
+       behind the last segment: then so are all of the wave's, and none of them has a k-mer to add) */
+    uint64_t row_first = wave_first;
+    uint64_t late_anchor = 0, late_far = 0, late_n = 0;  // (SUMS) a measured run whose two words of P are on their way: sums_add at the end of the turn
+    uint32_t late_row = 0;
+    bool late_forward = true;
+    if constexpr (SUMS) {
+        if (sink.read_of) row_first = wave_first < n_reads ? sink.read_of[wave_first] : 0;
+    }
     uint64_t* const wave_rows = report + wave * reads_per_wave * 6;  // (PER_READ) the row of the wave's first read
 #ifdef SSHASH_STREAM_STATS
     /* (a debug build, tools/jobs/r06_stream_stats.sh: what the lanes of a wave do per turn -- wave-level sums in scalar registers, out
@@ -463,9 +504,23 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
         STAT(st_ext, pending);
         if (pending) {
             const uint64_t b = cur + k - 1, valid_end = inv < rd_end ? inv : rd_end;
+            uint64_t anchor = 0;
+            if constexpr (SUMS) anchor = sums_run_anchor(d, sink, off, hit_sid, ori);  // (on its way while the run is measured)
             const uint64_t run = extend_run<W>(d, packed, off, ori, b, valid_end - b, run_step_load<W>(d, packed, off, ori > 0, b, 0));
             if constexpr (COVER) cover_mark_run(d, sink, off, hit_sid, ori, run + 1);
             if constexpr (DEPTH) depth_mark_run(d, sink, off, hit_sid, ori, run + 1);
+            if constexpr (SUMS && !LATE_SUMS) {
+                const uint64_t far = sums_run_far(d, sink, off, hit_sid, ori, run + 1);
+                sums_add(sink, row_first + my_row, ori > 0 ? far : anchor, ori > 0 ? anchor : far, run + 1);
+            }
+            if constexpr (LATE_SUMS) {
+                /* asked for here, added at the end of the turn (or of the kernel). The row goes along: the lane may take its next read in between. */
+                late_far = sums_run_far(d, sink, off, hit_sid, ori, run + 1);  // (neither word is looked at here, not even to tell which is which)
+                late_anchor = anchor;
+                late_forward = ori > 0;
+                late_n = run + 1;
+                late_row = my_row;
+            }
             if constexpr (RECORDS) {  // (the hit lies a base before cur)
                 run_record_store(d, sink, begins, wave_first + my_row, cursor, cur - 1, off, hit_sid, ori, run + 1);
                 ++cursor;
@@ -527,6 +582,11 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                 } else if constexpr (RECORDS) {
                     my_row = uint32_t(r - wave_first);
                     cursor = sink.run_offsets[r];
+                } else if constexpr (SUMS) {
+                    if (rd_end - cur >= k) {  // (a read without a k-mer adds nothing: its row keeps the caller's zeros)
+                        atomicAdd(wave_moved_out + 4, (unsigned long long)(rd_end - cur - k + 1));
+                        my_row = uint32_t((sink.read_of ? sink.read_of[r] : r) - row_first);
+                    }
                 } else {
                     if (rd_end - cur >= k) atomicAdd(wave_moved_out + 4, (unsigned long long)(rd_end - cur - k + 1));
                 }
@@ -697,7 +757,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                     found = r.outcome == FAST_HIT;
                     off = r.kmer_offset;
                     ori = r.orientation;
-                    if constexpr (RECORDS || COVER || DEPTH) hit_sid = r.string_id;
+                    if constexpr (RECORDS || COVER || DEPTH || SUMS) hit_sid = r.string_id;
                     const bool stands = !found && !(where & WALK_VISITED);
                     if (stands || (where & WALK_HEAVY_PENDING)) {
                         /* a miss that stands for the k-mers behind this one: those that elect the same key occurrence (sk_key_persists)
@@ -735,7 +795,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                 found = h.found;
                 off = h.kmer_offset;
                 ori = h.orientation;
-                if constexpr (RECORDS || COVER || DEPTH) hit_sid = h.string_id;
+                if constexpr (RECORDS || COVER || DEPTH || SUMS) hit_sid = h.string_id;
                 neg_unknown_mini = !SK && !h.found && !h.minimizer_found;
             }
         }
@@ -757,11 +817,26 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                 if constexpr (DEPTH) {
                     if (!pending) depth_mark_run(d, sink, off, hit_sid, ori, 1);
                 }
+                if constexpr (SUMS) {
+                    if (!pending) {  // a run of one: P[id + 1] - P[id]
+                        const uint64_t kmer_id = off - uint64_t(hit_sid) * (k - 1);
+                        sums_add(sink, row_first + my_row, sink.values_prefix[kmer_id + 1], sink.values_prefix[kmer_id], 1);
+                    }
+                }
             } else {
                 ++c_negative;
             }
             ++cur;
         }
+        if constexpr (LATE_SUMS) {
+            if (late_n) {
+                sums_add(sink, row_first + late_row, late_forward ? late_far : late_anchor, late_forward ? late_anchor : late_far, late_n);
+                late_n = 0;
+            }
+        }
+    }
+    if constexpr (LATE_SUMS) {  // (the turn that measured the last run of all left the loop before its end)
+        if (late_n) sums_add(sink, row_first + late_row, late_forward ? late_far : late_anchor, late_forward ? late_anchor : late_far, late_n);
     }
 #ifdef SSHASH_STREAM_STATS
     const unsigned long long st_neg_kept = wave_sum(st_kept_lane);
@@ -954,6 +1029,20 @@ void inclusive_scan_u32(uint32_t const* in, uint32_t* out, uint64_t n, uint32_t*
     HIP_CHECK(hipGetLastError());
 }
 
+/* ---- the values of the sums form as 64-bit words, ready for exclusive_scan_u64: wide[i] = values[i], or -- at_least >= 1 -- whether
+        values[i] >= at_least; word n (the scan turns it into the total) zero ---- */
+__global__ void __launch_bounds__(256)
+values_widen_kernel(const uint32_t* __restrict__ values, const uint64_t n, const uint32_t at_least, uint64_t* __restrict__ wide) {
+    const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i > n) return;
+    uint64_t v = 0;
+    if (i < n) {
+        const uint32_t x = values[i];
+        v = at_least ? uint64_t(x >= at_least) : uint64_t(x);
+    }
+    wide[i] = v;
+}
+
 /* ==== long reads: SEGMENTS ==========================================================================================================
    One lane walks one read, so a batch of few long reads is few lanes, and its time is that of its longest read. A k-mer is positive,
    negative or invalid whatever lies around it; only whether a positive k-mer is a search or an extension depends on the k-mer before
@@ -963,7 +1052,8 @@ void inclusive_scan_u32(uint32_t const* in, uint32_t* out, uint64_t n, uint32_t*
    afterwards: a segment's first k-mer, when positive, was counted as a search; in the whole read it is an extension iff it continues
    the run of the k-mer before it (continues_run) -- the SEAM is then JOINED. The seam kernel looks both k-mers up, one lane a seam, and
    moves one count from searches to extensions for every joined seam. The cover is the same either way (OR), and so are the depth's
-   deltas: adjacent runs [lo, mid) and [mid, hi) leave what [lo, hi) leaves, the +1 and the -1 at mid cancel.
+   deltas: adjacent runs [lo, mid) and [mid, hi) leave what [lo, hi) leaves, the +1 and the -1 at mid cancel. The sums likewise: P[mid]
+   cancels, and the segments of a read add into the read's row (sink.read_of).
    The table is built on the stream: the segments of every read, their exclusive scan (the index of every read's first segment), and
    one lane per ENTRY that finds its read by bisection over those -- no lane's work grows with a read's length. The host sizes the table
    from a bound (segment_bound); the entries past the true count are empty segments, which the run kernel takes for reads shorter than k. */
@@ -1115,12 +1205,14 @@ void launch_run_kernel(device_replica const* rep, dict_view const& d, dim3 grid,
 /* `run_phases` (with `sink`): RUNS_COUNT -- sink.run_offsets becomes the CSR offsets of the reads' runs (the counting form of the kernel, then
    the scan; `report` as without, may be null) --, RUNS_WRITE -- the records, for run_offsets that hold those offsets --, or both; or
    RUNS_COVER alone -- the cover form, ONE launch: the runs' k-mer ids marked in the bitmap at sink.records, `report` as without, may be null --;
-   or RUNS_DEPTH alone -- the depth form, ONE launch: the runs' +1 / -1 added to the 32-bit deltas at sink.records, `report` as with the cover. */
-enum : int { RUNS_COUNT = 1, RUNS_WRITE = 2, RUNS_COVER = 4, RUNS_DEPTH = 8 };
+   or RUNS_DEPTH alone -- the depth form, ONE launch: the runs' +1 / -1 added to the 32-bit deltas at sink.records, `report` as with the cover --;
+   or RUNS_SUMS alone -- the sums form: the reads' rows at sink.records (n_reads x 2 words) zeroed, then ONE launch that adds every run's
+   sum out of sink.values_prefix and its length to its read's row, `report` as with the cover. */
+enum : int { RUNS_COUNT = 1, RUNS_WRITE = 2, RUNS_COVER = 4, RUNS_DEPTH = 8, RUNS_SUMS = 16 };
 void launch_streaming_runs(device_replica const* rep, char const* bases, uint64_t const* offsets, uint64_t n_reads, uint64_t total_bases, uint64_t* report,
                            hipStream_t s, uint64_t* rows = nullptr /* per read: n_reads x 6 words; `report` may then be null */,
                            run_sink sink = run_sink{nullptr, nullptr, 0}, int run_phases = 0,
-                           uint64_t S = 0 /* the reads cut into segments of S k-mers (totals, rows, cover, depth; never the run records) */) {
+                           uint64_t S = 0 /* the reads cut into segments of S k-mers (totals, rows, cover, depth, sums; never the run records) */) {
     dict_view const& d = rep->view;
     const bool segmented = S != 0;
     if (segmented && (run_phases & (RUNS_COUNT | RUNS_WRITE))) throw error(error_kind::internal, "run records are not segmented");
@@ -1183,13 +1275,19 @@ void launch_streaming_runs(device_replica const* rep, char const* bases, uint64_
         HIP_CHECK(hipMemsetAsync(spare, 0, 6 * sizeof(uint64_t), s));
         return spare;
     };
-    /* the row, counting and record forms keep a lane's read as a 31-bit index into its wave's share -- not the cover and totals forms */
-    if ((rows || (run_phases & (RUNS_COUNT | RUNS_WRITE))) && reads_per_wave >> 31) throw error(error_kind::argument, "too many reads for one call");
+    /* the row, counting, record and sums forms keep a lane's read as a 31-bit index into its wave's share -- not the cover and totals forms */
+    if ((rows || (run_phases & (RUNS_COUNT | RUNS_WRITE | RUNS_SUMS))) && reads_per_wave >> 31) throw error(error_kind::argument, "too many reads for one call");
     if (run_phases & RUNS_COVER) {
         launch_run_kernel<STREAM_COVER>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), sink);
         if (segmented && caller_report) seams(nullptr, caller_report);  // (nobody reads the six counters: no seam is looked at)
     } else if (run_phases & RUNS_DEPTH) {
         launch_run_kernel<STREAM_DEPTH>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), sink);
+        if (segmented && caller_report) seams(nullptr, caller_report);
+    } else if (run_phases & RUNS_SUMS) {
+        /* (a run that spans a seam arrives as [lo, mid) and [mid, hi): P[mid] cancels, the lengths add up -- the seams are for the counters alone) */
+        HIP_CHECK(hipMemsetAsync(sink.records, 0, n_whole_reads * 2 * sizeof(uint64_t), s));
+        if (segmented) sink.read_of = seg + L.read;
+        launch_run_kernel<STREAM_SUMS>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), sink);
         if (segmented && caller_report) seams(nullptr, caller_report);
     } else if (run_phases) {
         if (run_phases & RUNS_COUNT) {
@@ -1345,6 +1443,41 @@ void engine::streaming_depth_device(int device, char const* d_bases, uint64_t co
     if (total_bases == 0) return;  // empty reads only: no k-mer
     const uint64_t S = segments_for(segment_kmers);
     launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, run_sink{nullptr, d_deltas, 0}, RUNS_DEPTH, S);
+    if (S) ++m_segmented_launches;  // (counted once the launches are made: a call that threw is none)
+}
+
+/* The prefix sums of a value per k-mer (sshash_value_prefix_device): widened, word num_kmers zero, scanned in place. */
+void engine::value_prefix_device(int device, uint32_t const* d_values, uint32_t at_least, uint64_t* d_prefix, void* stream) const {
+    device_replica const* rep = replica(device);
+    if (!d_values || !d_prefix) throw error(error_kind::argument, "null pointer");
+    device_guard guard(device);
+    hipStream_t s = hipStream_t(stream);
+    const uint64_t n = rep->view.num_kmers, blocks = (n + 256) / 256;  // (n + 1 words)
+    if (blocks >> 31) throw error(error_kind::argument, "too many k-mers for one launch");
+    hipLaunchKernelGGL(values_widen_kernel, dim3(uint32_t(blocks)), dim3(256), 0, s, d_values, n, at_least, d_prefix);
+    HIP_CHECK(hipGetLastError());
+    device_buffers tmp(rep, s);  // (stream-ordered, out of the replica's pool: handed back behind the apply launch)
+    exclusive_scan_u64(d_prefix, n + 1, tmp.alloc<uint64_t>(scan_tiles(n + 1)), s);
+}
+
+/* Per read, the sum of a value per k-mer over its positive k-mers and their number (sshash_streaming_sums_device): the sums form of the
+   run kernel, a memset and one launch. Every row is written: also when no base is there to look at. */
+void engine::streaming_sums_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
+                                   uint64_t const* d_prefix, uint64_t* d_sums, uint64_t* d_report, void* stream, uint64_t segment_kmers) const {
+    device_replica const* rep = replica(device);  // (not resident: that error first)
+    if (n_reads == 0) return;
+    if (!d_prefix || !d_sums) throw error(error_kind::argument, "prefix or sums pointer is null");
+    /* (as the depth: a shard's run kernel follows a run through k-mers of other shards, and the shards' rows added would hold those twice) */
+    if (m_idx->num_shards > 1) throw error(error_kind::argument, "a minimizer shard counts per k-mer: use the host call (sshash_streaming_sums)");
+    device_guard guard(device);
+    hipStream_t s = hipStream_t(stream);
+    total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
+    if (total_bases == 0) {  // empty reads only: their rows are zero
+        HIP_CHECK(hipMemsetAsync(d_sums, 0, n_reads * 2 * sizeof(uint64_t), s));
+        return;
+    }
+    const uint64_t S = segments_for(segment_kmers);
+    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, run_sink{nullptr, d_sums, 0, d_prefix, nullptr}, RUNS_SUMS, S);
     if (S) ++m_segmented_launches;  // (counted once the launches are made: a call that threw is none)
 }
 
@@ -1704,6 +1837,53 @@ depth_mark_ids_kernel(const uint8_t* __restrict__ flags, const uint64_t* __restr
     if (minus && id + 1 < num_kmers) (void)__hip_atomic_fetch_add(deltas + id + 1, 0u - minus, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+/* ---- the reads' sums out of the per-k-mer results (the host calls' route for reads too long for one lane, and for minimizer shards): one
+        lane a place, its k-mer's value P[id + 1] - P[id] and 1 into the two words of its read's row. The stretches of one read are
+        those of stream_classify_rows_kernel -- a stretch begins at the wave's first k-mer and at every k-mer that is the first of its read --;
+        the lanes of a wave sum over their stretch (a segmented sum, as stream_segment_rows_kernel), and the stretch's first lane, the only
+        one to look its read up in the offsets, adds what is not zero: at most one pair of atomics per wave and read. ---- */
+__global__ void __launch_bounds__(256)
+sums_add_ids_kernel(const uint8_t* __restrict__ flags, const uint64_t* __restrict__ kmer_id, const uint64_t total_bases, const uint64_t num_kmers,
+                    const uint64_t* __restrict__ prefix, const uint64_t* __restrict__ offsets, const uint64_t n_reads, uint64_t* __restrict__ sums) {
+    const uint64_t p = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint8_t f = p < total_bases ? flags[p] : uint8_t(0);
+    const bool has = (f & (SQ_VALID | SQ_INVALID)) != 0;
+    uint64_t v = 0, n = 0;
+    if (f & SQ_VALID) {
+        const uint64_t id = kmer_id[p];
+        if (id < num_kmers) {  // (INVALID_U64: not in the dictionary)
+            v = prefix[id + 1] - prefix[id];
+            n = 1;
+        }
+    }
+    const uint64_t have = __ballot(has);
+    if (__ballot(n != 0) == 0) return;  // (uniform)
+    const uint64_t below = (uint64_t(1) << lane) - 1;
+    const bool head = has && ((f & SQ_FIRST) || (have & below) == 0);
+    const uint64_t heads = __ballot(head);
+    const uint64_t mine_or_before = heads & (below | (uint64_t(1) << lane));
+    const uint32_t stretch = mine_or_before ? 63u - uint32_t(__builtin_clzll(mine_or_before)) : 64u;  // the head of my stretch (64: a place before the wave's first k-mer)
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+        const bool same = __shfl_down(stretch, o, 64) == stretch && lane + o < 64;
+        const uint64_t further_v = __shfl_down(v, o, 64), further_n = __shfl_down(n, o, 64);
+        if (same) {
+            v += further_v;
+            n += further_n;
+        }
+    }
+    if (!head || n == 0) return;
+    uint64_t lo = 0, hi = n_reads - 1;  // my read: the largest r with offsets[r] <= p
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (offsets[mid] <= p) lo = mid;
+        else hi = mid - 1;
+    }
+    unsigned long long* const row = reinterpret_cast<unsigned long long*>(sums + 2 * lo);
+    if (v) (void)__hip_atomic_fetch_add(row, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)__hip_atomic_fetch_add(row + 1, (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 /* ---- covered k-mers per string: a segmented popcount of a cover bitmap. The ids of string s are [begin(s), begin(s + 1)),
         begin(s) = endpoints[s] - s * (k - 1); strings hold from one k-mer to millions, so the lanes go over the bitmap's WORDS, one each.
         A lane finds the string of its word's first id -- the workgroup's first lane by bisection over all strings, the others from
@@ -1876,9 +2056,10 @@ void engine::depth_string_sums_device(int device, uint32_t const* d_depth, uint6
 
 void engine::streaming_lookup_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
                                      uint64_t total_bases, result_view const& d_out, uint64_t* d_report, void* stream, uint64_t* d_rows,
-                                     run_sink const* runs, uint64_t* d_cover, uint32_t* d_deltas) const {
+                                     run_sink const* runs, uint64_t* d_cover, uint32_t* d_deltas, uint64_t const* d_prefix, uint64_t* d_sums) const {
     device_replica const* rep = replica(device);
-    if (!d_out.kmer_id && !d_report && !d_rows && !runs && !d_cover && !d_deltas) throw error(error_kind::argument, "neither a kmer_id array nor a report to fill");
+    if ((d_prefix != nullptr) != (d_sums != nullptr)) throw error(error_kind::internal, "the sums go with their prefix");
+    if (!d_out.kmer_id && !d_report && !d_rows && !runs && !d_cover && !d_deltas && !d_sums) throw error(error_kind::argument, "neither a kmer_id array nor a report to fill");
     if (d_out.minimizer_found) throw error(error_kind::argument, "the streaming lookup does not report minimizer_found");
     if (n_reads == 0 || total_bases == 0) return;
     device_guard guard(device);
@@ -1931,6 +2112,11 @@ void engine::streaming_lookup_device(int device, char const* d_bases, uint64_t c
     }
     if (d_deltas) {
         hipLaunchKernelGGL(depth_mark_ids_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, flags, ids, total_bases, d.num_kmers, d_deltas);
+        HIP_CHECK(hipGetLastError());
+    }
+    if (d_sums) {
+        hipLaunchKernelGGL(sums_add_ids_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, flags, ids, total_bases, d.num_kmers, d_prefix,
+                           d_read_offsets, n_reads, d_sums);
         HIP_CHECK(hipGetLastError());
     }
     if (runs) {
@@ -2138,14 +2324,18 @@ streaming_report engine::streaming_query_host(char const* bases, uint64_t const*
 /* With `rows` (n_reads x 6 words, host) a lane's device block also holds a row for every read of the largest piece, and a piece's rows
    come back into the caller's array at the piece's first read. With `cover` (and no rows) a piece's k-mers are marked in the bitmap
    that `cover` keeps on the lane's device: the lanes of a device share it, OR commutes. With `depth` (and neither) its runs are added to
-   the deltas that `depth` keeps there: addition commutes as well. (A minimizer shard takes the per-k-mer route for every piece: only
+   the deltas that `depth` keeps there: addition commutes as well. With `sums` (and `prefix`, and none of those) a lane's device block
+   holds two words for every read of the largest piece, out of the prefix sums that `prefix` keeps there, and they come back as the rows
+   do. (A minimizer shard takes the per-k-mer route for every piece: only
    that one asks of every k-mer whether the shard owns it -- streaming_depth_device.) */
 streaming_report engine::streaming_query_per_read_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* rows,
-                                                       cover_bitmaps const* cover, depth_arrays const* depth) const {
+                                                       cover_bitmaps const* cover, depth_arrays const* depth, value_prefixes const* prefix,
+                                                       uint64_t* sums) const {
     if (n_reads == 0) return {};
     const piece_cuts pieces = cut_lane_pieces(read_offsets, n_reads);
-    const uint64_t row_bytes = 6 * sizeof(uint64_t);
-    return run_piece_lanes(*this, bases, read_offsets, pieces, rows ? pieces.max_reads * row_bytes : 0, [&](staged_piece const& p) {
+    const uint64_t row_bytes = 6 * sizeof(uint64_t), sum_bytes = 2 * sizeof(uint64_t);
+    const uint64_t extra_bytes = rows ? pieces.max_reads * row_bytes : sums ? pieces.max_reads * sum_bytes : 0;
+    return run_piece_lanes(*this, bases, read_offsets, pieces, extra_bytes, [&](staged_piece const& p) {
         const bool per_kmer = p.long_read && !p.segments;  // (no segments: a long read's piece takes the position-parallel pipeline)
         if (rows) {
             uint64_t* d_rows = reinterpret_cast<uint64_t*>(p.d_extra);
@@ -2159,11 +2349,19 @@ streaming_report engine::streaming_query_per_read_host(char const* bases, uint64
         } else if (depth) {
             if (per_kmer || m_idx->num_shards > 1) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, nullptr, nullptr, nullptr, depth->on(p.device));
             else if (p.nb) streaming_depth_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, depth->on(p.device), p.d_report, p.s, p.segments);
+        } else if (sums) {
+            uint64_t* d_sums = reinterpret_cast<uint64_t*>(p.d_extra);
+            const bool by_ids = per_kmer || m_idx->num_shards > 1;
+            if (by_ids || p.nb == 0) HIP_CHECK(hipMemsetAsync(d_sums, 0, p.n * sum_bytes, p.s));  // (the per-k-mer pass adds to its rows; no bases: no kernel at all)
+            if (by_ids) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, nullptr, nullptr, nullptr, nullptr, prefix->on(p.device), d_sums);
+            else if (p.nb) streaming_sums_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, prefix->on(p.device), d_sums, p.d_report, p.s, p.segments);
+            HIP_CHECK(hipMemcpyAsync(p.h_extra, d_sums, p.n * sum_bytes, hipMemcpyDeviceToHost, p.s));
         } else {
             piece_totals(*this, p.device, p.long_read, p.segments, p.d_bases, p.d_offsets, p.n, p.nb, p.d_report, p.s);
         }
         HIP_CHECK(hipStreamSynchronize(p.s));
         if (rows) std::memcpy(rows + 6 * p.first, p.h_extra, p.n * row_bytes);
+        else if (sums) std::memcpy(sums + 2 * p.first, p.h_extra, p.n * sum_bytes);
     });
 }
 
@@ -2281,6 +2479,59 @@ void depth_arrays::add_into(uint32_t* h_depth) const {
             for (uint64_t j = 0; j < n; ++j) h_depth[at + j] += part[j];
         }
     }
+}
+
+/* ---- the prefix sums of a host call's values: uploaded to every resident replica and built there; the 4-byte copy goes, the 8 bytes per
+        k-mer stay in HBM for as long as the object lives ---- */
+value_prefixes::value_prefixes(engine const& eng, uint32_t const* h_values, uint32_t at_least) : m_devices(resident_devices(eng)) {
+    const uint64_t n = eng.index().num_kmers;
+    int prev = 0;
+    HIP_CHECK(hipGetDevice(&prev));
+    void* values = nullptr;
+    try {
+        for (int device : m_devices) {
+            HIP_CHECK(hipSetDevice(device));
+            void* p = nullptr;
+            HIP_CHECK(hipMalloc(&p, (n + 1) * sizeof(uint64_t)));
+            m_prefix.push_back(static_cast<uint64_t*>(p));
+            HIP_CHECK(hipMalloc(&values, std::max<uint64_t>(n, 1) * sizeof(uint32_t)));
+            HIP_CHECK(hipMemcpy(values, h_values, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+            eng.value_prefix_device(device, static_cast<uint32_t const*>(values), at_least, m_prefix.back(), nullptr);
+            HIP_CHECK(hipStreamSynchronize(nullptr));  // (the lanes' streams do not wait for the null stream)
+            HIP_CHECK(hipFree(values));
+            values = nullptr;
+        }
+    } catch (...) {
+        if (values) (void)hipFree(values);
+        for (size_t i = 0; i < m_prefix.size(); ++i) {
+            (void)hipSetDevice(m_devices[i]);
+            (void)hipFree(m_prefix[i]);
+        }
+        (void)hipSetDevice(prev);
+        throw;
+    }
+    (void)hipSetDevice(prev);
+}
+
+value_prefixes::~value_prefixes() {
+    int prev = 0;
+    if (hipGetDevice(&prev) != hipSuccess) return;
+    for (size_t i = 0; i < m_prefix.size(); ++i) {
+        (void)hipSetDevice(m_devices[i]);
+        (void)hipFree(m_prefix[i]);
+    }
+    (void)hipSetDevice(prev);
+}
+
+uint64_t const* value_prefixes::on(int device) const {
+    for (size_t i = 0; i < m_devices.size(); ++i)
+        if (m_devices[i] == device) return m_prefix[i];
+    throw error(error_kind::internal, "no value prefix on this device");
+}
+
+streaming_report engine::streaming_sums_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, value_prefixes const& prefix,
+                                             uint64_t* sums) const {
+    return streaming_query_per_read_host(bases, read_offsets, n_reads, nullptr, nullptr, nullptr, &prefix, sums);
 }
 
 streaming_report engine::streaming_depth_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, depth_arrays const& depth) const {
