@@ -1,18 +1,22 @@
 #!/usr/bin/env python
-"""Worker of tests/test_gpu_forms_sweep.py, and the input generator it shares with tests/test_forms_sweep_inputs.py: EVERY output form
-of the streaming run kernel -- the batch counters, the per-read rows, the run records, the cover bitmap, the depth deltas -- and the
-segment machinery for long reads, at one point (k, m, length of the table's keys, replica layer), regular then canonical. The run forms
-do arithmetic the per-k-mer forms never do (kmer_id = offset - string_id * (k - 1), the first id of a backward run, a segment's end at
-+ S + k - 1, the first invalid base of a window, the funnel shift of a two-word seed), and the length of the table's keys is a parameter
-of its own (`hashed`, sk_key_persists); the points of the sweep are where these change: k = 33 (one base in the second word), m = k,
-m < 12, even m (a self-complementary m-mer ties the two strands), a key length on either side of m.
+"""Worker of tests/test_gpu_forms_sweep.py, and the input generator it shares with tests/test_forms_sweep_inputs.py: ALL SEVEN output
+forms of the streaming run kernel -- the batch counters, the per-read rows, the run counts and records, the cover bitmap, the depth
+deltas, the per-read sums over a value per k-mer -- and the segment machinery for long reads, at one point (k, m, length of the table's
+keys, replica layer), regular then canonical. The run forms do arithmetic the per-k-mer forms never do (kmer_id = offset - string_id *
+(k - 1), the first id of a backward run, a segment's end at + S + k - 1, the first invalid base of a window, the funnel shift of a
+two-word seed), and the length of the table's keys is a parameter of its own (`hashed`, sk_key_persists); the points of the sweep are
+where these change: k = 33 (one base in the second word; for the sums, the first k at which a run's two words of the prefix are added
+where the run is measured and not at the end of the turn), m = k, m < 12, even m (a self-complementary m-mer ties the two strands), a
+key length on either side of m.
 
 One worker process = one point (the replica layer and the key length are read from the environment when a replica is uploaded; the
 worker sets nothing itself and asserts from device_stats() that the setting took). On the CPU first (gate): the reads hold every kind
 of read, run and seam the kernels have a branch for, and the ids of the oracle's restated state machine equal GroundTruth.lookup of
-every valid k-mer of every read -- two references, neither of them the library's GPU path. Then every form through the host and the
-device entry point, uncut, cut into segments of 1, 7 and 64 k-mers, and uncut again; all comparisons exact. Prints one JSON line; any
-mismatch is an assertion error.
+every valid k-mer of every read -- two references, neither of them the library's GPU path. The sums have two references of their own,
+both numpy over the oracle's results: values[ids].sum() per read, and the kernel's formula restated -- per run record P[hi] - P[lo] over
+P = cumsum(values) --, asserted equal, over values under which a slip by one id at either end of any run changes the sum. Then every
+form through the host and the device entry point, uncut, cut into segments of 1, 7 and 64 k-mers, and uncut again; all comparisons
+exact. Prints one JSON line; any mismatch is an assertion error.
 
     python tests/gpu_forms_worker.py <k> <m> <key_length or 0> <layer: table|directory> <table_keys binary> <scratch dir> [--cpu-only]"""
 from __future__ import annotations
@@ -260,6 +264,82 @@ def string_of_ids(gt, k):
     return np.repeat(np.arange(sizes.size), sizes), sizes
 
 
+# ---- the sums: values, and two references in numpy ---------------------------------------------------------------------------------------
+ALL_ONES = 0xFFFFFFFF
+HALF = 1 << 31  # the threshold that about half of the random values pass
+BACKWARD = 0x80000000
+
+
+def sums_cases(n_kmers, seed):
+    """-> [(name, values, at_least)]: full-range random values (a run of two already carries across 2^32 as often as not), whether
+    they reach HALF, and all 0xFFFFFFFF"""
+    v = np.random.default_rng(seed).integers(0, 1 << 32, n_kmers, dtype=np.uint64).astype(np.uint32)
+    return [("random", v, 0), ("at least 2^31", v, HALF), ("all ones", np.full(n_kmers, ALL_ONES, dtype=np.uint32), 0)]
+
+
+def run_words(runs, n_kmers):
+    """per run record the two words of the prefix that the kernel reads (sums_run_anchor, sums_run_far), by orientation: the one that
+    does not depend on the run's length -- id forward, id + 1 backward -- and the one that does -- id + n forward, id + 1 - n backward
+    -> (anchor, far, n, forward). A backward run's ids go down from its first k-mer's."""
+    n = (runs["num_kmers"] & np.uint32(BACKWARD - 1)).astype(np.int64)
+    forward = (runs["num_kmers"] & np.uint32(BACKWARD)) == 0
+    kmer_id = runs["kmer_id"].astype(np.int64)
+    anchor = np.where(forward, kmer_id, kmer_id + 1)
+    far = np.where(forward, kmer_id + n, kmer_id + 1 - n)
+    assert (n >= 1).all() and (np.minimum(anchor, far) >= 0).all() and (np.maximum(anchor, far) <= n_kmers).all(), "a run outside the ids"
+    return anchor, far, n, forward
+
+
+def rows_from_runs(offsets, runs, values, at_least, n_kmers):
+    """the sums form's own formula in numpy, over the run records: per read the sum over its runs of P[hi] - P[lo], P the exclusive
+    prefix sums of the values in 64 bits, and of the runs' lengths"""
+    import sshash_amd
+
+    v = values.astype(np.uint64) if at_least == 0 else (values >= np.uint32(at_least)).astype(np.uint64)
+    P = np.zeros(n_kmers + 1, dtype=np.uint64)
+    np.cumsum(v, dtype=np.uint64, out=P[1:])
+    anchor, far, n, forward = run_words(runs, n_kmers)
+    worth = np.where(forward, P[far] - P[anchor], P[anchor] - P[far])  # (modulo 2^64, as the kernel)
+    read = np.repeat(np.arange(offsets.size - 1), np.diff(offsets.astype(np.int64)))
+    out = np.zeros(offsets.size - 1, dtype=sshash_amd.READ_SUM_DTYPE)
+    np.add.at(out["sum"], read, worth)
+    np.add.at(out["positive_kmers"], read, n.astype(np.uint64))
+    return out
+
+
+def neighbours_differ(runs, values, n_kmers):
+    """under `values` a run [lo, hi) that is read one id too low or too high, at one end or at both, sums to something else: the values
+    of the ids that would come in are not those of the ids that would go out, and none of them is zero. The ids below 0 and above the
+    last do not exist: the runs that begin at id 0 or end at the last id are asked for what there is
+    -> how many runs have no id below them, how many none above"""
+    anchor, far, n, forward = run_words(runs, n_kmers)
+    lo, hi = np.minimum(anchor, far), np.maximum(anchor, far)
+    assert (hi - lo == n).all()
+    v = values.astype(np.int64)
+    below, above = lo > 0, hi < n_kmers
+    assert (v[lo[below] - 1] != v[hi[below] - 1]).all(), "a run moved down by one id would sum to the same"
+    assert (v[lo[above]] != v[hi[above]]).all(), "a run moved up by one id would sum to the same"
+    assert (v[lo] != 0).all() and (v[hi - 1] != 0).all() and (v[lo[below] - 1] != 0).all() and (v[hi[above]] != 0).all(), "an end moved by one id would go unseen"
+    return int((~below).sum()), int((~above).sum())
+
+
+def sums_references(pt, cases, reads, ids, oracle):
+    """-> ({name: rows}, (run_offsets, run records)) the rows of `reads` under every case, from the oracle's ids per k-mer; asserted equal to the rows from
+    its run records"""
+    from gpu_runs_worker import oracle_runs
+    from gpu_sums_worker import flat_ids, rows_of
+    from gpu_sums_worker import same as same_rows
+
+    n_kmers = pt.case.gt.num_kmers
+    flat = flat_ids(ids)
+    offsets, runs = oracle_runs(oracle, reads)
+    want = {}
+    for name, values, at_least in cases:
+        want[name] = rows_of(flat, len(reads), values, at_least)
+        same_rows(rows_from_runs(offsets, runs, values, at_least, n_kmers), want[name], f"sums, {name}: P[hi] - P[lo] over the run records against values[ids].sum()")
+    return want, (offsets, runs)
+
+
 def gate(pt):
     """on the CPU, before any device call: every kind of read, run and seam is there, and the oracle's ids are the input's"""
     from gpu_cover_worker import bitmap_of
@@ -312,19 +392,67 @@ def gate(pt):
     hk, _, hids = classify(case.oracle, pt.repeated[:1], k)
     assert (hk[0] == np.array([2] + [3] * 100)).all(), "the repeated read is one run of 101 k-mers"
     pt.hot_ids = hids[0]
-    return {"kmers": n_kmers, "strings": len(pt.sequences), "reads": len(reads), "read_kmers": int(pt.want_totals[0]), "runs": int(pt.want_totals[4]),
+    # the sums: per read values[ids].sum() and the number of ids, and the same from the run records
+    pt.sums_cases = sums_cases(n_kmers, 7000 * k + 10 * pt.m + int(pt.canonical))
+    assert 0.4 < (pt.sums_cases[0][1] >= np.uint32(HALF)).mean() < 0.6
+    pt.want_sums, (pt.want_offsets, pt.want_runs) = sums_references(pt, pt.sums_cases, reads, pt.ids, case.oracle)
+    assert int(pt.want_offsets[-1]) == int(pt.want_totals[4])
+    for name, rows in pt.want_sums.items():
+        assert (rows["positive_kmers"] == pt.want_rows[:, 1]).all(), f"sums, {name}: positive_kmers against column 1 of the rows"
+    no_id_below, no_id_above = neighbours_differ(pt.want_runs, pt.sums_cases[0][1], n_kmers)
+    assert no_id_below > 0 and no_id_above > 0, "runs from id 0 and runs to the last id"
+    backward_runs = (pt.want_runs["num_kmers"] & np.uint32(BACKWARD)) != 0
+    assert backward_runs.any() and not backward_runs.all()
+    pt.batch = reads[:20] + [pt.long_reads[0], ""] + reads[20:40] + [pt.long_reads[1]]
+    batch_ids = pt.ids[:20] + [pt.long_ids[0], pt.ids[0][:0]] + pt.ids[20:40] + [pt.long_ids[1]]
+    pt.want_batch_sums, _ = sums_references(pt, pt.sums_cases, pt.batch, batch_ids, case.oracle)
+    pt.want_hot_sums, (_, hot_runs) = sums_references(pt, pt.sums_cases[:1], pt.repeated[:1], hids, case.oracle)
+    assert hot_runs.size == 1
+    sums = {"positive_kmers": int(pt.want_sums["random"]["positive_kmers"].sum(dtype=np.uint64)), "largest_row_sum": int(pt.want_sums["random"]["sum"].max()),
+            "largest_row_sum_of_the_long_reads": int(pt.want_batch_sums["all ones"]["sum"].max()), "runs": int(pt.want_runs.size),
+            "runs_without_an_id_below": no_id_below, "runs_without_an_id_above": no_id_above}
+    assert sums["positive_kmers"] == int(pt.want_totals[1]) > 0 and sums["largest_row_sum"] > (1 << 32)
+    return {"kmers": n_kmers, "sums": sums, "strings": len(pt.sequences), "reads": len(reads), "read_kmers": int(pt.want_totals[0]), "runs": int(pt.want_totals[4]),
             "seams_joined": {str(S): found[f"seam_in_forward_run@{S}"] + found[f"seam_in_backward_run@{S}"] for S in SEGMENT_SIZES}, "kinds": kinds,
             "floors": pt.floors}
 
 
 # ---- the device --------------------------------------------------------------------------------------------------------------------------
+def sums_everything(d, reads, cases, prefixes, device):
+    """the sums of `reads` under every case through the host call (device False), or through the device call over the case's prefix,
+    once with a report and once with a NULL report -> a dict of arrays, compared word for word (gpu_segments_worker.same)"""
+    from gpu_per_read_worker import report_row
+    from gpu_sums_worker import device_sums
+
+    out = {}
+    for (name, values, at_least), (_, p_prefix) in zip(cases, prefixes):
+        if device:
+            out[name], out[name + ": report"] = device_sums(d, reads, p_prefix, report=[0] * 6)
+            out[name + ": no report"], _ = device_sums(d, reads, p_prefix)
+        else:
+            rows, rep = d.streaming_sums(reads, values, at_least)
+            out[name], out[name + ": report"] = rows, report_row(rep)
+    return out
+
+
+def sums_wanted(want, cases, totals):
+    """-> (what sums_everything must give through the host calls, through the device calls)"""
+    host, device = {}, {}
+    for name, _, _ in cases:
+        host[name], host[name + ": report"] = want[name], totals
+    for name, _, _ in cases:
+        device[name], device[name + ": report"], device[name + ": no report"] = want[name], totals, want[name]
+    return host, device
+
+
 def check_flavour(pt, key_length, layer):
     import sshash_amd
     from gpu_cover_worker import bitmap_of, device_string_counts
     from gpu_depth_worker import depth_of, device_depth, device_string_sums
     from gpu_per_read_worker import oracle_rows
-    from gpu_runs_worker import check_both, oracle_runs
+    from gpu_runs_worker import check_both
     from gpu_segments_worker import accumulated, everything, launches, same
+    from gpu_sums_worker import device_prefix, device_sums
     from test_gpu_streaming import _as_dict
 
     case, k, m, reads = pt.case, pt.k, pt.m, pt.reads
@@ -338,16 +466,20 @@ def check_flavour(pt, key_length, layer):
     totals, rows, cover, depth = pt.want_totals, pt.want_rows, pt.want_cover, pt.want_depth
     want_host = {"totals": totals, "rows": rows, "rows_report": totals, "cover": cover, "cover_report": totals, "depth": depth, "depth_report": totals}
     want_device = dict(want_host, rows_no_report=rows, cover_no_report=cover, depth_no_report=depth)
+    cases = pt.sums_cases
+    sums_host, sums_device = sums_wanted(pt.want_sums, cases, totals)
 
-    # ---- uncut: the five forms, host and device (rows into a prefilled array between guard rows) ----
+    # ---- uncut: the seven forms, host and device (rows into a prefilled array between guard rows) ----
     assert d.read_segments()["kmers"] == sshash_amd.SEGMENTS_OFF, "a new dictionary does not segment"
     d.set_read_segments(sshash_amd.SEGMENTS_OFF, device_calls=True)
     assert _as_dict(d.streaming_query(reads)) == case.oracle.streaming_query(reads), f"{what}: streaming_query"
     assert (oracle_rows(case.oracle, reads) == rows).all()
     same(everything(d, reads, False), want_host, f"{what}: uncut, host calls")
     same(everything(d, reads, True), want_device, f"{what}: uncut, device calls")
-    want_offsets, want_runs = oracle_runs(case.oracle, reads)
-    assert int(want_offsets[-1]) == int(totals[4])
+    prefixes = [device_prefix(d, values, at_least) for _, values, at_least in cases]  # (against numpy.cumsum in 64 bits, guard words around it; held to the end)
+    same(sums_everything(d, reads, cases, prefixes, False), sums_host, f"{what}: sums uncut, host calls")
+    same(sums_everything(d, reads, cases, prefixes, True), sums_device, f"{what}: sums uncut, device calls")
+    want_offsets, want_runs = pt.want_offsets, pt.want_runs
     check_both(d, reads, want_offsets, want_runs, what)
     per_read, report = d.streaming_lookup(reads, full=True)
     assert _as_dict(report) == case.oracle.streaming_query(reads), f"{what}: streaming_lookup report"
@@ -381,9 +513,15 @@ def check_flavour(pt, key_length, layer):
     assert sorted(deltas[deltas != 0].tolist()) == ([REPEATS] if hi == n_kmers - 1 else [REPEATS, (1 << 32) - REPEATS]), f"{what}: the deltas of the repeated read"
     got, _ = d.streaming_depth(pt.repeated)
     assert (got == want_hot).all(), f"{what}: one read {REPEATS} times, host call"
+    want_hot_rows = np.repeat(pt.want_hot_sums["random"], REPEATS)
+    assert int(want_hot_rows["positive_kmers"][0]) == 101 and int(want_hot_rows["sum"][0]) > (1 << 32)
+    got, rep = device_sums(d, pt.repeated, prefixes[0][1], report=[0] * 6)
+    assert got.tobytes() == want_hot_rows.tobytes() and int(rep[1]) == 101 * REPEATS, f"{what}: sums, one read {REPEATS} times: {REPEATS} equal rows"
+    got, _ = d.streaming_sums(pt.repeated, cases[0][1])
+    assert got.tobytes() == want_hot_rows.tobytes(), f"{what}: sums, one read {REPEATS} times, host call"
 
     # ---- reads above 2^16 bases: the host calls (the position-parallel route), the device calls (one lane each) ----
-    batch = reads[:20] + [pt.long_reads[0], ""] + reads[20:40] + [pt.long_reads[1]]
+    batch = pt.batch
     bk, bids = pt.kinds[:20] + [pt.long_kinds[0], pt.kinds[0][:0]] + pt.kinds[20:40] + [pt.long_kinds[1]], pt.ids[:20] + pt.long_ids[:1] + pt.ids[20:40] + pt.long_ids[1:]
     brows = rows_of(bk)
     assert (brows == oracle_rows(case.oracle, batch)).all()
@@ -393,6 +531,9 @@ def check_flavour(pt, key_length, layer):
     long_device = dict(long_host, rows_no_report=brows, cover_no_report=bcover, depth_no_report=bdepth)
     same(everything(d, batch, False), long_host, f"{what}: the long reads uncut, host calls")
     same(everything(d, batch, True), long_device, f"{what}: the long reads uncut, device calls")
+    long_sums_host, long_sums_device = sums_wanted(pt.want_batch_sums, cases, brows.sum(0))
+    same(sums_everything(d, batch, cases, prefixes, False), long_sums_host, f"{what}: sums, the long reads uncut, host calls (the per-k-mer route)")
+    same(sums_everything(d, batch, cases, prefixes, True), long_sums_device, f"{what}: sums, the long reads uncut, device calls (one lane each)")
     assert launches(d) == 0, "SEGMENTS_OFF launched over segments"
 
     # ---- segments of S k-mers: byte for byte the uncut answers, also into arrays that hold values ----
@@ -416,6 +557,12 @@ def check_flavour(pt, key_length, layer):
         assert launches(d) > at, f"{what}: S = {S}: the device calls did not launch over segments"
         same(accumulated(d, reads, False, before_cover, before_depth), acc_host, f"{what}: S = {S}, host calls into arrays that hold values")
         same(accumulated(d, reads, True, before_cover, before_depth), acc_device, f"{what}: S = {S}, device calls into arrays that hold values")
+        at = launches(d)
+        same(sums_everything(d, reads, cases, prefixes, False), sums_host, f"{what}: sums, S = {S}, host calls")
+        assert launches(d) >= at + len(cases), f"{what}: S = {S}: the host calls of the sums did not launch over segments"
+        at = launches(d)
+        same(sums_everything(d, reads, cases, prefixes, True), sums_device, f"{what}: sums, S = {S}, device calls")
+        assert launches(d) == at + 2 * len(cases), f"{what}: S = {S}: every device call of the sums launches over segments once"
         segmented[str(S)] = launches(d)
     # ---- the long reads at the default S ----
     d.set_read_segments(device_calls=True)
@@ -425,12 +572,21 @@ def check_flavour(pt, key_length, layer):
     same(everything(d, batch, False), long_host, f"{what}: the long reads at the default S, host calls")
     same(everything(d, batch, True), long_device, f"{what}: the long reads at the default S, device calls")
     assert launches(d) > at
+    at = launches(d)
+    same(sums_everything(d, batch, cases, prefixes, False), long_sums_host, f"{what}: sums, the long reads at the default S, host calls")
+    assert launches(d) >= at + len(cases)
+    at = launches(d)
+    same(sums_everything(d, batch, cases, prefixes, True), long_sums_device, f"{what}: sums, the long reads at the default S, device calls")
+    assert launches(d) == at + 2 * len(cases)
     # ---- and off again ----
     d.set_read_segments(sshash_amd.SEGMENTS_OFF, device_calls=True)
     at = launches(d)
     same(everything(d, reads, False), want_host, f"{what}: SEGMENTS_OFF again, host calls")
     same(everything(d, reads, True), want_device, f"{what}: SEGMENTS_OFF again, device calls")
+    same(sums_everything(d, reads, cases, prefixes, False), sums_host, f"{what}: sums, SEGMENTS_OFF again, host calls")
+    same(sums_everything(d, reads, cases, prefixes, True), sums_device, f"{what}: sums, SEGMENTS_OFF again, device calls")
     assert launches(d) == at, "SEGMENTS_OFF launched over segments"
+    del prefixes
     d.close()
     return {"sk_slots": st["sk_slots"], "directory_sectors": st["directory_sectors"], "sk_key_length": st["sk_key_length"], "sk_heavy_kmers": st["sk_heavy_kmers"],
             "default_S": S, "segmented_launches": segmented}

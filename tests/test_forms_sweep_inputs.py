@@ -3,7 +3,12 @@ tests/gpu_forms_worker.py runs ahead of its first device call, for every row of 
 of read and of run (forward, backward, of one k-mer, of 64 and more, from id 0, to the last id, reads shorter than k, empty, without a
 hit, with N's), seams of every kind fall where segments of 1, 2, 7 and 64 k-mers are cut, the ids of the oracle's restated state machine
 equal GroundTruth.lookup of every valid k-mer of every read (the long reads above 2^16 bases among them), the repeated read is one run,
-and at an even m the reads walk over at least FLOOR tying k-mers of the dictionary."""
+and at an even m the reads walk over at least FLOOR tying k-mers of the dictionary. The sweep holds all seven forms of the run kernel:
+for the sums the gate computes, per read, values[ids].sum() and the number of ids over those oracle ids, and once more the kernel's
+own formula over the oracle's run records -- P[hi] - P[lo] over P = numpy.cumsum(values) in 64 bits, [lo, hi) from the record's kmer_id,
+its length and its backward bit -- and asserts the two equal, for full-range random values, for whether they reach 2^31, and for all
+0xFFFFFFFF; under the random values a run moved by one id, at either end or both, sums to something else, except where there is no
+such id: runs from id 0 and runs to the last id, of which there are some at every point."""
 from __future__ import annotations
 
 import pytest
@@ -29,9 +34,13 @@ def test_gate(k, m, key_length, layer, canonical, table_keys_exe, tmp_path):
     pt = make_inputs(k, m, key_length, canonical, table_keys_exe, str(tmp_path))
     got = gate(pt)  # (asserts every kind and both references)
     print(f"k={k} m={m} key={key_length} canonical={canonical}: {got['kmers']} k-mers in {got['strings']} strings, {got['reads']} reads, {got['runs']} runs, "
-          f"seams joined {got['seams_joined']}")
+          f"seams joined {got['seams_joined']}, sums {got['sums']}")
     assert 5000 <= got["kmers"] <= 80000 and all(got["seams_joined"][str(S)] > 0 for S in SEGMENT_SIZES)
     assert all(len(r) > (1 << 16) for r in pt.long_reads) and len(pt.repeated) == 4096
+    sums = got["sums"]
+    assert sums["runs"] == got["runs"] and sums["runs_without_an_id_below"] > 0 and sums["runs_without_an_id_above"] > 0
+    assert sums["positive_kmers"] > 0 and sums["largest_row_sum"] > (1 << 32) and sums["largest_row_sum_of_the_long_reads"] > 20000 * 0xFFFFFFFF
+    assert set(pt.want_sums) == set(pt.want_batch_sums) == {"random", "at least 2^31", "all ones"}
     if m % 2 == 0:
         assert all(c["read_kmers_found"] >= FLOOR for c in got["floors"].values()), got["floors"]
     else:
