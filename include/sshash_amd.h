@@ -259,18 +259,18 @@ sshash_status sshash_streaming_query_device(const sshash_dict* d, int device, co
  *      invalid whatever lies around it, so such a read can be cut: with S = kmers_per_segment a read of K k-mers becomes ceil(K / S)
  *      SEGMENTS of S k-mers (neighbours overlap by k - 1 bases; nothing is copied), one lane each. What differs is put right on the
  *      device: a segment's first k-mer counts as a search where in the whole read it may be an extension -- the rule of the runs
- *      below --, and a pass over the seams moves those back. The six counters, every per-read row, the cover, the depth and the sums
- *      are word for word what the uncut reads give.
+ *      below --, and a pass over the seams moves those back. The six counters, every per-read row, the cover, the depth, the sums and
+ *      the classes are word for word what the uncut reads give.
  *      Segmenting is OPT-IN: a new dictionary is at SSHASH_SEGMENTS_OFF with device_calls = 0 and takes the routes it always took.
  *      kmers_per_segment: 0 = the library's default S (256, RESULTS.md: best of 256, 1024, 4096 through the host call; the device calls
  *      favour 1024 slightly); SSHASH_SEGMENTS_OFF = never segment; otherwise 1 .. 2^30 (tiny values are allowed and only slow: tests
  *      put seams into small reads with them). Anything else, or a NULL dictionary, is SSHASH_ERR_ARGUMENT. Needs no device. Not to be changed while a call
  *      on the dictionary is in flight.
- *      Host and file calls (sshash_streaming_query, _per_read, _cover, _depth, _sums and their _from_file forms), once an S is set: a piece of
+ *      Host and file calls (sshash_streaming_query, _per_read, _cover, _depth, _sums, _classes and their _from_file forms), once an S is set: a piece of
  *      the batch that holds a read of more than S k-mers takes the run kernel over segments; pieces of shorter reads take exactly the launches they took
  *      before. With SSHASH_SEGMENTS_OFF a piece that holds a read above 2^16 bases goes through the position-parallel pipeline of
  *      sshash_streaming_lookup instead (one point lookup per k-mer, the same results).
- *      Device calls (sshash_streaming_query_device, _per_read_device, _cover_device, _depth_device, _sums_device): segment only with device_calls != 0
+ *      Device calls (sshash_streaming_query_device, _per_read_device, _cover_device, _depth_device, _sums_device, _classes_device): segment only with device_calls != 0
  *      -- they cannot see the reads' lengths without a synchronisation, and building the table costs a batch of short reads three small
  *      launches and a scan. With it: scratch of 24 bytes per segment (72 with rows) for at most num_reads + total_bases / S segments,
  *      sized from that bound without a synchronisation; the entries past the true count are empty and lie behind the last segment, so
@@ -501,6 +501,68 @@ sshash_status sshash_streaming_sums(const sshash_dict* d, const char* bases, con
 typedef int (*sshash_read_sums_fn)(void* ctx, uint64_t first_read, uint64_t n, const sshash_read_sum* sums);
 sshash_status sshash_streaming_sums_from_file(const sshash_dict* d, const char* filename, int multiline, const uint32_t* values,
                                               uint32_t at_least, sshash_read_sums_fn fn, void* ctx, sshash_streaming_report* report);
+
+/* ---- CLASSES: per read, its positive k-mers by class of string -- WHOSE a read's hits are (no reference counterpart as a call). `labels`
+ *      holds num_strings words of uint32_t, word s the class of string s (sshash_lookup_result.string_id): a reference genome, a taxon, a
+ *      colour-set id, host / target / contaminant, plasmid / chromosome. With C = num_classes, 1 <= C <= SSHASH_MAX_CLASSES, the output is
+ *      num_reads x C words of uint32_t, row-major:
+ *          rows[r * C + c] = the number of places of read r where sshash_streaming_lookup returns a k-mer whose string_id s has
+ *                            labels[s] == c;
+ *      every strand counts, every occurrence counts. A label >= C means "no class": its k-mers are positive in the report and counted in
+ *      no column, which doubles as a mask. A read shorter than k, an empty read and a read without a hit have a row of zeros. Rows are
+ *      OVERWRITTEN, every one of them; nothing outside rows[0 .. num_reads * C) is written. All arithmetic is modulo 2^32. 4-byte
+ *      alignment is all that is asked of `rows`. Above SSHASH_MAX_CLASSES a dense row is the wrong shape: sshash_streaming_runs stays
+ *      the route.
+ *      Preconditions and status codes as the sums calls: a null dictionary, or null bases / read_offsets / labels / rows with
+ *      num_reads > 0, is SSHASH_ERR_ARGUMENT, and so is num_classes == 0 or above SSHASH_MAX_CLASSES, all before anything runs;
+ *      num_reads == 0 succeeds and touches nothing; a dictionary that is not resident is SSHASH_ERR_NO_DEVICE. A minimizer shard
+ *      (num_shards > 1) counts the k-mers it owns and no others, so the shards' rows added together are the rows of the whole index;
+ *      for that a shard's host and file calls look every k-mer up on its own (the pipeline of sshash_streaming_lookup), and
+ *      sshash_streaming_classes_device, which is the run kernel, is SSHASH_ERR_ARGUMENT on a minimizer shard -- as
+ *      sshash_streaming_sums_device and for its reason.
+ *      Segments (sshash_set_read_segments): as the sums calls; many lanes then add into one row, and the rows are word for word what the
+ *      uncut reads give. ---- */
+#define SSHASH_MAX_CLASSES 4096u
+/* device buffers, asynchronous on hip_stream. labels: num_strings uint32, only read. rows: num_reads * num_classes uint32, OVERWRITTEN.
+ * report and total_bases as for sshash_streaming_depth_device. Always the run kernel: the rows are zeroed (one memset) and ONE launch
+ * adds every run's length to the column of its string's label in its read's row -- a run lies in one string: one 4-byte load and one
+ * 32-bit atomic add that nothing waits for, whatever the run's length; no scratch beyond that of sshash_streaming_query_device. */
+sshash_status sshash_streaming_classes_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
+                                              uint64_t num_reads, uint64_t total_bases, const uint32_t* labels, uint32_t num_classes,
+                                              uint32_t* rows, uint64_t* report, void* hip_stream);
+/* host buffers, sharded over all resident replicas like sshash_streaming_sums. labels: host, num_strings uint32, uploaded once per call to
+ * every resident replica. A piece of the batch holds no more reads than make 64 MiB of rows (4096 reads at 4096 classes) and travels
+ * through the lanes' pinned blocks. A piece that holds a read above 2^16 bases, with segments off, goes through the position-parallel
+ * pipeline of sshash_streaming_lookup and is counted from its per-k-mer string ids, which gives the same rows. report may be NULL. */
+sshash_status sshash_streaming_classes(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
+                                       const uint32_t* labels, uint32_t num_classes, uint32_t* rows, sshash_streaming_report* report);
+/* a query file: the contract of sshash_streaming_sums_from_file -- rows are handed over in batches, IN FILE ORDER, one row of num_classes
+ * words for EVERY record of the file, one call of `fn` at a time; a non-zero return of `fn` stops the query (SSHASH_ERR_ARGUMENT,
+ * sshash_last_error() carries the value). The labels stay in the HBM of every replica for the whole file. report may be NULL. */
+typedef int (*sshash_read_classes_fn)(void* ctx, uint64_t first_read, uint64_t n, const uint32_t* rows);
+sshash_status sshash_streaming_classes_from_file(const sshash_dict* d, const char* filename, int multiline, const uint32_t* labels,
+                                                 uint32_t num_classes, sshash_read_classes_fn fn, void* ctx, sshash_streaming_report* report);
+
+/* The finish of the rows. BEST: one sshash_read_class per read -- the class with the largest count (among equals the smallest class), that
+ * count, the largest count among the OTHER classes (equal to `best` on a tie), and the row's sum modulo 2^32; a row of zeros gives
+ * {SSHASH_NO_CLASS, 0, 0, 0}. TOTALS: totals[c] = the 64-bit sum of column c over the reads, num_classes uint64 -- the sample's profile
+ * by class. Both OVERWRITE their output. The _device forms take device pointers and are asynchronous on hip_stream (best: a group of
+ * min(64, the power of two at or above num_classes) lanes per read; totals: one 64-bit atomic per column and workgroup); the others are
+ * plain host code over host arrays and need no dictionary. NULL rows or output with num_reads > 0 (totals: a NULL output always),
+ * num_classes == 0 or above SSHASH_MAX_CLASSES: SSHASH_ERR_ARGUMENT. */
+#define SSHASH_NO_CLASS 0xFFFFFFFFu
+typedef struct sshash_read_class {
+    uint32_t best_class; /* SSHASH_NO_CLASS: the row is all zeros */
+    uint32_t best;
+    uint32_t second;
+    uint32_t total;
+} sshash_read_class;
+sshash_status sshash_class_best_device(const sshash_dict* d, int device, const uint32_t* rows, uint64_t num_reads, uint32_t num_classes,
+                                       sshash_read_class* best, void* hip_stream);
+sshash_status sshash_class_best(const uint32_t* rows, uint64_t num_reads, uint32_t num_classes, sshash_read_class* best);
+sshash_status sshash_class_totals_device(const sshash_dict* d, int device, const uint32_t* rows, uint64_t num_reads, uint32_t num_classes,
+                                         uint64_t* totals, void* hip_stream);
+sshash_status sshash_class_totals(const uint32_t* rows, uint64_t num_reads, uint32_t num_classes, uint64_t* totals);
 
 /* ---- streaming_query<Dict,canonical>::lookup for EVERY k-mer of every read (include/streaming_query.hpp:56-109),
  *      batched: what the reference returns k-mer by k-mer while it streams a read. Every non-NULL array of `out` has one

@@ -447,6 +447,62 @@ public:
         return to_report(s);
     }
 
+    /* CLASSES (sshash_streaming_classes; the definitions are in include/sshash_amd.h): per read, its positive k-mers by class of string.
+       `labels`: num_strings() words, a label >= num_classes is no class; `rows` is sized to num_reads x num_classes, row-major, and
+       overwritten. Returns the batch's report. */
+    streaming_query_report streaming_classes(char const* bases, uint64_t const* read_offsets, uint64_t num_reads, std::vector<uint32_t> const& labels,
+                                             uint32_t num_classes, std::vector<uint32_t>& rows) const {
+        if (labels.size() < num_strings()) throw std::invalid_argument("labels has fewer than num_strings() words");
+        rows.assign(num_reads * uint64_t(num_classes), 0u);
+        std::vector<uint32_t> spare(1);
+        sshash_streaming_report s;
+        check(sshash_streaming_classes(m_h, bases, read_offsets, num_reads, labels.empty() ? spare.data() : labels.data(), num_classes,
+                                       rows.empty() ? spare.data() : rows.data(), &s));
+        return to_report(s);
+    }
+    /* device buffers, asynchronous on hip_stream: d_rows -- num_reads x num_classes uint32 -- is overwritten, d_labels -- num_strings()
+       uint32 -- only read, d_report -- may be null -- six counters (accumulated into) */
+    void streaming_classes_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t num_reads, uint64_t total_bases,
+                                  uint32_t const* d_labels, uint32_t num_classes, uint32_t* d_rows, uint64_t* d_report, void* hip_stream) const {
+        check(sshash_streaming_classes_device(m_h, device, d_bases, d_read_offsets, num_reads, total_bases, d_labels, num_classes, d_rows, d_report, hip_stream));
+    }
+    /* a query file, one row per record, handed over in file order: fn(first_read, rows, n) for one batch after the other, rows n x
+       num_classes words; a non-zero return stops the query (std::runtime_error). Fn: int(uint64_t, uint32_t const*, uint64_t). */
+    template <typename Fn>
+    streaming_query_report streaming_classes_from_file(std::string const& filename, bool multiline, std::vector<uint32_t> const& labels,
+                                                       uint32_t num_classes, Fn&& fn) const {
+        if (labels.size() < num_strings()) throw std::invalid_argument("labels has fewer than num_strings() words");
+        struct context {
+            std::remove_reference_t<Fn>* fn;
+        } ctx{&fn};
+        std::vector<uint32_t> spare(1);
+        sshash_streaming_report s;
+        check(sshash_streaming_classes_from_file(
+            m_h, filename.c_str(), multiline, labels.empty() ? spare.data() : labels.data(), num_classes,
+            [](void* c, uint64_t first_read, uint64_t n, const uint32_t* rows) -> int { return int((*static_cast<context*>(c)->fn)(first_read, rows, n)); },
+            &ctx, &s));
+        return to_report(s);
+    }
+    /* the finish of the rows (sshash_class_best, sshash_class_totals): on the host over host arrays, or device buffers, asynchronous */
+    static std::vector<sshash_read_class> class_best(std::vector<uint32_t> const& rows, uint32_t num_classes) {
+        if (num_classes == 0 || rows.size() % num_classes) throw std::invalid_argument("rows is not a whole number of rows");
+        std::vector<sshash_read_class> best(rows.size() / num_classes);
+        check(sshash_class_best(rows.data(), best.size(), num_classes, best.data()));
+        return best;
+    }
+    static std::vector<uint64_t> class_totals(std::vector<uint32_t> const& rows, uint32_t num_classes) {
+        if (num_classes == 0 || rows.size() % num_classes) throw std::invalid_argument("rows is not a whole number of rows");
+        std::vector<uint64_t> totals(num_classes);
+        check(sshash_class_totals(rows.data(), rows.size() / num_classes, num_classes, totals.data()));
+        return totals;
+    }
+    void class_best_device(int device, uint32_t const* d_rows, uint64_t num_reads, uint32_t num_classes, sshash_read_class* d_best, void* hip_stream) const {
+        check(sshash_class_best_device(m_h, device, d_rows, num_reads, num_classes, d_best, hip_stream));
+    }
+    void class_totals_device(int device, uint32_t const* d_rows, uint64_t num_reads, uint32_t num_classes, uint64_t* d_totals, void* hip_stream) const {
+        check(sshash_class_totals_device(m_h, device, d_rows, num_reads, num_classes, d_totals, hip_stream));
+    }
+
     /* a query file, one row per record, handed over in file order: fn(first_read, rows, n) for one batch after the other; a
        non-zero return stops the query (std::runtime_error). Fn: int(uint64_t, streaming_query_report const*, uint64_t). */
     template <typename Fn>

@@ -12,6 +12,9 @@ Method names and argument meaning follow ``sshash::dictionary`` (reference
 """
 from ._binding import (  # noqa: F401
     INVALID_U64,
+    MAX_CLASSES,
+    NO_CLASS,
+    READ_CLASS_DTYPE,
     READ_SUM_DTYPE,
     SEGMENTS_OFF,
     RUN_BACKWARD,
@@ -20,6 +23,8 @@ from ._binding import (  # noqa: F401
     LookupResult,
     SSHashError,
     StreamingQueryReport,
+    class_best,
+    class_totals,
     cover_to_ids,
     device_count,
     encode_kmers,
@@ -31,6 +36,9 @@ from ._binding import (  # noqa: F401
 
 __all__ = [
     "INVALID_U64",
+    "MAX_CLASSES",
+    "NO_CLASS",
+    "READ_CLASS_DTYPE",
     "READ_SUM_DTYPE",
     "SEGMENTS_OFF",
     "RUN_BACKWARD",
@@ -39,6 +47,8 @@ __all__ = [
     "LookupResult",
     "SSHashError",
     "StreamingQueryReport",
+    "class_best",
+    "class_totals",
     "cover_to_ids",
     "device_count",
     "encode_kmers",

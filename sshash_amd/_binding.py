@@ -112,6 +112,10 @@ _lib: Optional[C.CDLL] = None
 _PerReadFn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p)
 # sshash_read_sum (include/sshash_amd.h): a read's row of streaming_sums
 READ_SUM_DTYPE = np.dtype([("sum", "<u8"), ("positive_kmers", "<u8")])
+# sshash_read_class: a read's row of streaming_classes, finished by class_best
+READ_CLASS_DTYPE = np.dtype([("best_class", "<u4"), ("best", "<u4"), ("second", "<u4"), ("total", "<u4")])
+MAX_CLASSES = 4096  # SSHASH_MAX_CLASSES
+NO_CLASS = 0xFFFFFFFF  # SSHASH_NO_CLASS: best_class of a row of zeros
 
 
 def _preload_hip_runtime() -> None:
@@ -214,6 +218,13 @@ def _load() -> C.CDLL:
         "sshash_streaming_sums_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, P, P, P]),
         "sshash_streaming_sums": (C.c_int, [P, P, P, C.c_uint64, P, C.c_uint32, P, C.POINTER(_Report)]),
         "sshash_streaming_sums_from_file": (C.c_int, [P, C.c_char_p, C.c_int, P, C.c_uint32, _PerReadFn, P, C.POINTER(_Report)]),
+        "sshash_streaming_classes_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, C.c_uint32, P, P, P]),
+        "sshash_streaming_classes": (C.c_int, [P, P, P, C.c_uint64, P, C.c_uint32, P, C.POINTER(_Report)]),
+        "sshash_streaming_classes_from_file": (C.c_int, [P, C.c_char_p, C.c_int, P, C.c_uint32, _PerReadFn, P, C.POINTER(_Report)]),
+        "sshash_class_best_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P]),
+        "sshash_class_best": (C.c_int, [P, C.c_uint64, C.c_uint32, P]),
+        "sshash_class_totals_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P]),
+        "sshash_class_totals": (C.c_int, [P, C.c_uint64, C.c_uint32, P]),
         "sshash_route_packed_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P, P]),
         "sshash_route_bucket_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, C.c_int, P, P, P, P]),
         "sshash_route_bucket_by_key_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P, P, P]),
@@ -245,6 +256,8 @@ C_ABI_SYMBOLS = (
     "sshash_streaming_depth sshash_streaming_depth_device sshash_depth_finish_device sshash_streaming_depth_from_file "
     "sshash_depth_string_sums sshash_depth_string_sums_device sshash_set_read_segments sshash_get_read_segments "
     "sshash_value_prefix_device sshash_streaming_sums sshash_streaming_sums_device sshash_streaming_sums_from_file "
+    "sshash_streaming_classes sshash_streaming_classes_device sshash_streaming_classes_from_file "
+    "sshash_class_best sshash_class_best_device sshash_class_totals sshash_class_totals_device "
     "sshash_streaming_lookup sshash_streaming_lookup_device sshash_sharded_lookup_device sshash_sharded_lookup_rccl "
     "sshash_route_packed_device sshash_route_bucket_device sshash_route_bucket_by_key_device sshash_route_combine_device "
     "sshash_iterate_packed sshash_iterate_packed_device sshash_check_device"
@@ -991,6 +1004,90 @@ class Dictionary:
             return (np.concatenate(kept) if kept else np.zeros(0, dtype=READ_SUM_DTYPE)), self._report(r)
         return self._report(r)
 
+    # ---- streaming classes: a read's positive k-mers by class of string --------------------------------
+    def _labels_array(self, labels, num_classes: int) -> np.ndarray:
+        """`labels` as the calls want it: num_strings() uint32, contiguous."""
+        n = self.num_strings()
+        if not 1 <= int(num_classes) <= MAX_CLASSES:
+            raise ValueError(f"num_classes: 1 .. {MAX_CLASSES}")
+        labels = np.asarray(labels)
+        if labels.ndim != 1 or labels.size != n or labels.dtype.kind not in "ui":
+            raise ValueError(f"labels: {n} unsigned integers, one per string id")
+        if labels.dtype != np.uint32:
+            if labels.size and (int(labels.min()) < 0 or int(labels.max()) >> 32):
+                raise ValueError("labels: every one of them within 32 bits")
+            labels = labels.astype(np.uint32)
+        return np.ascontiguousarray(labels)
+
+    def streaming_classes_device(self, device: int, d_bases: int, d_read_offsets: int, num_reads: int, d_labels: int, num_classes: int,
+                                 d_rows: int, d_report: int = 0, stream: int = 0, total_bases: int = 0) -> None:
+        """Device buffers: d_rows receives num_reads x num_classes uint32 (overwritten; 4-byte aligned), out of d_labels (num_strings()
+        uint32, only read); d_report (0: none) six counters (accumulated into). `total_bases` as for streaming_query_device."""
+        _check(_load().sshash_streaming_classes_device(self._h, int(device), C.c_void_p(d_bases), C.c_void_p(d_read_offsets), int(num_reads),
+                                                       int(total_bases), C.c_void_p(d_labels), int(num_classes), C.c_void_p(d_rows),
+                                                       C.c_void_p(d_report), C.c_void_p(stream)))
+
+    def streaming_classes(self, reads: Sequence[Union[str, bytes]], labels, num_classes: int):
+        """Whose a read's hits are -> (rows, StreamingQueryReport): rows is an (n, num_classes) uint32 array, rows[r, c] = the number of
+        places of read r where streaming_lookup returns a k-mer whose string s has labels[s] == c (either strand, every occurrence;
+        modulo 2^32). `labels`: num_strings() integers within 32 bits; a label >= num_classes is no class and counted in no column."""
+        labels = self._labels_array(labels, num_classes)
+        chunks = [s.encode("ascii", "replace") if isinstance(s, str) else bytes(s) for s in reads]
+        offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
+        if chunks:
+            offsets[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
+        bases = np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8)
+        rows = np.zeros((len(chunks), int(num_classes)), dtype=np.uint32)
+        r = _Report()
+        _check(_load().sshash_streaming_classes(self._h, bases.ctypes.data, offsets.ctypes.data, len(chunks),
+                                                labels.ctypes.data if labels.size else bases.ctypes.data, int(num_classes),
+                                                rows.ctypes.data if len(chunks) else None, C.byref(r)))
+        return rows, self._report(r)
+
+    def streaming_classes_from_file(self, filename: str, labels, num_classes: int, multiline: bool = False,
+                                    per_read: Optional[Callable[[int, np.ndarray], Optional[int]]] = None):
+        """A query file classified like streaming_classes. per_read(first_read, rows) is called for one batch of the file after the
+        other, in file order, rows an (n, num_classes) uint32 array with row i for record first_read + i (every record has a row); a
+        return value other than None / 0 stops the query (SSHashError), an exception raised by the callable stops it too and is raised
+        again here. per_read=None: -> (rows of the whole file, StreamingQueryReport); otherwise -> StreamingQueryReport."""
+        labels = self._labels_array(labels, num_classes)
+        r = _Report()
+        raised, kept = [], []
+
+        def hand_over(_ctx, first_read, n, rows):
+            try:
+                block = np.ctypeslib.as_array(C.cast(rows, C.POINTER(C.c_uint32)), shape=(int(n), int(num_classes))).copy()
+                if per_read is None:
+                    kept.append(block)
+                    return 0
+                stop = per_read(int(first_read), block)
+                return int(stop) if stop else 0
+            except BaseException as e:  # (must not travel through the C frames)
+                raised.append(e)
+                return -1
+
+        fn = _PerReadFn(hand_over)
+        spare = np.zeros(1, dtype=np.uint32)
+        status = _load().sshash_streaming_classes_from_file(self._h, os.fsencode(filename), 1 if multiline else 0,
+                                                            labels.ctypes.data if labels.size else spare.ctypes.data, int(num_classes), fn, None,
+                                                            C.byref(r))
+        if raised:
+            raise raised[0]
+        _check(status)
+        if per_read is None:
+            return (np.concatenate(kept) if kept else np.zeros((0, int(num_classes)), dtype=np.uint32)), self._report(r)
+        return self._report(r)
+
+    def class_best_device(self, device: int, d_rows: int, num_reads: int, num_classes: int, d_best: int, stream: int = 0) -> None:
+        """Device buffers: d_best receives num_reads rows of READ_CLASS_DTYPE (overwritten) out of d_rows (num_reads x num_classes uint32)."""
+        _check(_load().sshash_class_best_device(self._h, int(device), C.c_void_p(d_rows), int(num_reads), int(num_classes), C.c_void_p(d_best),
+                                                C.c_void_p(stream)))
+
+    def class_totals_device(self, device: int, d_rows: int, num_reads: int, num_classes: int, d_totals: int, stream: int = 0) -> None:
+        """Device buffers: d_totals receives num_classes uint64 (overwritten), the sum of every column of d_rows over the reads."""
+        _check(_load().sshash_class_totals_device(self._h, int(device), C.c_void_p(d_rows), int(num_reads), int(num_classes), C.c_void_p(d_totals),
+                                                  C.c_void_p(stream)))
+
     def streaming_lookup(self, reads: Sequence[Union[str, bytes]], full: bool = False):
         """streaming_query::lookup for every k-mer of every read (reference include/streaming_query.hpp:56-109), batched.
         -> (list of LookupResult, one per read, len(read) - k + 1 entries each; StreamingQueryReport)."""
@@ -1105,6 +1202,38 @@ def write_weighted_fasta(d: "Dictionary", depth, path: str) -> None:
                 counts = " ".join(map(str, depth[lo + a:lo + a + n].tolist()))
                 f.write(f">{s} LN:i:{len(text)} ab:Z:{counts}\n{text.decode('ascii')}\n")
             s0 = s1
+
+
+def _class_rows(rows) -> np.ndarray:
+    """`rows` as the finish calls want them: (reads, classes) uint32, contiguous. Refused as the labels are: nothing is cast that would
+    change a count."""
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or not 1 <= rows.shape[1] <= MAX_CLASSES or rows.dtype.kind not in "ui":
+        raise ValueError(f"rows: (reads, classes) unsigned integers with 1 .. {MAX_CLASSES} classes")
+    if rows.dtype != np.uint32:
+        if rows.size and (int(rows.min()) < 0 or int(rows.max()) >> 32):
+            raise ValueError("rows: every count within 32 bits")
+        rows = rows.astype(np.uint32)
+    return np.ascontiguousarray(rows)
+
+
+def class_best(rows) -> np.ndarray:
+    """The finish of streaming_classes on the host (sshash_class_best) -> a READ_CLASS_DTYPE array, one entry per row: the class with the
+    largest count (among equals the smallest), that count, the largest count among the other classes, the row's sum modulo 2^32; a
+    row of zeros: (NO_CLASS, 0, 0, 0)."""
+    rows = _class_rows(rows)
+    best = np.zeros(rows.shape[0], dtype=READ_CLASS_DTYPE)
+    _check(_load().sshash_class_best(rows.ctypes.data if rows.shape[0] else None, rows.shape[0], rows.shape[1],
+                                     best.ctypes.data if rows.shape[0] else None))
+    return best
+
+
+def class_totals(rows) -> np.ndarray:
+    """The 64-bit sum of every column of streaming_classes' rows over the reads (sshash_class_totals): the sample's profile by class."""
+    rows = _class_rows(rows)
+    totals = np.zeros(rows.shape[1], dtype=np.uint64)
+    _check(_load().sshash_class_totals(rows.ctypes.data if rows.shape[0] else None, rows.shape[0], rows.shape[1], totals.ctypes.data))
+    return totals
 
 
 def cover_to_ids(cover) -> np.ndarray:

@@ -774,6 +774,110 @@ sshash_status sshash_streaming_sums_from_file(const sshash_dict* d, const char* 
     });
 }
 
+static_assert(sizeof(sshash_read_class) == 4 * sizeof(uint32_t), "a read's class is four words");
+static_assert(SSHASH_MAX_CLASSES == engine::MAX_CLASSES, "one cap");
+
+static bool classes_in_range(uint32_t num_classes) { return num_classes >= 1 && num_classes <= SSHASH_MAX_CLASSES; }
+
+sshash_status sshash_streaming_classes_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
+                                              uint64_t num_reads, uint64_t total_bases, const uint32_t* labels, uint32_t num_classes,
+                                              uint32_t* rows, uint64_t* report, void* hip_stream) {
+    if (!d || (num_reads && (!bases || !read_offsets || !labels || !rows))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (!classes_in_range(num_classes)) return fail(SSHASH_ERR_ARGUMENT, "num_classes must be 1 .. SSHASH_MAX_CLASSES");
+    return guarded([&] {
+        d->eng->streaming_classes_device(device, bases, read_offsets, num_reads, total_bases, labels, num_classes, rows, report, hip_stream);
+    });
+}
+
+sshash_status sshash_streaming_classes(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
+                                       const uint32_t* labels, uint32_t num_classes, uint32_t* rows, sshash_streaming_report* report) {
+    if (!d || (num_reads && (!bases || !read_offsets || !labels || !rows))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (!classes_in_range(num_classes)) return fail(SSHASH_ERR_ARGUMENT, "num_classes must be 1 .. SSHASH_MAX_CLASSES");
+    if (report) std::memset(report, 0, sizeof(*report));
+    return guarded([&] {
+        if (num_reads == 0) return;
+        const class_labels_on_devices on_devices(*d->eng, labels);
+        const streaming_report r = d->eng->streaming_classes_host(bases, read_offsets, num_reads, on_devices, num_classes, rows);
+        if (report) fill_report(report, r);
+    });
+}
+
+sshash_status sshash_streaming_classes_from_file(const sshash_dict* d, const char* filename, int multiline, const uint32_t* labels,
+                                                 uint32_t num_classes, sshash_read_classes_fn fn, void* ctx, sshash_streaming_report* report) {
+    if (!d || !filename || !labels || !fn) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (!classes_in_range(num_classes)) return fail(SSHASH_ERR_ARGUMENT, "num_classes must be 1 .. SSHASH_MAX_CLASSES");
+    if (report) std::memset(report, 0, sizeof(*report));
+    return guarded([&] {
+        read_stream in(filename, multiline != 0, d->idx->k, true);  // (every record of the file: row i is record i)
+        if (!in.supported()) {
+            fprintf(stderr, "unsupported query file format\n");
+            return;
+        }
+        /* the sequential reader, as sshash_streaming_sums_from_file; the labels stay on the devices from the first batch to the last */
+        const class_labels_on_devices on_devices(*d->eng, labels);
+        streaming_report total;
+        uint64_t first_read = 0;
+        std::vector<uint32_t> rows;
+        for_each_batch(in, [&](read_batch const& batch) {
+            const uint64_t n = batch.num_reads();
+            if (n == 0) return;
+            rows.resize(n * num_classes);
+            total += d->eng->streaming_classes_host(batch.bases.data(), batch.offsets.data(), n, on_devices, num_classes, rows.data());
+            if (report) fill_report(report, total);
+            const int stop = fn(ctx, first_read, n, rows.data());
+            if (stop) throw error(error_kind::argument, "the per-read callback returned " + std::to_string(stop));
+            first_read += n;
+        });
+    });
+}
+
+sshash_status sshash_class_best_device(const sshash_dict* d, int device, const uint32_t* rows, uint64_t num_reads, uint32_t num_classes,
+                                       sshash_read_class* best, void* hip_stream) {
+    if (!d || (num_reads && (!rows || !best))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (!classes_in_range(num_classes)) return fail(SSHASH_ERR_ARGUMENT, "num_classes must be 1 .. SSHASH_MAX_CLASSES");
+    return guarded([&] { d->eng->class_best_device(device, rows, num_reads, num_classes, reinterpret_cast<uint32_t*>(best), hip_stream); });
+}
+
+sshash_status sshash_class_best(const uint32_t* rows, uint64_t num_reads, uint32_t num_classes, sshash_read_class* best) {
+    if (num_reads && (!rows || !best)) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (!classes_in_range(num_classes)) return fail(SSHASH_ERR_ARGUMENT, "num_classes must be 1 .. SSHASH_MAX_CLASSES");
+    return guarded([&] {
+        for (uint64_t r = 0; r < num_reads; ++r) {
+            const uint32_t* const row = rows + r * num_classes;
+            sshash_read_class out{SSHASH_NO_CLASS, 0, 0, 0};
+            for (uint32_t c = 0; c < num_classes; ++c) {  // (ascending, and only a LARGER count takes the lead: among equals the smallest class)
+                const uint32_t v = row[c];
+                out.total += v;
+                if (v > out.best) {
+                    out.second = out.best;
+                    out.best = v;
+                    out.best_class = c;
+                } else if (v > out.second) {
+                    out.second = v;
+                }
+            }
+            best[r] = out;
+        }
+    });
+}
+
+sshash_status sshash_class_totals_device(const sshash_dict* d, int device, const uint32_t* rows, uint64_t num_reads, uint32_t num_classes,
+                                         uint64_t* totals, void* hip_stream) {
+    if (!d || !totals || (num_reads && !rows)) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (!classes_in_range(num_classes)) return fail(SSHASH_ERR_ARGUMENT, "num_classes must be 1 .. SSHASH_MAX_CLASSES");
+    return guarded([&] { d->eng->class_totals_device(device, rows, num_reads, num_classes, totals, hip_stream); });
+}
+
+sshash_status sshash_class_totals(const uint32_t* rows, uint64_t num_reads, uint32_t num_classes, uint64_t* totals) {
+    if (!totals || (num_reads && !rows)) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (!classes_in_range(num_classes)) return fail(SSHASH_ERR_ARGUMENT, "num_classes must be 1 .. SSHASH_MAX_CLASSES");
+    return guarded([&] {
+        std::fill(totals, totals + num_classes, uint64_t(0));
+        for (uint64_t r = 0; r < num_reads; ++r)
+            for (uint32_t c = 0; c < num_classes; ++c) totals[c] += rows[r * num_classes + c];
+    });
+}
+
 sshash_status sshash_streaming_lookup_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
                                              uint64_t num_reads, uint64_t total_bases, const sshash_results* out, uint64_t* report,
                                              void* hip_stream) {

@@ -45,14 +45,27 @@ struct streaming_report {  // streaming_query_report, include/util.hpp:21-36
 /* where the runs of a streaming call go (streaming.hip), device pointers: run_offsets -- n_reads + 1 words, CSR --, the records
    (sshash_streaming_run, include/sshash_amd.h) and how many of them there is room for. The sums form alone reads the two members
    behind them: the prefix sums of the values (num_kmers + 1 words) -- its rows, two words a read, are at `records` -- and, for reads cut
-   into segments, the read of every entry of the segment table (null: an entry is a read). */
+   into segments, the read of every entry of the segment table (null: an entry is a read). The classes form keeps its rows at `records`
+   as well and `read_of` as the sums form; the struct is not grown for it (every instantiation of the run kernel takes it by value, and
+   its size and offsets are what they were): the number of classes shares the word of `capacity` and the labels, one 32-bit word per
+   string, the word of `values_prefix`. A sink is of one form from its making on -- class_sink (streaming.hip) makes the classes form's --,
+   so only the member that was written is ever read. */
 struct run_sink {
     uint64_t* run_offsets;
     void* records;
-    uint64_t capacity;
-    uint64_t const* values_prefix;
+    union {
+        uint64_t capacity;     // the records form: room for so many records
+        uint64_t num_classes;  // the classes form: words in a row
+    };
+    union {
+        uint64_t const* values_prefix;  // the sums form
+        uint32_t const* labels;         // the classes form
+    };
     uint64_t const* read_of;
+    run_sink(uint64_t* offsets, void* recs, uint64_t room, uint64_t const* prefix = nullptr, uint64_t const* reads = nullptr)
+        : run_offsets(offsets), records(recs), capacity(room), values_prefix(prefix), read_of(reads) {}
 };
+static_assert(sizeof(run_sink) == 40, "the run kernel takes the sink by value: its layout is part of every instantiation");
 
 class engine;
 
@@ -103,6 +116,20 @@ public:
 private:
     std::vector<int> m_devices;
     std::vector<uint64_t*> m_prefix;
+};
+
+/* The labels of a classes call (num_strings words of 32 bits) in the HBM of every resident replica, uploaded once, for the length of a
+   host call or of a whole query file (streaming.hip); throws no_device when no replica is resident. */
+class class_labels_on_devices {
+public:
+    class_labels_on_devices(engine const& eng, uint32_t const* h_labels);
+    ~class_labels_on_devices();
+    class_labels_on_devices(class_labels_on_devices const&) = delete;
+    class_labels_on_devices& operator=(class_labels_on_devices const&) = delete;
+    uint32_t const* on(int device) const;  // the labels on `device` (device pointer)
+private:
+    std::vector<int> m_devices;
+    std::vector<uint32_t*> m_labels;
 };
 
 class engine {
@@ -209,8 +236,8 @@ public:
                                          uint64_t segment_kmers = SEGMENTS_AS_SET) const;
 
     /* Long reads (sshash_set_read_segments in include/sshash_amd.h): `kmers_per_segment` 0 = the default S, SEGMENTS_OFF = never -- the state of
-       a new dictionary --, else 1 .. 2^30 (throws otherwise). The host and file calls -- counters, rows, cover, depth, sums -- send a piece that holds a read of more
-       than S k-mers through the run kernel over segments; `device_calls`: the five device entry points segment as well. Never on a
+       a new dictionary --, else 1 .. 2^30 (throws otherwise). The host and file calls -- counters, rows, cover, depth, sums, classes -- send a piece that holds a read of more
+       than S k-mers through the run kernel over segments; `device_calls`: the six device entry points segment as well. Never on a
        minimizer shard, never the run records. Not to be changed while a call is in flight. */
     void set_read_segments(uint64_t kmers_per_segment, bool device_calls);
     uint64_t read_segment_kmers() const { return m_segment_kmers; }  // S, or SEGMENTS_OFF
@@ -277,6 +304,23 @@ public:
     streaming_report streaming_sums_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, value_prefixes const& prefix,
                                          uint64_t* sums) const;
 
+    /* PER READ, its positive k-mers by CLASS OF STRING (sshash_streaming_classes[_device]): word c of row r of `d_rows` (num_classes words
+       of 32 bits a read, overwritten) = the positive k-mers of read r in strings s with d_labels[s] == c (num_strings words, only read; a
+       label >= num_classes is no class). Device buffers, asynchronous, always the run kernel, its classes form: a memset and one launch;
+       `d_report` (nullable) is accumulated into. Throws on a minimizer shard. */
+    static constexpr uint32_t MAX_CLASSES = 4096;  // SSHASH_MAX_CLASSES
+    void streaming_classes_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
+                                  uint32_t const* d_labels, uint32_t num_classes, uint32_t* d_rows, uint64_t* d_report, void* stream,
+                                  uint64_t segment_kmers = SEGMENTS_AS_SET) const;
+    /* Host buffers, over all resident replicas, with the labels `labels` keeps on them; `rows` (host, n_reads x num_classes words) is
+       overwritten. Pieces as the sums, and no piece of more reads than make 64 MiB of rows; a piece with a long read and every piece of
+       a minimizer shard is counted from the per-k-mer ids (classes_add_ids_kernel). Returns the totals. */
+    streaming_report streaming_classes_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, class_labels_on_devices const& labels,
+                                            uint32_t num_classes, uint32_t* rows) const;
+    /* The finish of the rows (sshash_class_best_device, sshash_class_totals_device): device buffers, asynchronous, outputs overwritten. */
+    void class_best_device(int device, uint32_t const* d_rows, uint64_t n_reads, uint32_t num_classes, uint32_t* d_best /* four words a read */, void* stream) const;
+    void class_totals_device(int device, uint32_t const* d_rows, uint64_t n_reads, uint32_t num_classes, uint64_t* d_totals, void* stream) const;
+
     /* Per-k-mer results of the streaming query (streaming_query::lookup for every k-mer of every read,
        include/streaming_query.hpp:56-109): entry read_offsets[r] + j of every non-null array of `d_out` = the k-mer
        starting at base j of read r; places where no k-mer starts are left untouched. `d_report` (nullable): the six
@@ -289,7 +333,10 @@ public:
                                  uint64_t* d_cover = nullptr /* a cover bitmap: the ids of the positive k-mers ORed into it */,
                                  uint32_t* d_deltas = nullptr /* the deltas of a depth array: +1 / -1 around every positive k-mer's id added to them */,
                                  uint64_t const* d_prefix = nullptr, uint64_t* d_sums = nullptr /* with the prefix sums of a value per k-mer: the value of
-                                                                      every positive k-mer and 1 ADDED to the two words of its read's row */) const;
+                                                                      every positive k-mer and 1 ADDED to the two words of its read's row */,
+                                 uint32_t const* d_labels = nullptr, uint32_t num_classes = 0, uint32_t* d_class_rows = nullptr /* with a label
+                                                                      per string: 1 ADDED, for every positive k-mer, to the column of its string's
+                                                                      label in its read's row of num_classes words */) const;
     streaming_report streaming_lookup_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads,
                                            result_view const& h_out) const;
 

@@ -318,8 +318,17 @@ __device__ __forceinline__ void row_flush(uint64_t* __restrict__ row, bool parti
                          that difference and the run's length to the two words of the read's row at sink.records (sums_add: two 64-bit
                          atomics without return into rows the caller zeroed). The lane keeps the index of its row, one register, counted
                          from the row of its wave's first read (sink.read_of: the read of every segment, for reads cut into segments,
-                         whose lanes then share rows -- addition commutes). One launch, as the depth. */
-enum : int { STREAM_TOTALS = 0, STREAM_ROWS = 1, STREAM_RUN_COUNTS = 2, STREAM_RUN_RECORDS = 3, STREAM_COVER = 4, STREAM_DEPTH = 5, STREAM_SUMS = 6 };
+                         whose lanes then share rows -- addition commutes). One launch, as the depth.
+     STREAM_CLASSES      the six counters of the batch as STREAM_TOTALS, and PER READ its positive k-mers BY CLASS OF STRING: a run lies in
+                         one string, so it is worth its length in one column -- the label of its string (sink.labels: one 32-bit word
+                         per string id) -- of its read's row of sink.num_classes 32-bit words at sink.records; a label at or above
+                         that count is no class and adds nothing. The sums form with another add (classes_add: ONE 32-bit atomic without
+                         return into rows the caller zeroed, one 4-byte load a run whatever its length); the row's index is kept as
+                         there, sink.read_of included. One launch. */
+enum : int {
+    STREAM_TOTALS = 0, STREAM_ROWS = 1, STREAM_RUN_COUNTS = 2, STREAM_RUN_RECORDS = 3, STREAM_COVER = 4, STREAM_DEPTH = 5, STREAM_SUMS = 6,
+    STREAM_CLASSES = 7
+};
 
 /* the record of the run of `n` k-mers whose first (in read order) starts at base `at` of the packed reads and lies at offset `off` of
    the strings, in string `sid`: to place `cursor` of the records, unless that is past what the read or the caller has room for */
@@ -387,6 +396,23 @@ __device__ __forceinline__ void sums_add(run_sink const& sink, uint64_t row, uin
     (void)__hip_atomic_fetch_add(words + 1, (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+/* the classes form's sink (engine.hpp: run_sink): rows at `records`, their width in `num_classes`, the labels at `labels` */
+inline run_sink class_sink(uint32_t const* labels, uint32_t classes, uint32_t* rows) {
+    run_sink sink{nullptr, rows, 0, nullptr, nullptr};
+    sink.num_classes = classes;
+    sink.labels = labels;
+    return sink;
+}
+
+/* the same run into the column of its string's class (rows of sink.num_classes words of 32 bits, arithmetic modulo 2^32): its length,
+   whatever its ids are. A label at or above the number of classes is no class: nothing is added. Nothing comes back from the add. */
+__device__ __forceinline__ void classes_add(run_sink const& sink, uint64_t row, uint32_t label, uint64_t n) {
+    const uint32_t classes = uint32_t(sink.num_classes);
+    if (label >= classes) return;
+    uint32_t* const word = static_cast<uint32_t*>(sink.records) + row * classes + label;
+    (void)__hip_atomic_fetch_add(word, uint32_t(n), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 /* The reads are given by a begin and an end pointer: read r spans the bases [begins[r], ends[r]) of the packed copy. For whole reads the two
    are `offsets` and `offsets + 1` -- the two words the kernel has always loaded --; for long reads cut into segments they are the two
    arrays of the segment table, and a "read" of the kernel is a segment ("long reads: SEGMENTS" below). */
@@ -396,12 +422,20 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                      const uint64_t* __restrict__ okay, const uint64_t* __restrict__ begins, const uint64_t* __restrict__ ends, const uint64_t n_reads,
                      const uint64_t reads_per_wave, const uint32_t move_out_every, uint64_t* __restrict__ report, const run_sink sink) {
     constexpr bool PER_READ = MODE == STREAM_ROWS, COUNT_RUNS = MODE == STREAM_RUN_COUNTS, RECORDS = MODE == STREAM_RUN_RECORDS, COVER = MODE == STREAM_COVER,
-                   DEPTH = MODE == STREAM_DEPTH, SUMS = MODE == STREAM_SUMS;
+                   DEPTH = MODE == STREAM_DEPTH, SUMS = MODE == STREAM_SUMS, CLASSES = MODE == STREAM_CLASSES;
+    constexpr bool ROW_INDEX = SUMS || CLASSES;  // the lane keeps the index of its read's row, counted from row_first
     /* (SUMS) when a measured run's two words of P are added to its row: at the end of the turn -- by then the seed's own loads have been
        waited for, and these with them -- or where the run is measured, which makes the wave wait for them there. Late costs seven
        registers across the turn. Measured, 2 x 10^7 reads of 150 bases with the table: at k <= 31 late 15.85 ms against 16.56, at
        k <= 63, where the kernel spills as it is (72 bytes of scratch; late: 92), 13.76 against 12.58. */
     constexpr bool LATE_SUMS = SUMS && W == 1;
+    /* (CLASSES) added where the run is measured, at every W. What made the late add pay for the sums at k <= 31 is absent here: there
+       the second word of P depends on the run's length, is asked for behind the run's own loads and has to be waited for before the
+       add. The label depends on the hit alone: it is asked for before the run is measured (as sums_run_anchor), the loads of a wave
+       come back in the order they were issued, so it is there when the run's last load is, and the add -- which returns nothing --
+       waits for no load of its own. A late add would carry the label, the length and the row (three registers) across the turn in
+       a kernel that is at its 96 with the table, to save a wait that does not exist. No late variant was built; measured as it is,
+       same reads, 4 classes: 14.94 ms at k <= 31 beside the sums form's 15.85 (late), 12.19 at k <= 63 beside its 12.36 (early). */
     __shared__ uint4 stage[SK ? 4 * 256 : 1];  // a wave's 64 bucket lines on their way from the quads that fetch them to the lanes that own them
     uint4* const wave_stage = stage + (SK ? (threadIdx.x >> 6) * 256 : 0);
     /* the counters are 32 bits wide in the lanes (six registers fewer than five 64-bit ones: with them the k <= 63 kernel fits five waves a
@@ -459,7 +493,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
     uint64_t late_anchor = 0, late_far = 0, late_n = 0;  // (SUMS) a measured run whose two words of P are on their way: sums_add at the end of the turn
     uint32_t late_row = 0;
     bool late_forward = true;
-    if constexpr (SUMS) {
+    if constexpr (ROW_INDEX) {
         if (sink.read_of) row_first = wave_first < n_reads ? sink.read_of[wave_first] : 0;
     }
     uint64_t* const wave_rows = report + wave * reads_per_wave * 6;  // (PER_READ) the row of the wave's first read
@@ -506,7 +540,10 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
             const uint64_t b = cur + k - 1, valid_end = inv < rd_end ? inv : rd_end;
             uint64_t anchor = 0;
             if constexpr (SUMS) anchor = sums_run_anchor(d, sink, off, hit_sid, ori);  // (on its way while the run is measured)
+            uint32_t label = 0;
+            if constexpr (CLASSES) label = sink.labels[hit_sid];  // (likewise)
             const uint64_t run = extend_run<W>(d, packed, off, ori, b, valid_end - b, run_step_load<W>(d, packed, off, ori > 0, b, 0));
+            if constexpr (CLASSES) classes_add(sink, row_first + my_row, label, run + 1);
             if constexpr (COVER) cover_mark_run(d, sink, off, hit_sid, ori, run + 1);
             if constexpr (DEPTH) depth_mark_run(d, sink, off, hit_sid, ori, run + 1);
             if constexpr (SUMS && !LATE_SUMS) {
@@ -582,7 +619,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                 } else if constexpr (RECORDS) {
                     my_row = uint32_t(r - wave_first);
                     cursor = sink.run_offsets[r];
-                } else if constexpr (SUMS) {
+                } else if constexpr (ROW_INDEX) {
                     if (rd_end - cur >= k) {  // (a read without a k-mer adds nothing: its row keeps the caller's zeros)
                         atomicAdd(wave_moved_out + 4, (unsigned long long)(rd_end - cur - k + 1));
                         my_row = uint32_t((sink.read_of ? sink.read_of[r] : r) - row_first);
@@ -757,7 +794,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                     found = r.outcome == FAST_HIT;
                     off = r.kmer_offset;
                     ori = r.orientation;
-                    if constexpr (RECORDS || COVER || DEPTH || SUMS) hit_sid = r.string_id;
+                    if constexpr (RECORDS || COVER || DEPTH || SUMS || CLASSES) hit_sid = r.string_id;
                     const bool stands = !found && !(where & WALK_VISITED);
                     if (stands || (where & WALK_HEAVY_PENDING)) {
                         /* a miss that stands for the k-mers behind this one: those that elect the same key occurrence (sk_key_persists)
@@ -795,7 +832,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                 found = h.found;
                 off = h.kmer_offset;
                 ori = h.orientation;
-                if constexpr (RECORDS || COVER || DEPTH || SUMS) hit_sid = h.string_id;
+                if constexpr (RECORDS || COVER || DEPTH || SUMS || CLASSES) hit_sid = h.string_id;
                 neg_unknown_mini = !SK && !h.found && !h.minimizer_found;
             }
         }
@@ -822,6 +859,9 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                         const uint64_t kmer_id = off - uint64_t(hit_sid) * (k - 1);
                         sums_add(sink, row_first + my_row, sink.values_prefix[kmer_id + 1], sink.values_prefix[kmer_id], 1);
                     }
+                }
+                if constexpr (CLASSES) {
+                    if (!pending) classes_add(sink, row_first + my_row, sink.labels[hit_sid], 1);  // a run of one
                 }
             } else {
                 ++c_negative;
@@ -1207,12 +1247,14 @@ void launch_run_kernel(device_replica const* rep, dict_view const& d, dim3 grid,
    RUNS_COVER alone -- the cover form, ONE launch: the runs' k-mer ids marked in the bitmap at sink.records, `report` as without, may be null --;
    or RUNS_DEPTH alone -- the depth form, ONE launch: the runs' +1 / -1 added to the 32-bit deltas at sink.records, `report` as with the cover --;
    or RUNS_SUMS alone -- the sums form: the reads' rows at sink.records (n_reads x 2 words) zeroed, then ONE launch that adds every run's
-   sum out of sink.values_prefix and its length to its read's row, `report` as with the cover. */
-enum : int { RUNS_COUNT = 1, RUNS_WRITE = 2, RUNS_COVER = 4, RUNS_DEPTH = 8, RUNS_SUMS = 16 };
+   sum out of sink.values_prefix and its length to its read's row, `report` as with the cover --;
+   or RUNS_CLASSES alone -- the classes form, a sink made by class_sink: the reads' rows at sink.records (n_reads x sink.num_classes words of
+   32 bits) zeroed, then ONE launch that adds every run's length to the column of its string's label, `report` as with the cover. */
+enum : int { RUNS_COUNT = 1, RUNS_WRITE = 2, RUNS_COVER = 4, RUNS_DEPTH = 8, RUNS_SUMS = 16, RUNS_CLASSES = 32 };
 void launch_streaming_runs(device_replica const* rep, char const* bases, uint64_t const* offsets, uint64_t n_reads, uint64_t total_bases, uint64_t* report,
                            hipStream_t s, uint64_t* rows = nullptr /* per read: n_reads x 6 words; `report` may then be null */,
                            run_sink sink = run_sink{nullptr, nullptr, 0}, int run_phases = 0,
-                           uint64_t S = 0 /* the reads cut into segments of S k-mers (totals, rows, cover, depth, sums; never the run records) */) {
+                           uint64_t S = 0 /* the reads cut into segments of S k-mers (totals, rows, cover, depth, sums, classes; never the run records) */) {
     dict_view const& d = rep->view;
     const bool segmented = S != 0;
     if (segmented && (run_phases & (RUNS_COUNT | RUNS_WRITE))) throw error(error_kind::internal, "run records are not segmented");
@@ -1276,7 +1318,7 @@ void launch_streaming_runs(device_replica const* rep, char const* bases, uint64_
         return spare;
     };
     /* the row, counting, record and sums forms keep a lane's read as a 31-bit index into its wave's share -- not the cover and totals forms */
-    if ((rows || (run_phases & (RUNS_COUNT | RUNS_WRITE | RUNS_SUMS))) && reads_per_wave >> 31) throw error(error_kind::argument, "too many reads for one call");
+    if ((rows || (run_phases & (RUNS_COUNT | RUNS_WRITE | RUNS_SUMS | RUNS_CLASSES))) && reads_per_wave >> 31) throw error(error_kind::argument, "too many reads for one call");
     if (run_phases & RUNS_COVER) {
         launch_run_kernel<STREAM_COVER>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), sink);
         if (segmented && caller_report) seams(nullptr, caller_report);  // (nobody reads the six counters: no seam is looked at)
@@ -1288,6 +1330,12 @@ void launch_streaming_runs(device_replica const* rep, char const* bases, uint64_
         HIP_CHECK(hipMemsetAsync(sink.records, 0, n_whole_reads * 2 * sizeof(uint64_t), s));
         if (segmented) sink.read_of = seg + L.read;
         launch_run_kernel<STREAM_SUMS>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), sink);
+        if (segmented && caller_report) seams(nullptr, caller_report);
+    } else if (run_phases & RUNS_CLASSES) {
+        /* (a run that spans a seam arrives as two in the same string, whose lengths add up in the same column) */
+        HIP_CHECK(hipMemsetAsync(sink.records, 0, n_whole_reads * sink.num_classes * sizeof(uint32_t), s));
+        if (segmented) sink.read_of = seg + L.read;
+        launch_run_kernel<STREAM_CLASSES>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), sink);
         if (segmented && caller_report) seams(nullptr, caller_report);
     } else if (run_phases) {
         if (run_phases & RUNS_COUNT) {
@@ -1478,6 +1526,29 @@ void engine::streaming_sums_device(int device, char const* d_bases, uint64_t con
     }
     const uint64_t S = segments_for(segment_kmers);
     launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, run_sink{nullptr, d_sums, 0, d_prefix, nullptr}, RUNS_SUMS, S);
+    if (S) ++m_segmented_launches;  // (counted once the launches are made: a call that threw is none)
+}
+
+/* Per read, its positive k-mers by class of string (sshash_streaming_classes_device): the classes form of the run kernel, a memset and
+   one launch. Every row is written: also when no base is there to look at. */
+void engine::streaming_classes_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
+                                      uint32_t const* d_labels, uint32_t num_classes, uint32_t* d_rows, uint64_t* d_report, void* stream,
+                                      uint64_t segment_kmers) const {
+    device_replica const* rep = replica(device);  // (not resident: that error first)
+    if (n_reads == 0) return;
+    if (!d_labels || !d_rows) throw error(error_kind::argument, "labels or rows pointer is null");
+    if (num_classes == 0 || num_classes > MAX_CLASSES) throw error(error_kind::argument, "num_classes must be 1 .. 4096");
+    /* (as the depth and the sums: a shard's run kernel follows a run through k-mers of other shards, and the shards' rows added would hold those twice) */
+    if (m_idx->num_shards > 1) throw error(error_kind::argument, "a minimizer shard counts per k-mer: use the host call (sshash_streaming_classes)");
+    device_guard guard(device);
+    hipStream_t s = hipStream_t(stream);
+    total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
+    if (total_bases == 0) {  // empty reads only: their rows are zero
+        HIP_CHECK(hipMemsetAsync(d_rows, 0, n_reads * num_classes * sizeof(uint32_t), s));
+        return;
+    }
+    const uint64_t S = segments_for(segment_kmers);
+    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, class_sink(d_labels, num_classes, d_rows), RUNS_CLASSES, S);
     if (S) ++m_segmented_launches;  // (counted once the launches are made: a call that threw is none)
 }
 
@@ -1884,6 +1955,52 @@ sums_add_ids_kernel(const uint8_t* __restrict__ flags, const uint64_t* __restric
     (void)__hip_atomic_fetch_add(row + 1, (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+/* ---- the reads' rows by class out of the per-k-mer results (the same two callers): one lane a place, the label of its k-mer's string --
+        none where no k-mer of the dictionary (or of this shard) starts, or where the label is no class. A stretch is here a run of
+        lanes in one read's stretch (as above) WITH THE SAME LABEL; the lanes count over it, and its first lane, when the label is a
+        class, finds its read and adds the count to that column: one atomic per stretch. ---- */
+__global__ void __launch_bounds__(256)
+classes_add_ids_kernel(const uint8_t* __restrict__ flags, const uint64_t* __restrict__ kmer_id, const uint64_t* __restrict__ string_id,
+                       const uint64_t total_bases, const uint64_t num_kmers, const uint32_t* __restrict__ labels, const uint32_t classes,
+                       const uint64_t* __restrict__ offsets, const uint64_t n_reads, uint32_t* __restrict__ rows) {
+    constexpr uint32_t NO_CLASS = ~0u;
+    const uint64_t p = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint8_t f = p < total_bases ? flags[p] : uint8_t(0);
+    const bool has = (f & (SQ_VALID | SQ_INVALID)) != 0;
+    uint32_t label = NO_CLASS;
+    if ((f & SQ_VALID) && kmer_id[p] < num_kmers) {  // (INVALID_U64: not in the dictionary, and then its string means nothing)
+        label = labels[string_id[p]];
+        if (label >= classes) label = NO_CLASS;
+    }
+    uint32_t n = label != NO_CLASS ? 1u : 0u;
+    const uint64_t have = __ballot(has);
+    if (__ballot(n != 0) == 0) return;  // (uniform)
+    const uint64_t below = (uint64_t(1) << lane) - 1, upto = below | (uint64_t(1) << lane);
+    const uint64_t read_heads = __ballot(has && ((f & SQ_FIRST) || (have & below) == 0));
+    const uint64_t mine_or_before = read_heads & upto;
+    const uint32_t of_read = mine_or_before ? 63u - uint32_t(__builtin_clzll(mine_or_before)) : 64u;  // the head of my read's stretch (64: a place before the wave's first k-mer)
+    /* (both shuffles before anything is decided: inside `a || b` the second would run with the lanes switched off that the first
+       settled, and a lane whose neighbour is switched off reads nothing of it) */
+    const uint32_t read_before = __shfl_up(of_read, 1, 64), label_before = __shfl_up(label, 1, 64);
+    const bool head = lane == 0 || read_before != of_read || label_before != label;
+    const uint64_t heads = __ballot(head);  // (lane 0 is one: never empty below)
+    const uint32_t stretch = 63u - uint32_t(__builtin_clzll(heads & upto));
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+        const bool same = __shfl_down(stretch, o, 64) == stretch && lane + o < 64;
+        const uint32_t further = __shfl_down(n, o, 64);
+        if (same) n += further;
+    }
+    if (!head || n == 0 || label == NO_CLASS) return;  // (n != 0: the stretch's label, mine, is a class, and a k-mer lies at p -- p lies in a read)
+    uint64_t lo = 0, hi = n_reads - 1;  // my read: the largest r with offsets[r] <= p
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (offsets[mid] <= p) lo = mid;
+        else hi = mid - 1;
+    }
+    (void)__hip_atomic_fetch_add(rows + lo * classes + label, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 /* ---- covered k-mers per string: a segmented popcount of a cover bitmap. The ids of string s are [begin(s), begin(s + 1)),
         begin(s) = endpoints[s] - s * (k - 1); strings hold from one k-mer to millions, so the lanes go over the bitmap's WORDS, one each.
         A lane finds the string of its word's first id -- the workgroup's first lane by bisection over all strings, the others from
@@ -2054,12 +2171,127 @@ void engine::depth_string_sums_device(int device, uint32_t const* d_depth, uint6
     HIP_CHECK(hipGetLastError());
 }
 
+/* ---- the finish of the class rows. BEST: a group of `group` lanes (a power of two, at most 64: class_group) per read strides over the
+        read's row; a lane keeps the largest count it met, the first class that had it and the largest of the others, `group` of those are
+        merged by butterfly shuffles, the group's first lane stores the read's four words
+        {best_class, best, second, total}. A count takes the lead only when it is LARGER: among equals the smallest class stays, and a
+        row of zeros keeps the class it began with, NO_CLASS. ---- */
+struct class_lead {
+    uint32_t best, cls, second;
+};
+__device__ __forceinline__ class_lead class_merge(class_lead a, class_lead b) {
+    const bool b_leads = b.best > a.best || (b.best == a.best && b.cls < a.cls);
+    const class_lead w = b_leads ? b : a, l = b_leads ? a : b;
+    return class_lead{w.best, w.cls, l.best > w.second ? l.best : w.second};  // (the loser's second is at most its best)
+}
+__global__ void __launch_bounds__(256)
+class_best_kernel(const uint32_t* __restrict__ rows, const uint64_t n_reads, const uint32_t classes, const uint32_t group, uint32_t* __restrict__ out) {
+    const uint64_t t = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    const uint64_t r = t / group;  // (a group lies in one wave: 64 is a multiple of it)
+    const uint32_t sub = uint32_t(t) & (group - 1);
+    class_lead mine{0u, ~0u, 0u};
+    uint32_t total = 0;
+    if (r < n_reads) {
+        const uint32_t* const row = rows + r * classes;
+        for (uint32_t c = sub; c < classes; c += group) {  // (ascending: the first class with the lane's largest count is its smallest)
+            const uint32_t v = row[c];
+            total += v;
+            if (v > mine.best) {
+                mine.second = mine.best;
+                mine.best = v;
+                mine.cls = c;
+            } else if (v > mine.second) {
+                mine.second = v;
+            }
+        }
+    }
+    for (uint32_t o = 1; o < group; o <<= 1) {  // (lane ^ o stays inside the group; every lane of the wave is here)
+        const class_lead other{uint32_t(__shfl_xor(mine.best, o, 64)), uint32_t(__shfl_xor(mine.cls, o, 64)), uint32_t(__shfl_xor(mine.second, o, 64))};
+        total += uint32_t(__shfl_xor(total, o, 64));
+        mine = class_merge(mine, other);
+    }
+    if (r < n_reads && sub == 0) {
+        uint32_t* const words = out + 4 * r;
+        words[0] = mine.cls;
+        words[1] = mine.best;
+        words[2] = mine.second;
+        words[3] = total;
+    }
+}
+
+/* G = min(64, the smallest power of two >= classes) */
+static uint32_t class_group(uint32_t classes) {
+    uint32_t g = 1;
+    while (g < classes && g < 64) g <<= 1;
+    return g;
+}
+
+void engine::class_best_device(int device, uint32_t const* d_rows, uint64_t n_reads, uint32_t num_classes, uint32_t* d_best, void* stream) const {
+    replica(device);  // (not resident: that error first)
+    if (n_reads == 0) return;
+    if (!d_rows || !d_best) throw error(error_kind::argument, "null pointer");
+    if (num_classes == 0 || num_classes > MAX_CLASSES) throw error(error_kind::argument, "num_classes must be 1 .. 4096");
+    device_guard guard(device);
+    const uint32_t group = class_group(num_classes);
+    const uint64_t blocks = (n_reads + 256 / group - 1) / (256 / group);
+    if (blocks >> 31) throw error(error_kind::argument, "too many reads for one launch");
+    hipLaunchKernelGGL(class_best_kernel, dim3(uint32_t(blocks)), dim3(256), 0, hipStream_t(stream), d_rows, n_reads, num_classes, group, d_best);
+    HIP_CHECK(hipGetLastError());
+}
+
+/* ---- TOTALS: the 64-bit sum of every column over the reads. A workgroup takes `block_reads` reads. With 256 classes or more lane t sums
+        the columns t, t + 256, ... over them; with fewer, 256 / classes reads are taken side by side -- lane t is on column t % classes
+        of every (256 / classes)-th read -- and the lanes of a column meet in LDS. Either way consecutive lanes read consecutive words,
+        and one 64-bit atomic per column and workgroup goes into the zeroed totals. ---- */
+__global__ void __launch_bounds__(256)
+class_totals_kernel(const uint32_t* __restrict__ rows, const uint64_t n_reads, const uint32_t classes, const uint64_t block_reads,
+                    uint64_t* __restrict__ totals) {
+    __shared__ uint64_t part[256];
+    const uint64_t first = uint64_t(blockIdx.x) * block_reads, last = first + block_reads < n_reads ? first + block_reads : n_reads;
+    unsigned long long* const out = reinterpret_cast<unsigned long long*>(totals);
+    if (classes >= 256) {
+        for (uint32_t c = threadIdx.x; c < classes; c += 256) {
+            uint64_t sum = 0;
+            for (uint64_t r = first; r < last; ++r) sum += rows[r * classes + c];
+            if (sum) (void)__hip_atomic_fetch_add(out + c, (unsigned long long)sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        return;
+    }
+    const uint32_t side = 256 / classes, c = threadIdx.x % classes, mine = threadIdx.x / classes;  // (lanes at or past side * classes: none)
+    uint64_t sum = 0;
+    if (mine < side)
+        for (uint64_t r = first + mine; r < last; r += side) sum += rows[r * classes + c];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x < classes) {
+        for (uint32_t i = 1; i < side; ++i) sum += part[threadIdx.x + i * classes];
+        if (sum) (void)__hip_atomic_fetch_add(out + c, (unsigned long long)sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+void engine::class_totals_device(int device, uint32_t const* d_rows, uint64_t n_reads, uint32_t num_classes, uint64_t* d_totals, void* stream) const {
+    replica(device);  // (not resident: that error first)
+    if (!d_totals || (n_reads && !d_rows)) throw error(error_kind::argument, "null pointer");
+    if (num_classes == 0 || num_classes > MAX_CLASSES) throw error(error_kind::argument, "num_classes must be 1 .. 4096");
+    device_guard guard(device);
+    hipStream_t s = hipStream_t(stream);
+    HIP_CHECK(hipMemsetAsync(d_totals, 0, num_classes * sizeof(uint64_t), s));
+    if (n_reads == 0) return;
+    const uint64_t block_reads = std::max<uint64_t>(1, (uint64_t(1) << 16) / num_classes);  // (some 2^16 words a workgroup)
+    const uint64_t blocks = (n_reads + block_reads - 1) / block_reads;
+    if (blocks >> 31) throw error(error_kind::argument, "too many reads for one launch");
+    hipLaunchKernelGGL(class_totals_kernel, dim3(uint32_t(blocks)), dim3(256), 0, s, d_rows, n_reads, num_classes, block_reads, d_totals);
+    HIP_CHECK(hipGetLastError());
+}
+
 void engine::streaming_lookup_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
                                      uint64_t total_bases, result_view const& d_out, uint64_t* d_report, void* stream, uint64_t* d_rows,
-                                     run_sink const* runs, uint64_t* d_cover, uint32_t* d_deltas, uint64_t const* d_prefix, uint64_t* d_sums) const {
+                                     run_sink const* runs, uint64_t* d_cover, uint32_t* d_deltas, uint64_t const* d_prefix, uint64_t* d_sums,
+                                     uint32_t const* d_labels, uint32_t num_classes, uint32_t* d_class_rows) const {
     device_replica const* rep = replica(device);
     if ((d_prefix != nullptr) != (d_sums != nullptr)) throw error(error_kind::internal, "the sums go with their prefix");
-    if (!d_out.kmer_id && !d_report && !d_rows && !runs && !d_cover && !d_deltas && !d_sums) throw error(error_kind::argument, "neither a kmer_id array nor a report to fill");
+    if ((d_labels != nullptr) != (d_class_rows != nullptr) || (d_labels && num_classes == 0)) throw error(error_kind::internal, "the class rows go with their labels");
+    if (!d_out.kmer_id && !d_report && !d_rows && !runs && !d_cover && !d_deltas && !d_sums && !d_class_rows) throw error(error_kind::argument, "neither a kmer_id array nor a report to fill");
     if (d_out.minimizer_found) throw error(error_kind::argument, "the streaming lookup does not report minimizer_found");
     if (n_reads == 0 || total_bases == 0) return;
     device_guard guard(device);
@@ -2117,6 +2349,11 @@ void engine::streaming_lookup_device(int device, char const* d_bases, uint64_t c
     if (d_sums) {
         hipLaunchKernelGGL(sums_add_ids_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, flags, ids, total_bases, d.num_kmers, d_prefix,
                            d_read_offsets, n_reads, d_sums);
+        HIP_CHECK(hipGetLastError());
+    }
+    if (d_class_rows) {
+        hipLaunchKernelGGL(classes_add_ids_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, flags, ids, sid, total_bases, d.num_kmers, d_labels,
+                           num_classes, d_read_offsets, n_reads, d_class_rows);
         HIP_CHECK(hipGetLastError());
     }
     if (runs) {
@@ -2216,9 +2453,9 @@ namespace {
 /* Host buffers: the reads are cut into pieces of at most ~32 MiB of bases; per replica up to eight lanes (the
    pooled pinned pipelines of the lookup host path, replica.hpp) pull pieces from a shared counter and run
    copy-in -> H2D -> kernel, accumulating the six counters in device memory; one read-back per lane. */
-piece_cuts cut_lane_pieces(uint64_t const* read_offsets, uint64_t n_reads) {
+piece_cuts cut_lane_pieces(uint64_t const* read_offsets, uint64_t n_reads, uint64_t reads_cap = ~uint64_t(0) /* the call's own cap on a piece's reads */) {
     return cut_pieces(read_offsets, n_reads, uint64_t(32) << 20,
-                      test_hook_u64("stream_piece_reads", uint64_t(1) << 20, 1, uint64_t(1) << 20));  // (tests: seams between pieces inside a small batch)
+                      std::min(reads_cap, test_hook_u64("stream_piece_reads", uint64_t(1) << 20, 1, uint64_t(1) << 20)));  // (tests: seams between pieces inside a small batch)
 }
 
 /* One lane walks one read: a read of megabases (a contig, a multiline FASTA record) would keep a single lane busy for minutes. Where the
@@ -2532,6 +2769,68 @@ uint64_t const* value_prefixes::on(int device) const {
 streaming_report engine::streaming_sums_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, value_prefixes const& prefix,
                                              uint64_t* sums) const {
     return streaming_query_per_read_host(bases, read_offsets, n_reads, nullptr, nullptr, nullptr, &prefix, sums);
+}
+
+/* ---- the labels of a host call: one copy in the HBM of every resident replica for as long as the object lives ---- */
+class_labels_on_devices::class_labels_on_devices(engine const& eng, uint32_t const* h_labels) : m_devices(resident_devices(eng)) {
+    const uint64_t n = eng.index().num_strings;
+    int prev = 0;
+    HIP_CHECK(hipGetDevice(&prev));
+    try {
+        for (int device : m_devices) {
+            HIP_CHECK(hipSetDevice(device));
+            void* p = nullptr;
+            HIP_CHECK(hipMalloc(&p, std::max<uint64_t>(n, 1) * sizeof(uint32_t)));
+            m_labels.push_back(static_cast<uint32_t*>(p));
+            HIP_CHECK(hipMemcpy(p, h_labels, n * sizeof(uint32_t), hipMemcpyHostToDevice));  // (synchronous: the lanes' streams find it there)
+        }
+    } catch (...) {
+        for (size_t i = 0; i < m_labels.size(); ++i) {
+            (void)hipSetDevice(m_devices[i]);
+            (void)hipFree(m_labels[i]);
+        }
+        (void)hipSetDevice(prev);
+        throw;
+    }
+    (void)hipSetDevice(prev);
+}
+
+class_labels_on_devices::~class_labels_on_devices() {
+    int prev = 0;
+    if (hipGetDevice(&prev) != hipSuccess) return;
+    for (size_t i = 0; i < m_labels.size(); ++i) {
+        (void)hipSetDevice(m_devices[i]);
+        (void)hipFree(m_labels[i]);
+    }
+    (void)hipSetDevice(prev);
+}
+
+uint32_t const* class_labels_on_devices::on(int device) const {
+    for (size_t i = 0; i < m_devices.size(); ++i)
+        if (m_devices[i] == device) return m_labels[i];
+    throw error(error_kind::internal, "no labels on this device");
+}
+
+/* The rows travel as the sums' do, through `num_classes` words a read of the lane's blocks; a piece holds no more reads than make
+   CLASS_PIECE_BYTES of rows (beside cut_lane_pieces' bytes of bases and its hook: 4096 reads at the cap of 4096 classes). */
+streaming_report engine::streaming_classes_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, class_labels_on_devices const& labels,
+                                                uint32_t num_classes, uint32_t* rows) const {
+    if (n_reads == 0) return {};
+    if (num_classes == 0 || num_classes > MAX_CLASSES) throw error(error_kind::argument, "num_classes must be 1 .. 4096");
+    constexpr uint64_t CLASS_PIECE_BYTES = uint64_t(64) << 20;
+    const uint64_t row_bytes = num_classes * sizeof(uint32_t);
+    const piece_cuts pieces = cut_lane_pieces(read_offsets, n_reads, CLASS_PIECE_BYTES / row_bytes);
+    return run_piece_lanes(*this, bases, read_offsets, pieces, pieces.max_reads * row_bytes, [&](staged_piece const& p) {
+        uint32_t* d_rows = reinterpret_cast<uint32_t*>(p.d_extra);
+        const bool by_ids = (p.long_read && !p.segments) || m_idx->num_shards > 1;
+        if (by_ids || p.nb == 0) HIP_CHECK(hipMemsetAsync(d_rows, 0, p.n * row_bytes, p.s));  // (the per-k-mer pass adds to its rows; no bases: no kernel at all)
+        if (by_ids) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                            labels.on(p.device), num_classes, d_rows);
+        else if (p.nb) streaming_classes_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, labels.on(p.device), num_classes, d_rows, p.d_report, p.s, p.segments);
+        HIP_CHECK(hipMemcpyAsync(p.h_extra, d_rows, p.n * row_bytes, hipMemcpyDeviceToHost, p.s));
+        HIP_CHECK(hipStreamSynchronize(p.s));
+        std::memcpy(rows + p.first * num_classes, p.h_extra, p.n * row_bytes);
+    });
 }
 
 streaming_report engine::streaming_depth_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, depth_arrays const& depth) const {
