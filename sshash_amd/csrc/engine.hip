@@ -1386,7 +1386,8 @@ void engine::iterate_packed_device(int device, uint64_t begin, uint64_t end, uin
     int cus = 0;
     HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
     const uint64_t num_tiles = (end - begin + IT_TILE - 1) / IT_TILE;
-    const uint64_t max_blocks = uint64_t(std::max(cus, 1)) * IT_BLOCKS_PER_CU;
+    /* the tests make a block own several tiles of a small range: the hand-over between the tiles of a block (hooks.hpp) */
+    const uint64_t max_blocks = test_hook_u64("iterate_blocks", uint64_t(std::max(cus, 1)) * IT_BLOCKS_PER_CU, 1, uint64_t(1) << 20);
     const uint64_t tiles_per_block = (num_tiles + max_blocks - 1) / max_blocks;
     const dim3 grid(uint32_t((num_tiles + tiles_per_block - 1) / tiles_per_block)), block(IT_BLOCK);
     if (rep->view.k <= 31)
@@ -1439,7 +1440,7 @@ void engine::check_device(int device, uint64_t out[8]) const {
     device_guard guard(device);
     const uint64_t n = rep->view.num_kmers;
     const uint32_t W = rep->view.k <= 31 ? 1 : 2;
-    const uint64_t chunk = std::min(n, CHECK_CHUNK);
+    const uint64_t chunk = std::min(n, test_hook_u64("check_chunk", CHECK_CHUNK, 1, CHECK_CHUNK));  // (the tests: several rounds over a small dictionary)
     /* The call runs on a stream of its own, so that it does not serialise with the other work of the process on the device, as
        the null stream would (declared after `tmp`: it is drained and handed back before the buffers are freed). */
     device_buffers tmp;
