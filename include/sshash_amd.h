@@ -564,6 +564,52 @@ sshash_status sshash_class_totals_device(const sshash_dict* d, int device, const
                                          uint64_t* totals, void* hip_stream);
 sshash_status sshash_class_totals(const uint32_t* rows, uint64_t num_reads, uint32_t num_classes, uint64_t* totals);
 
+/* ---- ANCHORS: per read, its LONGEST RUN -- the one place of a read a mapper extends from, and the length of its longest exact match
+ *      (no reference counterpart as a call). For read r, best[r] is a sshash_streaming_run, the 32-byte record of sshash_streaming_runs
+ *      with the same field meanings: the record of read r with the largest num_kmers & 0x7FFFFFFF (bit 31, the strand, takes no part
+ *      in the comparison); among equals the one with the smallest read_pos, that is, the first in read order. A read shorter than k, an
+ *      empty read and a read without a hit get a record of 32 zero bytes: num_kmers == 0 is the sign, a real run has at least 1.
+ *      Every record of best[0 .. num_reads) is OVERWRITTEN; nothing outside that range is written. Equivalently: best[r] is that
+ *      argmax over runs[run_offsets[r] : run_offsets[r + 1]] of sshash_streaming_runs on the same reads -- sshash_runs_best below
+ *      computes it from those --, but its size is known before the call and it takes one launch, not a count, a prefix sum and a
+ *      second launch. The six counters are accumulated into `report` as sshash_streaming_cover_device does; report may be NULL.
+ *      Preconditions and status codes: a null dictionary, or null bases / read_offsets / best with num_reads > 0, is
+ *      SSHASH_ERR_ARGUMENT, and so is a null `fn`, all before anything runs and with nothing written; num_reads == 0 succeeds and
+ *      touches nothing; a dictionary that is not resident is SSHASH_ERR_NO_DEVICE. Segments never apply, whatever
+ *      sshash_set_read_segments says: a longest run is not additive over segments, so these calls do not cut a read and do not
+ *      count as segmented launches. A minimizer shard (num_shards > 1) is SSHASH_ERR_ARGUMENT from the device, host and file calls:
+ *      the run kernel of a shard follows a run through k-mers it does not own, and the shards' longest runs do not combine into the
+ *      whole index's; sshash_streaming_runs on the whole index is the route. ---- */
+/* device buffers, asynchronous on hip_stream. best: num_reads records, OVERWRITTEN (16-byte aligned, as the records of
+ * sshash_streaming_runs_device). report and total_bases as for sshash_streaming_cover_device. PRECONDITION, that of
+ * sshash_streaming_runs_device: every read is shorter than 2^31 bases. Always the run kernel: the records are zeroed (one memset) and
+ * ONE launch follows in which the lane that owns a read keeps the length of the read's longest run so far in a register and stores a
+ * run's record over the read's when the run is longer -- plain stores, no atomics, no scratch beyond that of
+ * sshash_streaming_query_device. */
+sshash_status sshash_streaming_best_run_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
+                                               uint64_t num_reads, uint64_t total_bases, sshash_streaming_run* best, uint64_t* report,
+                                               void* hip_stream);
+/* host buffers, sharded over all resident replicas like sshash_streaming_sums; a piece's records travel through the lanes' pinned blocks.
+ * A piece that holds a read above 2^16 bases goes the way it goes in sshash_streaming_runs -- the position-parallel pipeline of
+ * sshash_streaming_lookup and its compaction into run records -- and sshash_runs_best_device over those, which gives the same
+ * records. A read of 2^31 bases or more is SSHASH_ERR_ARGUMENT. report may be NULL. */
+sshash_status sshash_streaming_best_run(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
+                                        sshash_streaming_run* best, sshash_streaming_report* report);
+/* a query file: the contract of sshash_streaming_sums_from_file -- records are handed over in batches, IN FILE ORDER, one record for
+ * EVERY record of the file, one call of `fn` at a time; a non-zero return of `fn` stops the query (SSHASH_ERR_ARGUMENT,
+ * sshash_last_error() carries the value). report may be NULL. */
+typedef int (*sshash_read_best_run_fn)(void* ctx, uint64_t first_read, uint64_t n, const sshash_streaming_run* best);
+sshash_status sshash_streaming_best_run_from_file(const sshash_dict* d, const char* filename, int multiline, sshash_read_best_run_fn fn,
+                                                  void* ctx, sshash_streaming_report* report);
+/* The finish over a COMPLETE CSR of run records (run_offsets[num_reads] records are present): best[r] = the argmax above over
+ * runs[run_offsets[r] : run_offsets[r + 1]], 32 zero bytes for an empty range; best is OVERWRITTEN. The _device form takes device
+ * pointers and is asynchronous on hip_stream (one lane a record and one 64-bit atomic max per record into 8 bytes of stream-ordered
+ * scratch per read, then one lane a read); the other is plain host code over host arrays and needs no dictionary. NULL run_offsets or
+ * best with num_reads > 0, or NULL runs where run_offsets[num_reads] > 0 (host form; the device form cannot see it): SSHASH_ERR_ARGUMENT. */
+sshash_status sshash_runs_best_device(const sshash_dict* d, int device, const uint64_t* run_offsets, const sshash_streaming_run* runs,
+                                      uint64_t num_reads, sshash_streaming_run* best, void* hip_stream);
+sshash_status sshash_runs_best(const uint64_t* run_offsets, const sshash_streaming_run* runs, uint64_t num_reads, sshash_streaming_run* best);
+
 /* ---- streaming_query<Dict,canonical>::lookup for EVERY k-mer of every read (include/streaming_query.hpp:56-109),
  *      batched: what the reference returns k-mer by k-mer while it streams a read. Every non-NULL array of `out` has one
  *      entry per BASE of `bases` (total_bases = read_offsets[num_reads] entries): entry read_offsets[r] + j is the result

@@ -503,6 +503,47 @@ public:
         check(sshash_class_totals_device(m_h, device, d_rows, num_reads, num_classes, d_totals, hip_stream));
     }
 
+    /* ANCHORS (sshash_streaming_best_run; the definition is in include/sshash_amd.h): per read its longest run, among equals the first in
+       read order; a read without a hit has a record of zeros (num_kmers == 0). `best` is sized to num_reads and overwritten. Never
+       over segments; throws on a minimizer shard. Returns the batch's report. */
+    streaming_query_report streaming_best_run(char const* bases, uint64_t const* read_offsets, uint64_t num_reads, std::vector<sshash_streaming_run>& best) const {
+        best.assign(num_reads, sshash_streaming_run{});
+        sshash_streaming_report s;
+        check(sshash_streaming_best_run(m_h, bases, read_offsets, num_reads, best.data(), &s));
+        return to_report(s);
+    }
+    /* device buffers, asynchronous on hip_stream: d_best -- num_reads records -- is overwritten, d_report -- may be null -- six counters
+       (accumulated into) */
+    void streaming_best_run_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t num_reads, uint64_t total_bases,
+                                   sshash_streaming_run* d_best, uint64_t* d_report, void* hip_stream) const {
+        check(sshash_streaming_best_run_device(m_h, device, d_bases, d_read_offsets, num_reads, total_bases, d_best, d_report, hip_stream));
+    }
+    /* a query file, one record per record of the file, handed over in file order: fn(first_read, best, n) for one batch after the other;
+       a non-zero return stops the query (std::runtime_error). Fn: int(uint64_t, sshash_streaming_run const*, uint64_t). */
+    template <typename Fn>
+    streaming_query_report streaming_best_run_from_file(std::string const& filename, bool multiline, Fn&& fn) const {
+        struct context {
+            std::remove_reference_t<Fn>* fn;
+        } ctx{&fn};
+        sshash_streaming_report s;
+        check(sshash_streaming_best_run_from_file(
+            m_h, filename.c_str(), multiline,
+            [](void* c, uint64_t first_read, uint64_t n, const sshash_streaming_run* best) -> int { return int((*static_cast<context*>(c)->fn)(first_read, best, n)); },
+            &ctx, &s));
+        return to_report(s);
+    }
+    /* the finish over a complete CSR of run records (sshash_runs_best): on the host over host arrays, or device buffers, asynchronous */
+    static std::vector<sshash_streaming_run> runs_best(std::vector<uint64_t> const& run_offsets, std::vector<sshash_streaming_run> const& runs) {
+        if (run_offsets.empty() || run_offsets.back() > runs.size()) throw std::invalid_argument("run_offsets is no CSR over runs");
+        std::vector<sshash_streaming_run> best(run_offsets.size() - 1);
+        check(sshash_runs_best(run_offsets.data(), runs.data(), best.size(), best.data()));
+        return best;
+    }
+    void runs_best_device(int device, uint64_t const* d_run_offsets, sshash_streaming_run const* d_runs, uint64_t num_reads, sshash_streaming_run* d_best,
+                          void* hip_stream) const {
+        check(sshash_runs_best_device(m_h, device, d_run_offsets, d_runs, num_reads, d_best, hip_stream));
+    }
+
     /* a query file, one row per record, handed over in file order: fn(first_read, rows, n) for one batch after the other; a
        non-zero return stops the query (std::runtime_error). Fn: int(uint64_t, streaming_query_report const*, uint64_t). */
     template <typename Fn>

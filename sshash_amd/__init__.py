@@ -31,6 +31,7 @@ from ._binding import (  # noqa: F401
     expand_runs,
     ids_to_cover,
     library_path,
+    runs_best,
     write_weighted_fasta,
 )
 
@@ -55,5 +56,6 @@ __all__ = [
     "expand_runs",
     "ids_to_cover",
     "library_path",
+    "runs_best",
     "write_weighted_fasta",
 ]

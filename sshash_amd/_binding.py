@@ -225,6 +225,11 @@ def _load() -> C.CDLL:
         "sshash_class_best": (C.c_int, [P, C.c_uint64, C.c_uint32, P]),
         "sshash_class_totals_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P]),
         "sshash_class_totals": (C.c_int, [P, C.c_uint64, C.c_uint32, P]),
+        "sshash_streaming_best_run_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, P, P]),
+        "sshash_streaming_best_run": (C.c_int, [P, P, P, C.c_uint64, P, C.POINTER(_Report)]),
+        "sshash_streaming_best_run_from_file": (C.c_int, [P, C.c_char_p, C.c_int, _PerReadFn, P, C.POINTER(_Report)]),
+        "sshash_runs_best_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, P, P]),
+        "sshash_runs_best": (C.c_int, [P, P, C.c_uint64, P]),
         "sshash_route_packed_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P, P]),
         "sshash_route_bucket_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, C.c_int, P, P, P, P]),
         "sshash_route_bucket_by_key_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P, P, P]),
@@ -258,6 +263,7 @@ C_ABI_SYMBOLS = (
     "sshash_value_prefix_device sshash_streaming_sums sshash_streaming_sums_device sshash_streaming_sums_from_file "
     "sshash_streaming_classes sshash_streaming_classes_device sshash_streaming_classes_from_file "
     "sshash_class_best sshash_class_best_device sshash_class_totals sshash_class_totals_device "
+    "sshash_streaming_best_run sshash_streaming_best_run_device sshash_streaming_best_run_from_file sshash_runs_best sshash_runs_best_device "
     "sshash_streaming_lookup sshash_streaming_lookup_device sshash_sharded_lookup_device sshash_sharded_lookup_rccl "
     "sshash_route_packed_device sshash_route_bucket_device sshash_route_bucket_by_key_device sshash_route_combine_device "
     "sshash_iterate_packed sshash_iterate_packed_device sshash_check_device"
@@ -1088,6 +1094,65 @@ class Dictionary:
         _check(_load().sshash_class_totals_device(self._h, int(device), C.c_void_p(d_rows), int(num_reads), int(num_classes), C.c_void_p(d_totals),
                                                   C.c_void_p(stream)))
 
+    # ---- streaming anchors: a read's longest run -----------------------------------------------------
+    def streaming_best_run_device(self, device: int, d_bases: int, d_read_offsets: int, num_reads: int, d_best: int, d_report: int = 0,
+                                  stream: int = 0, total_bases: int = 0) -> None:
+        """Device buffers: d_best receives num_reads records of RUN_DTYPE (overwritten; 16-byte aligned), d_report (0: none) six counters
+        (accumulated into). `total_bases` as for streaming_query_device. Reads below 2^31 bases; segments never apply."""
+        _check(_load().sshash_streaming_best_run_device(self._h, int(device), C.c_void_p(d_bases), C.c_void_p(d_read_offsets), int(num_reads),
+                                                        int(total_bases), C.c_void_p(d_best), C.c_void_p(d_report), C.c_void_p(stream)))
+
+    def streaming_best_run(self, reads: Sequence[Union[str, bytes]]):
+        """The one place per read -> (best, StreamingQueryReport): best is a RUN_DTYPE array, best[r] the longest run of read r (the
+        record of streaming_runs with the largest num_kmers & 0x7FFFFFFF, among equals the first in read order); a read without a hit
+        has a record of zeros, num_kmers == 0."""
+        chunks = [s.encode("ascii", "replace") if isinstance(s, str) else bytes(s) for s in reads]
+        offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
+        if chunks:
+            offsets[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
+        bases = np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8)
+        best = np.zeros(len(chunks), dtype=RUN_DTYPE)
+        r = _Report()
+        _check(_load().sshash_streaming_best_run(self._h, bases.ctypes.data, offsets.ctypes.data, len(chunks),
+                                                 best.ctypes.data if len(chunks) else None, C.byref(r)))
+        return best, self._report(r)
+
+    def streaming_best_run_from_file(self, filename: str, multiline: bool = False,
+                                     per_read: Optional[Callable[[int, np.ndarray], Optional[int]]] = None):
+        """A query file answered like streaming_best_run. per_read(first_read, best) is called for one batch of the file after the other,
+        in file order, best a RUN_DTYPE array with record i for record first_read + i of the file (every record has one); a return
+        value other than None / 0 stops the query (SSHashError), an exception raised by the callable stops it too and is raised again
+        here. per_read=None: -> (the records of the whole file, StreamingQueryReport); otherwise -> StreamingQueryReport."""
+        r = _Report()
+        raised, kept = [], []
+
+        def hand_over(_ctx, first_read, n, best):
+            try:
+                block = np.ctypeslib.as_array(C.cast(best, C.POINTER(C.c_uint8)), shape=(int(n) * RUN_DTYPE.itemsize,)).copy().view(RUN_DTYPE)
+                if per_read is None:
+                    kept.append(block)
+                    return 0
+                stop = per_read(int(first_read), block)
+                return int(stop) if stop else 0
+            except BaseException as e:  # (must not travel through the C frames)
+                raised.append(e)
+                return -1
+
+        fn = _PerReadFn(hand_over)
+        status = _load().sshash_streaming_best_run_from_file(self._h, os.fsencode(filename), 1 if multiline else 0, fn, None, C.byref(r))
+        if raised:
+            raise raised[0]
+        _check(status)
+        if per_read is None:
+            return (np.concatenate(kept) if kept else np.zeros(0, dtype=RUN_DTYPE)), self._report(r)
+        return self._report(r)
+
+    def runs_best_device(self, device: int, d_run_offsets: int, d_runs: int, num_reads: int, d_best: int, stream: int = 0) -> None:
+        """Device buffers: d_best receives num_reads records of RUN_DTYPE (overwritten), the longest of every read's records of a complete
+        CSR (d_run_offsets: num_reads + 1 uint64; d_runs: d_run_offsets[num_reads] records)."""
+        _check(_load().sshash_runs_best_device(self._h, int(device), C.c_void_p(d_run_offsets), C.c_void_p(d_runs), int(num_reads),
+                                               C.c_void_p(d_best), C.c_void_p(stream)))
+
     def streaming_lookup(self, reads: Sequence[Union[str, bytes]], full: bool = False):
         """streaming_query::lookup for every k-mer of every read (reference include/streaming_query.hpp:56-109), batched.
         -> (list of LookupResult, one per read, len(read) - k + 1 entries each; StreamingQueryReport)."""
@@ -1234,6 +1299,25 @@ def class_totals(rows) -> np.ndarray:
     totals = np.zeros(rows.shape[1], dtype=np.uint64)
     _check(_load().sshash_class_totals(rows.ctypes.data if rows.shape[0] else None, rows.shape[0], rows.shape[1], totals.ctypes.data))
     return totals
+
+
+def runs_best(run_offsets, runs) -> np.ndarray:
+    """The finish of streaming_runs on the host (sshash_runs_best) -> a RUN_DTYPE array, one record per read: the record of
+    runs[run_offsets[r]:run_offsets[r + 1]] with the largest num_kmers & 0x7FFFFFFF, among equals the first; zeros for an empty range."""
+    run_offsets = np.asarray(run_offsets)
+    if run_offsets.ndim != 1 or run_offsets.size == 0 or run_offsets.dtype.kind not in "ui":
+        raise ValueError("run_offsets: num_reads + 1 unsigned integers")
+    run_offsets = np.ascontiguousarray(run_offsets, dtype=np.uint64)
+    runs = np.asarray(runs)
+    if runs.dtype != RUN_DTYPE or runs.ndim != 1:
+        raise ValueError("runs: a one-dimensional RUN_DTYPE array")
+    runs = np.ascontiguousarray(runs)
+    n = run_offsets.size - 1
+    if n and (int(run_offsets[0]) != 0 or (np.diff(run_offsets.astype(np.int64)) < 0).any() or int(run_offsets[-1]) > runs.size):
+        raise ValueError("run_offsets: a CSR over the records of runs, from 0 and never going down")
+    best = np.zeros(n, dtype=RUN_DTYPE)
+    _check(_load().sshash_runs_best(run_offsets.ctypes.data, runs.ctypes.data if runs.size else None, n, best.ctypes.data if n else None))
+    return best
 
 
 def cover_to_ids(cover) -> np.ndarray:

@@ -878,6 +878,79 @@ sshash_status sshash_class_totals(const uint32_t* rows, uint64_t num_reads, uint
     });
 }
 
+/* ---- anchors: per read, its longest run (a sshash_streaming_run of 32 bytes: the static_assert stands with sshash_streaming_runs_device) ---- */
+sshash_status sshash_streaming_best_run_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
+                                               uint64_t num_reads, uint64_t total_bases, sshash_streaming_run* best, uint64_t* report,
+                                               void* hip_stream) {
+    if (!d || (num_reads && (!bases || !read_offsets || !best))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] { d->eng->streaming_best_run_device(device, bases, read_offsets, num_reads, total_bases, best, report, hip_stream); });
+}
+
+sshash_status sshash_streaming_best_run(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
+                                        sshash_streaming_run* best, sshash_streaming_report* report) {
+    if (!d || (num_reads && (!bases || !read_offsets || !best))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (report) std::memset(report, 0, sizeof(*report));
+    return guarded([&] {
+        if (num_reads == 0) return;
+        const streaming_report r = d->eng->streaming_best_run_host(bases, read_offsets, num_reads, best);
+        if (report) fill_report(report, r);
+    });
+}
+
+sshash_status sshash_streaming_best_run_from_file(const sshash_dict* d, const char* filename, int multiline, sshash_read_best_run_fn fn,
+                                                  void* ctx, sshash_streaming_report* report) {
+    if (!d || !filename || !fn) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (report) std::memset(report, 0, sizeof(*report));
+    return guarded([&] {
+        d->eng->best_run_ready();  // (no replica, a minimizer shard: said before the file is opened)
+        read_stream in(filename, multiline != 0, d->idx->k, true);  // (every record of the file: record i of the output is record i of the file)
+        if (!in.supported()) {
+            fprintf(stderr, "unsupported query file format\n");
+            return;
+        }
+        /* the sequential reader, as sshash_streaming_sums_from_file */
+        streaming_report total;
+        uint64_t first_read = 0;
+        std::vector<sshash_streaming_run> best;
+        for_each_batch(in, [&](read_batch const& batch) {
+            const uint64_t n = batch.num_reads();
+            if (n == 0) return;
+            best.resize(n);
+            total += d->eng->streaming_best_run_host(batch.bases.data(), batch.offsets.data(), n, best.data());
+            if (report) fill_report(report, total);
+            const int stop = fn(ctx, first_read, n, best.data());
+            if (stop) throw error(error_kind::argument, "the per-read callback returned " + std::to_string(stop));
+            first_read += n;
+        });
+    });
+}
+
+sshash_status sshash_runs_best_device(const sshash_dict* d, int device, const uint64_t* run_offsets, const sshash_streaming_run* runs,
+                                      uint64_t num_reads, sshash_streaming_run* best, void* hip_stream) {
+    if (!d || (num_reads && (!run_offsets || !best))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] { d->eng->runs_best_device(device, run_offsets, runs, num_reads, best, hip_stream); });
+}
+
+sshash_status sshash_runs_best(const uint64_t* run_offsets, const sshash_streaming_run* runs, uint64_t num_reads, sshash_streaming_run* best) {
+    if (num_reads && (!run_offsets || !best)) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    if (num_reads && !runs && run_offsets[num_reads] > run_offsets[0]) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] {
+        for (uint64_t r = 0; r < num_reads; ++r) {
+            sshash_streaming_run out;
+            std::memset(&out, 0, sizeof(out));
+            uint32_t longest = 0;
+            for (uint64_t i = run_offsets[r]; i < run_offsets[r + 1]; ++i) {  // (in read order, and only a LONGER run takes the lead: among equals the first)
+                const uint32_t length = runs[i].num_kmers & ~SSHASH_RUN_BACKWARD;
+                if (length > longest) {
+                    longest = length;
+                    out = runs[i];
+                }
+            }
+            best[r] = out;
+        }
+    });
+}
+
 sshash_status sshash_streaming_lookup_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
                                              uint64_t num_reads, uint64_t total_bases, const sshash_results* out, uint64_t* report,
                                              void* hip_stream) {

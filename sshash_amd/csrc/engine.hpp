@@ -321,6 +321,21 @@ public:
     void class_best_device(int device, uint32_t const* d_rows, uint64_t n_reads, uint32_t num_classes, uint32_t* d_best /* four words a read */, void* stream) const;
     void class_totals_device(int device, uint32_t const* d_rows, uint64_t n_reads, uint32_t num_classes, uint64_t* d_totals, void* stream) const;
 
+    /* PER READ, its LONGEST RUN (sshash_streaming_best_run[_device]): record r of `d_best` (one sshash_streaming_run of 32 bytes a read,
+       overwritten) = the run of read r with the most k-mers, among equals the first in read order; 32 zero bytes for a read without a
+       hit. Device buffers, asynchronous, always the run kernel, its best-run form: a memset and one launch, never over segments;
+       `d_report` (nullable) is accumulated into. Throws on a minimizer shard. */
+    void streaming_best_run_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases, void* d_best,
+                                   uint64_t* d_report, void* stream) const;
+    /* Host buffers, over all resident replicas; `best` (host, n_reads records) is overwritten. A piece with a read above 2^16 bases
+       goes through the per-k-mer pipeline's run records and runs_best_device. Throws on a minimizer shard. Returns the totals. */
+    streaming_report streaming_best_run_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, void* best) const;
+    /* no_device unless a replica is resident, then argument on a minimizer shard: what the file call asks before it opens its file */
+    void best_run_ready() const;
+    /* The finish of a complete CSR of run records (sshash_runs_best_device): per read the longest of d_runs[d_run_offsets[r] ..
+       d_run_offsets[r + 1]), among equals the first; zero bytes for an empty range. Device buffers, asynchronous, `d_best` overwritten. */
+    void runs_best_device(int device, uint64_t const* d_run_offsets, void const* d_runs, uint64_t n_reads, void* d_best, void* stream) const;
+
     /* Per-k-mer results of the streaming query (streaming_query::lookup for every k-mer of every read,
        include/streaming_query.hpp:56-109): entry read_offsets[r] + j of every non-null array of `d_out` = the k-mer
        starting at base j of read r; places where no k-mer starts are left untouched. `d_report` (nullable): the six

@@ -324,22 +324,46 @@ __device__ __forceinline__ void row_flush(uint64_t* __restrict__ row, bool parti
                          per string id) -- of its read's row of sink.num_classes 32-bit words at sink.records; a label at or above
                          that count is no class and adds nothing. The sums form with another add (classes_add: ONE 32-bit atomic without
                          return into rows the caller zeroed, one 4-byte load a run whatever its length); the row's index is kept as
-                         there, sink.read_of included. One launch. */
+                         there, sink.read_of included. One launch.
+     STREAM_BEST_RUN     the six counters of the batch as STREAM_TOTALS, and PER READ its LONGEST RUN (among equals the first in read
+                         order) as one sshash_streaming_run at sink.records, record r for read r, into records the caller zeroed: the
+                         lane owns its read, keeps the length of the longest run it has stored for it in one register (best_len, zero
+                         when it takes a read) and, where a run is measured, stores the run's record over the read's -- the record
+                         form's two 16-byte stores (run_record_write), plain, no atomics -- when the run is LONGER; runs come in the
+                         order of their place in the read, so the first of equals stays. The hit's string travels across the turn as
+                         in the record form, the read's index as in the counting form. Never over segments: a longest run is not
+                         additive. One launch. */
 enum : int {
     STREAM_TOTALS = 0, STREAM_ROWS = 1, STREAM_RUN_COUNTS = 2, STREAM_RUN_RECORDS = 3, STREAM_COVER = 4, STREAM_DEPTH = 5, STREAM_SUMS = 6,
-    STREAM_CLASSES = 7
+    STREAM_CLASSES = 7, STREAM_BEST_RUN = 8
 };
 
-/* the record of the run of `n` k-mers whose first (in read order) starts at base `at` of the packed reads and lies at offset `off` of
-   the strings, in string `sid`: to place `cursor` of the records, unless that is past what the read or the caller has room for */
+/* the record (sshash_streaming_run, 32 bytes) of the run of `n` k-mers of read `r` whose first (in read order) starts at base `at` of the
+   packed reads and lies at offset `off` of the strings, in string `sid`, to place `index` of `records`: two 16-byte stores, one 8-byte
+   load of the string's begin. The one statement of what a record holds: the record form and the best-run form both store through it. */
+__device__ __forceinline__ void run_record_write(dict_view const& d, void* records, uint64_t index, const uint64_t* __restrict__ begins, uint64_t r, uint64_t at,
+                                                 uint64_t off, uint32_t sid, int ori, uint64_t n) {
+    const uint64_t kmer_id = off - uint64_t(sid) * (d.k - 1), in_string = off - d.endpoints[sid];  // (store_result, lookup_device.hpp)
+    const uint32_t read_pos = uint32_t(at - begins[r]), length = uint32_t(n) | (ori > 0 ? 0u : 0x80000000u);
+    uint4* const rec = static_cast<uint4*>(records) + 2 * index;
+    rec[0] = make_uint4(uint32_t(kmer_id), uint32_t(kmer_id >> 32), sid, 0u);
+    rec[1] = make_uint4(uint32_t(in_string), uint32_t(in_string >> 32), read_pos, length);
+}
+
+/* that record to place `cursor` of the records, unless that is past what the read or the caller has room for */
 __device__ __forceinline__ void run_record_store(dict_view const& d, run_sink const& sink, const uint64_t* __restrict__ begins, uint64_t r,
                                                  uint64_t cursor, uint64_t at, uint64_t off, uint32_t sid, int ori, uint64_t n) {
     if (cursor >= sink.capacity || cursor >= sink.run_offsets[r + 1]) return;
-    const uint64_t kmer_id = off - uint64_t(sid) * (d.k - 1), in_string = off - d.endpoints[sid];  // (store_result, lookup_device.hpp)
-    const uint32_t read_pos = uint32_t(at - begins[r]), length = uint32_t(n) | (ori > 0 ? 0u : 0x80000000u);
-    uint4* const rec = static_cast<uint4*>(sink.records) + 2 * cursor;
-    rec[0] = make_uint4(uint32_t(kmer_id), uint32_t(kmer_id >> 32), sid, 0u);
-    rec[1] = make_uint4(uint32_t(in_string), uint32_t(in_string >> 32), read_pos, length);
+    run_record_write(d, sink.records, cursor, begins, r, at, off, sid, ori, n);
+}
+
+/* (the best-run form) the same run over the record of its read, record `r` of sink.records, when it is longer than the longest stored for
+   that read so far, whose length the lane keeps in `best_len`: strictly longer, so of equals the first in read order stays */
+__device__ __forceinline__ void best_run_store(dict_view const& d, run_sink const& sink, const uint64_t* __restrict__ begins, uint64_t r,
+                                               uint32_t& best_len, uint64_t at, uint64_t off, uint32_t sid, int ori, uint64_t n) {
+    if (n <= best_len) return;
+    best_len = uint32_t(n);  // (a read has fewer than 2^31 bases: the precondition of the run records)
+    run_record_write(d, sink.records, r, begins, r, at, off, sid, ori, n);
 }
 
 /* the k-mer ids [lo, hi), hi > lo, into the bitmap: an atomic OR (nothing comes back: the lane does not wait for it) for the first and the
@@ -422,7 +446,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                      const uint64_t* __restrict__ okay, const uint64_t* __restrict__ begins, const uint64_t* __restrict__ ends, const uint64_t n_reads,
                      const uint64_t reads_per_wave, const uint32_t move_out_every, uint64_t* __restrict__ report, const run_sink sink) {
     constexpr bool PER_READ = MODE == STREAM_ROWS, COUNT_RUNS = MODE == STREAM_RUN_COUNTS, RECORDS = MODE == STREAM_RUN_RECORDS, COVER = MODE == STREAM_COVER,
-                   DEPTH = MODE == STREAM_DEPTH, SUMS = MODE == STREAM_SUMS, CLASSES = MODE == STREAM_CLASSES;
+                   DEPTH = MODE == STREAM_DEPTH, SUMS = MODE == STREAM_SUMS, CLASSES = MODE == STREAM_CLASSES, BEST_RUN = MODE == STREAM_BEST_RUN;
     constexpr bool ROW_INDEX = SUMS || CLASSES;  // the lane keeps the index of its read's row, counted from row_first
     /* (SUMS) when a measured run's two words of P are added to its row: at the end of the turn -- by then the seed's own loads have been
        waited for, and these with them -- or where the run is measured, which makes the wave wait for them there. Late costs seven
@@ -486,6 +510,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
     /* (the run forms) the runs of the lane's read so far; where its next record goes; the string of the hit whose run is to be measured */
     uint32_t n_runs = 0, hit_sid = 0;
     uint64_t cursor = 0;
+    uint32_t best_len = 0;  // (BEST_RUN) the length of the longest run stored for the lane's read so far
     const uint64_t wave_first = wave * reads_per_wave;
     /* (SUMS) the row of the wave's first read: the read itself, or -- segments -- the read of that segment (an empty entry of the table,
        behind the last segment: then so are all of the wave's, and none of them has a k-mer to add) */
@@ -558,6 +583,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                 late_n = run + 1;
                 late_row = my_row;
             }
+            if constexpr (BEST_RUN) best_run_store(d, sink, begins, wave_first + my_row, best_len, cur - 1, off, hit_sid, ori, run + 1);  // (beside the counting below, not instead of it)
             if constexpr (RECORDS) {  // (the hit lies a base before cur)
                 run_record_store(d, sink, begins, wave_first + my_row, cursor, cur - 1, off, hit_sid, ori, run + 1);
                 ++cursor;
@@ -619,6 +645,12 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                 } else if constexpr (RECORDS) {
                     my_row = uint32_t(r - wave_first);
                     cursor = sink.run_offsets[r];
+                } else if constexpr (BEST_RUN) {
+                    if (rd_end - cur >= k) {  // (a read without a k-mer has no run: its record keeps the caller's zeros)
+                        atomicAdd(wave_moved_out + 4, (unsigned long long)(rd_end - cur - k + 1));
+                        my_row = uint32_t(r - wave_first);
+                        best_len = 0;
+                    }
                 } else if constexpr (ROW_INDEX) {
                     if (rd_end - cur >= k) {  // (a read without a k-mer adds nothing: its row keeps the caller's zeros)
                         atomicAdd(wave_moved_out + 4, (unsigned long long)(rd_end - cur - k + 1));
@@ -794,7 +826,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                     found = r.outcome == FAST_HIT;
                     off = r.kmer_offset;
                     ori = r.orientation;
-                    if constexpr (RECORDS || COVER || DEPTH || SUMS || CLASSES) hit_sid = r.string_id;
+                    if constexpr (RECORDS || COVER || DEPTH || SUMS || CLASSES || BEST_RUN) hit_sid = r.string_id;
                     const bool stands = !found && !(where & WALK_VISITED);
                     if (stands || (where & WALK_HEAVY_PENDING)) {
                         /* a miss that stands for the k-mers behind this one: those that elect the same key occurrence (sk_key_persists)
@@ -832,7 +864,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                 found = h.found;
                 off = h.kmer_offset;
                 ori = h.orientation;
-                if constexpr (RECORDS || COVER || DEPTH || SUMS || CLASSES) hit_sid = h.string_id;
+                if constexpr (RECORDS || COVER || DEPTH || SUMS || CLASSES || BEST_RUN) hit_sid = h.string_id;
                 neg_unknown_mini = !SK && !h.found && !h.minimizer_found;
             }
         }
@@ -862,6 +894,9 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                 }
                 if constexpr (CLASSES) {
                     if (!pending) classes_add(sink, row_first + my_row, sink.labels[hit_sid], 1);  // a run of one
+                }
+                if constexpr (BEST_RUN) {
+                    if (!pending) best_run_store(d, sink, begins, wave_first + my_row, best_len, cur, off, hit_sid, ori, 1);  // a run of one: the read's best only when it has none yet
                 }
             } else {
                 ++c_negative;
@@ -1249,15 +1284,17 @@ void launch_run_kernel(device_replica const* rep, dict_view const& d, dim3 grid,
    or RUNS_SUMS alone -- the sums form: the reads' rows at sink.records (n_reads x 2 words) zeroed, then ONE launch that adds every run's
    sum out of sink.values_prefix and its length to its read's row, `report` as with the cover --;
    or RUNS_CLASSES alone -- the classes form, a sink made by class_sink: the reads' rows at sink.records (n_reads x sink.num_classes words of
-   32 bits) zeroed, then ONE launch that adds every run's length to the column of its string's label, `report` as with the cover. */
-enum : int { RUNS_COUNT = 1, RUNS_WRITE = 2, RUNS_COVER = 4, RUNS_DEPTH = 8, RUNS_SUMS = 16, RUNS_CLASSES = 32 };
+   32 bits) zeroed, then ONE launch that adds every run's length to the column of its string's label, `report` as with the cover --;
+   or RUNS_BEST_RUN alone -- the best-run form: the reads' records at sink.records (n_reads x 32 bytes) zeroed, then ONE launch in which
+   every lane stores its read's longest run, `report` as with the cover; never segmented. */
+enum : int { RUNS_COUNT = 1, RUNS_WRITE = 2, RUNS_COVER = 4, RUNS_DEPTH = 8, RUNS_SUMS = 16, RUNS_CLASSES = 32, RUNS_BEST_RUN = 64 };
 void launch_streaming_runs(device_replica const* rep, char const* bases, uint64_t const* offsets, uint64_t n_reads, uint64_t total_bases, uint64_t* report,
                            hipStream_t s, uint64_t* rows = nullptr /* per read: n_reads x 6 words; `report` may then be null */,
                            run_sink sink = run_sink{nullptr, nullptr, 0}, int run_phases = 0,
                            uint64_t S = 0 /* the reads cut into segments of S k-mers (totals, rows, cover, depth, sums, classes; never the run records) */) {
     dict_view const& d = rep->view;
     const bool segmented = S != 0;
-    if (segmented && (run_phases & (RUNS_COUNT | RUNS_WRITE))) throw error(error_kind::internal, "run records are not segmented");
+    if (segmented && (run_phases & (RUNS_COUNT | RUNS_WRITE | RUNS_BEST_RUN))) throw error(error_kind::internal, "run records are not segmented");
     segment_layout L{};
     if (segmented) {
         L = segment_scratch(n_reads, total_bases, S, SCAN_TILE, rows != nullptr);
@@ -1318,7 +1355,7 @@ void launch_streaming_runs(device_replica const* rep, char const* bases, uint64_
         return spare;
     };
     /* the row, counting, record and sums forms keep a lane's read as a 31-bit index into its wave's share -- not the cover and totals forms */
-    if ((rows || (run_phases & (RUNS_COUNT | RUNS_WRITE | RUNS_SUMS | RUNS_CLASSES))) && reads_per_wave >> 31) throw error(error_kind::argument, "too many reads for one call");
+    if ((rows || (run_phases & (RUNS_COUNT | RUNS_WRITE | RUNS_SUMS | RUNS_CLASSES | RUNS_BEST_RUN))) && reads_per_wave >> 31) throw error(error_kind::argument, "too many reads for one call");
     if (run_phases & RUNS_COVER) {
         launch_run_kernel<STREAM_COVER>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), sink);
         if (segmented && caller_report) seams(nullptr, caller_report);  // (nobody reads the six counters: no seam is looked at)
@@ -1337,6 +1374,10 @@ void launch_streaming_runs(device_replica const* rep, char const* bases, uint64_
         if (segmented) sink.read_of = seg + L.read;
         launch_run_kernel<STREAM_CLASSES>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), sink);
         if (segmented && caller_report) seams(nullptr, caller_report);
+    } else if (run_phases & RUNS_BEST_RUN) {
+        /* (a read without a hit, or without a k-mer, keeps these zeros: num_kmers == 0 is "no run") */
+        HIP_CHECK(hipMemsetAsync(sink.records, 0, n_whole_reads * 32, s));
+        launch_run_kernel<STREAM_BEST_RUN>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), sink);
     } else if (run_phases) {
         if (run_phases & RUNS_COUNT) {
             launch_run_kernel<STREAM_RUN_COUNTS>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), sink);
@@ -1550,6 +1591,32 @@ void engine::streaming_classes_device(int device, char const* d_bases, uint64_t 
     const uint64_t S = segments_for(segment_kmers);
     launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, class_sink(d_labels, num_classes, d_rows), RUNS_CLASSES, S);
     if (S) ++m_segmented_launches;  // (counted once the launches are made: a call that threw is none)
+}
+
+/* a shard's run kernel follows a run through k-mers it does not own, and the longest runs of the shards do not combine into the whole
+   index's: no route of the best run serves a minimizer shard */
+static void best_run_refuse_shard(host_index const& idx) {
+    if (idx.num_shards > 1)
+        throw error(error_kind::argument, "a minimizer shard has no longest run: its run kernel follows a run through k-mers of other shards, and the shards' "
+                                          "longest runs do not combine into the whole index's -- use sshash_streaming_runs on the whole index");
+}
+
+/* Per read, its longest run (sshash_streaming_best_run_device): the best-run form of the run kernel, a memset and one launch, never over
+   segments. Every record is written: also when no base is there to look at. */
+void engine::streaming_best_run_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
+                                       void* d_best, uint64_t* d_report, void* stream) const {
+    device_replica const* rep = replica(device);  // (not resident: that error first)
+    if (n_reads == 0) return;
+    if (!d_best) throw error(error_kind::argument, "best pointer is null");
+    best_run_refuse_shard(*m_idx);
+    device_guard guard(device);
+    hipStream_t s = hipStream_t(stream);
+    total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
+    if (total_bases == 0) {  // empty reads only: no run
+        HIP_CHECK(hipMemsetAsync(d_best, 0, n_reads * 32, s));
+        return;
+    }
+    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, run_sink{nullptr, d_best, 0}, RUNS_BEST_RUN);
 }
 
 void engine::depth_finish_device(int device, uint32_t const* d_deltas, uint32_t* d_depth, void* stream) const {
@@ -2284,6 +2351,63 @@ void engine::class_totals_device(int device, uint32_t const* d_rows, uint64_t n_
     HIP_CHECK(hipGetLastError());
 }
 
+/* ---- the finish of a complete CSR of run records: per read its longest run, among equals the first (sshash_runs_best_device). One lane a
+        RECORD, so that a read with thousands of runs costs what any other costs: the lane finds its read by bisection over run_offsets
+        (as stream_segment_fill_kernel finds a segment's read) and issues one 64-bit atomic max, nothing coming back, into the read's word
+        of `keys`, zeroed before: (length << 32) | (0xFFFFFFFF - the record's index within its read) -- the largest key is the longest run
+        and among equals the earliest; bit 31 of num_kmers, the strand, takes no part. A real run has a length of at least 1, so a key of
+        0 is "no record". The number of records, run_offsets[n_reads], stays on the device: the lanes stride over them. Then one lane a
+        READ copies the record its key names, or stores 32 zero bytes. ---- */
+__global__ void __launch_bounds__(256)
+runs_best_kernel(const uint64_t* __restrict__ run_offsets, const uint4* __restrict__ runs, const uint64_t n_reads, unsigned long long* __restrict__ keys) {
+    const uint64_t n_records = run_offsets[n_reads], stride = uint64_t(gridDim.x) * blockDim.x;
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n_records; i += stride) {
+        uint64_t lo = 0, hi = n_reads - 1;  // my read: the largest r with run_offsets[r] <= i (i < run_offsets[n_reads]: its range is not empty and holds i)
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo + 1) / 2;
+            if (run_offsets[mid] <= i) lo = mid;
+            else hi = mid - 1;
+        }
+        const uint32_t length = runs[2 * i + 1].w & 0x7FFFFFFFu;
+        const unsigned long long key = ((unsigned long long)length << 32) | (0xFFFFFFFFu - uint32_t(i - run_offsets[lo]));
+        (void)__hip_atomic_fetch_max(keys + lo, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+__global__ void __launch_bounds__(256)
+runs_best_pick_kernel(const uint64_t* __restrict__ run_offsets, const uint4* __restrict__ runs, const uint64_t n_reads,
+                      const unsigned long long* __restrict__ keys, uint4* __restrict__ best) {
+    const uint64_t r = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (r >= n_reads) return;
+    const unsigned long long key = keys[r];
+    uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a;
+    if (key) {
+        const uint64_t i = run_offsets[r] + (0xFFFFFFFFu - uint32_t(key));
+        a = runs[2 * i];
+        b = runs[2 * i + 1];
+    }
+    best[2 * r] = a;
+    best[2 * r + 1] = b;
+}
+
+void engine::runs_best_device(int device, uint64_t const* d_run_offsets, void const* d_runs, uint64_t n_reads, void* d_best, void* stream) const {
+    device_replica const* rep = replica(device);  // (not resident: that error first)
+    if (n_reads == 0) return;
+    if (!d_run_offsets || !d_best) throw error(error_kind::argument, "null pointer");
+    const uint64_t blocks = (n_reads + 255) / 256;
+    if (blocks >> 31) throw error(error_kind::argument, "too many reads for one launch");
+    device_guard guard(device);
+    hipStream_t s = hipStream_t(stream);
+    device_buffers tmp(rep, s);  // (stream-ordered, out of the replica's pool: handed back behind the pick launch)
+    unsigned long long* keys = tmp.alloc<unsigned long long>(n_reads);
+    HIP_CHECK(hipMemsetAsync(keys, 0, n_reads * sizeof(unsigned long long), s));
+    /* (as many workgroups as keep the chip busy; a CSR without a record runs the key pass for nothing and reads no record) */
+    hipLaunchKernelGGL(runs_best_kernel, dim3(256 * 8), dim3(256), 0, s, d_run_offsets, static_cast<uint4 const*>(d_runs), n_reads, keys);
+    hipLaunchKernelGGL(runs_best_pick_kernel, dim3(uint32_t(blocks)), dim3(256), 0, s, d_run_offsets, static_cast<uint4 const*>(d_runs), n_reads, keys,
+                       static_cast<uint4*>(d_best));
+    HIP_CHECK(hipGetLastError());
+}
+
 void engine::streaming_lookup_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
                                      uint64_t total_bases, result_view const& d_out, uint64_t* d_report, void* stream, uint64_t* d_rows,
                                      run_sink const* runs, uint64_t* d_cover, uint32_t* d_deltas, uint64_t const* d_prefix, uint64_t* d_sums,
@@ -2887,6 +3011,51 @@ streaming_report engine::streaming_runs_host(char const* bases, uint64_t const* 
         base += piece_total[piece];
     }
     return report;
+}
+
+/* what every route of the best run asks of the dictionary before it looks at a read: a resident replica, and no minimizer shard */
+void engine::best_run_ready() const {
+    (void)resident_devices(*this);  // (throws no_device)
+    best_run_refuse_shard(*m_idx);
+}
+
+/* Per read, its longest run, host buffers (sshash_streaming_best_run): pieces and lanes as above (run_piece_lanes), a record per read of
+   the largest piece in the lane's blocks, never over segments. A piece that holds a read above 2^16 bases takes the route
+   streaming_runs_host takes for it -- the position-parallel pipeline with a counting sink, then a writing one: the piece's CSR records
+   -- and the finish of those (runs_best_device) on the same stream. */
+streaming_report engine::streaming_best_run_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, void* best) const {
+    constexpr uint64_t RECORD_BYTES = 32;
+    if (n_reads == 0) return {};
+    best_run_ready();
+    for (uint64_t r = 0; r < n_reads; ++r)
+        if ((read_offsets[r + 1] - read_offsets[r]) >> 31) throw error(error_kind::argument, "a read of 2^31 bases or more: a run record could not hold its positions");
+    const piece_cuts pieces = cut_lane_pieces(read_offsets, n_reads);
+    return run_piece_lanes(*this, bases, read_offsets, pieces, pieces.max_reads * RECORD_BYTES, [&](staged_piece const& p) {
+        void* d_best = p.d_extra;
+        device_buffers tmp(replica(p.device), p.s);  // (stream-ordered; freed behind the piece's last launch)
+        if (p.nb == 0) {  // (no bases: no kernel at all)
+            HIP_CHECK(hipMemsetAsync(d_best, 0, p.n * RECORD_BYTES, p.s));
+        } else if (p.long_read) {
+            uint64_t* d_counts = tmp.alloc<uint64_t>(p.n + 1);
+            const run_sink counting{d_counts, nullptr, 0};
+            streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, nullptr, &counting);
+            uint64_t* const h_total = reinterpret_cast<uint64_t*>(p.h_extra);  // (the pinned block's first word, until the records come back into it)
+            HIP_CHECK(hipMemcpyAsync(h_total, d_counts + p.n, sizeof(uint64_t), hipMemcpyDeviceToHost, p.s));
+            HIP_CHECK(hipStreamSynchronize(p.s));
+            const uint64_t total = *h_total;
+            void* d_records = tmp.alloc<uint64_t>(std::max<uint64_t>(total, 1) * (RECORD_BYTES / 8));
+            if (total) {
+                const run_sink writing{d_counts, d_records, total};
+                streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, nullptr, p.s, nullptr, &writing);
+            }
+            runs_best_device(p.device, d_counts, d_records, p.n, d_best, p.s);
+        } else {
+            streaming_best_run_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, d_best, p.d_report, p.s);
+        }
+        HIP_CHECK(hipMemcpyAsync(p.h_extra, d_best, p.n * RECORD_BYTES, hipMemcpyDeviceToHost, p.s));
+        HIP_CHECK(hipStreamSynchronize(p.s));
+        std::memcpy(static_cast<char*>(best) + p.first * RECORD_BYTES, p.h_extra, p.n * RECORD_BYTES);
+    });
 }
 
 /* The file query of an uncompressed FASTQ (engine.hpp). One reader thread feeding batches through streaming_query_host splits
