@@ -2,6 +2,7 @@
 #pragma once
 
 #include <atomic>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <shared_mutex>
@@ -69,67 +70,70 @@ static_assert(sizeof(run_sink) == 40, "the run kernel takes the sink by value: i
 
 class engine;
 
-/* One cover bitmap (ceil(num_kmers / 64) words, zeroed) in the HBM of every resident replica, for the length of a host call or of a
-   whole query file (streaming.hip); throws no_device when no replica is resident. */
-class cover_bitmaps {
+/* One device array of `count` elements of T (never fewer than one is allocated) in the HBM of every resident replica, for the length of
+   a host call or of a whole query file (streaming.hip). The constructor allocates on one replica after the other and hands every array
+   and its size in bytes, with its device current, to `fill`; when anything throws, what was allocated is freed again. The caller's
+   current device is restored. Throws no_device when no replica is resident. */
+template <class T>
+class replica_arrays {
 public:
-    explicit cover_bitmaps(engine const& eng);
-    ~cover_bitmaps();
-    cover_bitmaps(cover_bitmaps const&) = delete;
-    cover_bitmaps& operator=(cover_bitmaps const&) = delete;
-    uint64_t* on(int device) const;          // the bitmap on `device` (device pointer)
-    void or_into(uint64_t* h_cover) const;  // every replica's bitmap ORed into the caller's host bitmap; the lanes' work is done
-private:
-    uint64_t m_words;
+    using fill_fn = std::function<void(int device, T* array, uint64_t bytes)>;  // done with the array when it returns: the lanes' streams do not wait for the null stream
+    replica_arrays(engine const& eng, uint64_t count, char const* none_here /* what on() throws with */, fill_fn const& fill);
+    ~replica_arrays();
+    replica_arrays(replica_arrays const&) = delete;
+    replica_arrays& operator=(replica_arrays const&) = delete;
+    T* on(int device) const;  // the array on `device` (device pointer)
+protected:
+    uint64_t m_count;
     std::vector<int> m_devices;
-    std::vector<uint64_t*> m_bitmaps;
+    std::vector<T*> m_arrays;
+private:
+    void free_all(int then_device);
+    char const* m_none_here;
+};
+extern template class replica_arrays<uint32_t>;
+extern template class replica_arrays<uint64_t>;
+
+/* One cover bitmap (ceil(num_kmers / 64) words, zeroed) on every resident replica. */
+struct cover_bitmaps : replica_arrays<uint64_t> {
+    explicit cover_bitmaps(engine const& eng);
+    void or_into(uint64_t* h_cover) const;  // every replica's bitmap ORed into the caller's host bitmap; the lanes' work is done
 };
 
-/* The deltas of one depth array (num_kmers words of 32 bits, zeroed) in the HBM of every resident replica, for the length of a host
-   call or of a whole query file (streaming.hip); throws no_device when no replica is resident. */
-class depth_arrays {
-public:
+/* The deltas of one depth array (num_kmers words of 32 bits, zeroed) on every resident replica. */
+struct depth_arrays : replica_arrays<uint32_t> {
     explicit depth_arrays(engine const& eng);
-    ~depth_arrays();
-    depth_arrays(depth_arrays const&) = delete;
-    depth_arrays& operator=(depth_arrays const&) = delete;
-    uint32_t* on(int device) const;           // the deltas on `device` (device pointer)
     void add_into(uint32_t* h_depth) const;  // ONCE, when the lanes' work is done: every replica finishes its deltas in place and its depths are added to the caller's host array
 private:
     engine const& m_eng;
-    uint64_t m_kmers;
-    std::vector<int> m_devices;
-    std::vector<uint32_t*> m_deltas;
 };
 
-/* The 64-bit exclusive prefix sums of one array of values (num_kmers + 1 words, 8 bytes per k-mer) in the HBM of every resident replica,
-   for the length of a host call or of a whole query file (streaming.hip): `h_values` (host, num_kmers words of 32 bits) is uploaded to
-   every replica, the prefix is built there (engine::value_prefix_device) and the 4-byte copy is freed again; throws no_device when no
-   replica is resident. */
-class value_prefixes {
-public:
+/* The 64-bit exclusive prefix sums of one array of values (num_kmers + 1 words, 8 bytes per k-mer) on every resident replica: `h_values`
+   (host, num_kmers words of 32 bits) is uploaded to every replica, the prefix is built there (engine::value_prefix_device) and the
+   4-byte copy is freed again. */
+struct value_prefixes : replica_arrays<uint64_t> {
     value_prefixes(engine const& eng, uint32_t const* h_values, uint32_t at_least);
-    ~value_prefixes();
-    value_prefixes(value_prefixes const&) = delete;
-    value_prefixes& operator=(value_prefixes const&) = delete;
-    uint64_t const* on(int device) const;  // the prefix on `device` (device pointer)
-private:
-    std::vector<int> m_devices;
-    std::vector<uint64_t*> m_prefix;
 };
 
-/* The labels of a classes call (num_strings words of 32 bits) in the HBM of every resident replica, uploaded once, for the length of a
-   host call or of a whole query file (streaming.hip); throws no_device when no replica is resident. */
-class class_labels_on_devices {
-public:
+/* The labels of a classes call (num_strings words of 32 bits) on every resident replica, uploaded once. */
+struct class_labels_on_devices : replica_arrays<uint32_t> {
     class_labels_on_devices(engine const& eng, uint32_t const* h_labels);
-    ~class_labels_on_devices();
-    class_labels_on_devices(class_labels_on_devices const&) = delete;
-    class_labels_on_devices& operator=(class_labels_on_devices const&) = delete;
-    uint32_t const* on(int device) const;  // the labels on `device` (device pointer)
-private:
-    std::vector<int> m_devices;
-    std::vector<uint32_t*> m_labels;
+};
+
+/* What the per-k-mer pipeline fills out of its results beside the arrays of its result_view and the six counters
+   (engine::streaming_lookup_device): device pointers, null = not asked for. */
+struct per_kmer_outputs {
+    uint64_t* rows = nullptr;        // one report per read, n_reads x 6 words, ADDED to
+    run_sink const* runs = nullptr;  // the reads' runs, compacted out of the per-k-mer results: run_offsets overwritten, records below its capacity written
+    uint64_t* cover = nullptr;       // a cover bitmap: the ids of the positive k-mers ORed into it
+    uint32_t* deltas = nullptr;      // the deltas of a depth array: +1 / -1 around every positive k-mer's id added to them
+    /* with the prefix sums of a value per k-mer: the value of every positive k-mer and 1 ADDED to the two words of its read's row */
+    uint64_t const* prefix = nullptr;
+    uint64_t* sums = nullptr;
+    /* with a label per string: 1 ADDED, for every positive k-mer, to the column of its string's label in its read's row of num_classes words */
+    uint32_t const* labels = nullptr;
+    uint32_t num_classes = 0;
+    uint32_t* class_rows = nullptr;
 };
 
 class engine {
@@ -213,10 +217,7 @@ public:
     /* The same with one report PER READ: `rows` (host, n_reads x 6 words in the order of the device report, row r for read r; null:
        the totals only) is overwritten; returns the totals. A piece that holds a read of more than S k-mers takes the run kernel over
        segments (set_read_segments; off: above 2^16 bases the position-parallel pipeline), the others the run kernel; all give the same rows. */
-    streaming_report streaming_query_per_read_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* rows,
-                                                   cover_bitmaps const* cover = nullptr /* streaming_cover_host */,
-                                                   depth_arrays const* depth = nullptr /* streaming_depth_host */,
-                                                   value_prefixes const* prefix = nullptr, uint64_t* sums = nullptr /* streaming_sums_host */) const;
+    streaming_report streaming_query_per_read_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* rows) const;
     /* An uncompressed FASTQ file, read and parsed by the lanes themselves (reads.hpp: fastq_pieces): every lane takes pieces of
        the file from a shared counter, parses a piece straight into its pinned block, uploads it and runs the streaming
        kernels -- no single reader thread, no intermediate batch. Returns false when the file turned out not to be four lines
@@ -342,16 +343,7 @@ public:
        counters, accumulated. Device buffers, asynchronous. */
     void streaming_lookup_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
                                  uint64_t total_bases, result_view const& d_out, uint64_t* d_report, void* stream,
-                                 uint64_t* d_rows = nullptr /* one report per read, n_reads x 6 words, ADDED to */,
-                                 run_sink const* d_runs = nullptr /* the reads' runs, compacted out of the per-k-mer results: run_offsets overwritten,
-                                                                      records below its capacity written */,
-                                 uint64_t* d_cover = nullptr /* a cover bitmap: the ids of the positive k-mers ORed into it */,
-                                 uint32_t* d_deltas = nullptr /* the deltas of a depth array: +1 / -1 around every positive k-mer's id added to them */,
-                                 uint64_t const* d_prefix = nullptr, uint64_t* d_sums = nullptr /* with the prefix sums of a value per k-mer: the value of
-                                                                      every positive k-mer and 1 ADDED to the two words of its read's row */,
-                                 uint32_t const* d_labels = nullptr, uint32_t num_classes = 0, uint32_t* d_class_rows = nullptr /* with a label
-                                                                      per string: 1 ADDED, for every positive k-mer, to the column of its string's
-                                                                      label in its read's row of num_classes words */) const;
+                                 per_kmer_outputs const& more = {}) const;
     streaming_report streaming_lookup_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads,
                                            result_view const& h_out) const;
 
@@ -368,6 +360,10 @@ public:
 
 private:
     uint64_t segments_for(uint64_t asked) const;  // (streaming.hip)
+    /* what the streaming_*_device entry points share behind their own argument checks (streaming.hip) */
+    template <class Launch>
+    void run_kernel_call(int device, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases, void* stream, uint64_t segment_kmers,
+                         void* d_rows, uint64_t row_bytes, Launch const& launch) const;
     std::shared_ptr<host_index> m_idx;
     std::atomic<uint64_t> m_segment_kmers{SEGMENTS_OFF};  // (opt-in: a new dictionary takes the routes it always took)
     std::atomic<bool> m_segment_device_calls{false};

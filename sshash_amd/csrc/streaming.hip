@@ -1259,6 +1259,8 @@ void launch_seams(device_replica const* rep, dict_view const& d, hipStream_t s, 
 
 /* The one place that launches the run kernel: (k > 31, canonical, skew table) -> <W, CANON, SK>, in the form MODE. */
 template <int MODE>
+using run_form = std::integral_constant<int, MODE>;  // (a form as a value: launch_streaming_runs names it where it launches)
+template <int MODE>
 void launch_run_kernel(device_replica const* rep, dict_view const& d, dim3 grid, dim3 block, hipStream_t s, uint64_t const* packed, uint64_t const* okay,
                        uint64_t const* begins, uint64_t const* ends, uint64_t n_reads, uint64_t reads_per_wave, uint32_t move_out_every, uint64_t* report,
                        run_sink const& sink) {
@@ -1356,47 +1358,42 @@ void launch_streaming_runs(device_replica const* rep, char const* bases, uint64_
     };
     /* the row, counting, record and sums forms keep a lane's read as a 31-bit index into its wave's share -- not the cover and totals forms */
     if ((rows || (run_phases & (RUNS_COUNT | RUNS_WRITE | RUNS_SUMS | RUNS_CLASSES | RUNS_BEST_RUN))) && reads_per_wave >> 31) throw error(error_kind::argument, "too many reads for one call");
-    if (run_phases & RUNS_COVER) {
-        launch_run_kernel<STREAM_COVER>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), sink);
-        if (segmented && caller_report) seams(nullptr, caller_report);  // (nobody reads the six counters: no seam is looked at)
-    } else if (run_phases & RUNS_DEPTH) {
-        launch_run_kernel<STREAM_DEPTH>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), sink);
-        if (segmented && caller_report) seams(nullptr, caller_report);
-    } else if (run_phases & RUNS_SUMS) {
-        /* (a run that spans a seam arrives as [lo, mid) and [mid, hi): P[mid] cancels, the lengths add up -- the seams are for the counters alone) */
-        HIP_CHECK(hipMemsetAsync(sink.records, 0, n_whole_reads * 2 * sizeof(uint64_t), s));
-        if (segmented) sink.read_of = seg + L.read;
-        launch_run_kernel<STREAM_SUMS>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), sink);
-        if (segmented && caller_report) seams(nullptr, caller_report);
-    } else if (run_phases & RUNS_CLASSES) {
-        /* (a run that spans a seam arrives as two in the same string, whose lengths add up in the same column) */
-        HIP_CHECK(hipMemsetAsync(sink.records, 0, n_whole_reads * sink.num_classes * sizeof(uint32_t), s));
-        if (segmented) sink.read_of = seg + L.read;
-        launch_run_kernel<STREAM_CLASSES>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), sink);
-        if (segmented && caller_report) seams(nullptr, caller_report);
-    } else if (run_phases & RUNS_BEST_RUN) {
-        /* (a read without a hit, or without a k-mer, keeps these zeros: num_kmers == 0 is "no run") */
-        HIP_CHECK(hipMemsetAsync(sink.records, 0, n_whole_reads * 32, s));
-        launch_run_kernel<STREAM_BEST_RUN>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), sink);
+    /* the launch line of every form: what differs is the form, where the six counters (or the rows) go, and the sink */
+    auto run = [&](auto form, uint64_t* into) {
+        launch_run_kernel<decltype(form)::value>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, into, sink);
+    };
+    const int one_launch = run_phases & (RUNS_COVER | RUNS_DEPTH | RUNS_SUMS | RUNS_CLASSES | RUNS_BEST_RUN);
+    if (one_launch) {
+        /* the forms with a row per read add to it, or leave it alone (the best run of a read without a hit, or without a k-mer: num_kmers == 0 is
+           "no run"): zeroed first. Over segments their lanes look their read up. (A run that spans a seam arrives as [lo, mid) and [mid, hi):
+           the sums' P[mid] cancels, the lengths add up, in the same column of the classes -- the seams are for the counters alone.) */
+        const uint64_t row_bytes = one_launch == RUNS_SUMS ? 2 * sizeof(uint64_t) : one_launch == RUNS_CLASSES ? sink.num_classes * sizeof(uint32_t) : one_launch == RUNS_BEST_RUN ? 32 : 0;
+        if (row_bytes) HIP_CHECK(hipMemsetAsync(sink.records, 0, n_whole_reads * row_bytes, s));
+        if (segmented && (one_launch & (RUNS_SUMS | RUNS_CLASSES))) sink.read_of = seg + L.read;
+        if (one_launch == RUNS_COVER) run(run_form<STREAM_COVER>{}, totals());
+        else if (one_launch == RUNS_DEPTH) run(run_form<STREAM_DEPTH>{}, totals());
+        else if (one_launch == RUNS_SUMS) run(run_form<STREAM_SUMS>{}, totals());
+        else if (one_launch == RUNS_CLASSES) run(run_form<STREAM_CLASSES>{}, totals());
+        else run(run_form<STREAM_BEST_RUN>{}, totals());
+        if (segmented && caller_report) seams(nullptr, caller_report);  // (nobody reads the six counters: no seam is looked at; the best run is never segmented)
     } else if (run_phases) {
         if (run_phases & RUNS_COUNT) {
-            launch_run_kernel<STREAM_RUN_COUNTS>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), sink);
+            run(run_form<STREAM_RUN_COUNTS>{}, totals());
             HIP_CHECK(hipMemsetAsync(sink.run_offsets + n_reads, 0, sizeof(uint64_t), s));
             exclusive_scan_u64(sink.run_offsets, n_reads + 1, scan_sums, s);
         }
-        if (run_phases & RUNS_WRITE)
-            launch_run_kernel<STREAM_RUN_RECORDS>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, nullptr, sink);
+        if (run_phases & RUNS_WRITE) run(run_form<STREAM_RUN_RECORDS>{}, nullptr);
     } else if (rows) {
         if (segmented) {  // a row per segment in the scratch, then the reads' rows out of those and the seams
             uint8_t* const joined = reinterpret_cast<uint8_t*>(seg + L.joined);
-            launch_run_kernel<STREAM_ROWS>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, seg + L.rows, sink);
+            run(run_form<STREAM_ROWS>{}, seg + L.rows);
             seams(joined, nullptr);
             HIP_CHECK(hipMemsetAsync(rows, 0, n_whole_reads * 6 * sizeof(uint64_t), s));
             hipLaunchKernelGGL(stream_segment_rows_kernel, dim3(uint32_t((L.bound + 255) / 256)), dim3(256), 0, s, seg + L.rows, seg + L.read, joined,
                                seg + L.first + n_whole_reads, L.bound, rows);
             HIP_CHECK(hipGetLastError());
         } else {
-            launch_run_kernel<STREAM_ROWS>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, rows, sink);
+            run(run_form<STREAM_ROWS>{}, rows);
         }
         if (report) {
             const uint32_t blocks = uint32_t(std::min<uint64_t>((n_whole_reads + 255) / 256, 1024));
@@ -1404,7 +1401,7 @@ void launch_streaming_runs(device_replica const* rep, char const* bases, uint64_
             HIP_CHECK(hipGetLastError());
         }
     } else {
-        launch_run_kernel<STREAM_TOTALS>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, report, sink);
+        run(run_form<STREAM_TOTALS>{}, report);
         if (segmented && report) seams(nullptr, report);
     }
 }
@@ -1437,17 +1434,31 @@ void streaming_runs_passes(engine const& eng, int device, char const* d_bases, u
 
 }  // namespace
 
+/* What the device entry points of the run kernel share behind their own argument checks: the device made current, the number of bases
+   resolved, and -- empty reads only -- `d_rows` (nullable: the call keeps nothing per read) zeroed, `row_bytes` a read, and nothing
+   launched; else `launch` (void(hipStream_t, uint64_t total_bases, uint64_t S)) with the segments the call takes. */
+template <class Launch>
+void engine::run_kernel_call(int device, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases, void* stream, uint64_t segment_kmers,
+                             void* d_rows, uint64_t row_bytes, Launch const& launch) const {
+    device_guard guard(device);
+    hipStream_t s = hipStream_t(stream);
+    total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
+    if (total_bases == 0) {  // empty reads only: no k-mer, their rows are zero
+        if (d_rows) HIP_CHECK(hipMemsetAsync(d_rows, 0, n_reads * row_bytes, s));
+        return;
+    }
+    const uint64_t S = segments_for(segment_kmers);
+    launch(s, total_bases, S);
+    if (S) ++m_segmented_launches;  // (counted once the launches are made: a call that threw is none)
+}
+
 void engine::streaming_query_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
                                     uint64_t total_bases, uint64_t* d_report, void* stream, uint64_t segment_kmers) const {
     device_replica const* rep = replica(device);
     if (n_reads == 0) return;
-    device_guard guard(device);
-    hipStream_t s = hipStream_t(stream);
-    total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
-    if (total_bases == 0) return;
-    const uint64_t S = segments_for(segment_kmers);
-    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, run_sink{nullptr, nullptr, 0}, 0, S);
-    if (S) ++m_segmented_launches;  // (counted once the launches are made: a call that threw is none)
+    run_kernel_call(device, d_read_offsets, n_reads, total_bases, stream, segment_kmers, nullptr, 0, [&](hipStream_t s, uint64_t nb, uint64_t S) {
+        launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, nb, d_report, s, nullptr, run_sink{nullptr, nullptr, 0}, 0, S);
+    });
 }
 
 /* The setting of sshash_set_read_segments (engine.hpp). */
@@ -1478,16 +1489,9 @@ void engine::streaming_query_per_read_device(int device, char const* d_bases, ui
     device_replica const* rep = replica(device);
     if (n_reads == 0) return;
     if (!d_rows) throw error(error_kind::argument, "per-read output pointer is null");
-    device_guard guard(device);
-    hipStream_t s = hipStream_t(stream);
-    total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
-    if (total_bases == 0) {  // empty reads only: their rows are zero
-        HIP_CHECK(hipMemsetAsync(d_rows, 0, n_reads * 6 * sizeof(uint64_t), s));
-        return;
-    }
-    const uint64_t S = segments_for(segment_kmers);
-    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, d_rows, run_sink{nullptr, nullptr, 0}, 0, S);
-    if (S) ++m_segmented_launches;  // (counted once the launches are made: a call that threw is none)
+    run_kernel_call(device, d_read_offsets, n_reads, total_bases, stream, segment_kmers, d_rows, 6 * sizeof(uint64_t), [&](hipStream_t s, uint64_t nb, uint64_t S) {
+        launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, nb, d_report, s, d_rows, run_sink{nullptr, nullptr, 0}, 0, S);
+    });
 }
 
 /* The runs of every read (sshash_streaming_runs_device): count -> scan -> write, always the run kernel. */
@@ -1507,13 +1511,9 @@ void engine::streaming_cover_device(int device, char const* d_bases, uint64_t co
     device_replica const* rep = replica(device);  // (not resident: that error first)
     if (n_reads == 0) return;
     if (!d_cover) throw error(error_kind::argument, "cover pointer is null");
-    device_guard guard(device);
-    hipStream_t s = hipStream_t(stream);
-    total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
-    if (total_bases == 0) return;  // empty reads only: no k-mer
-    const uint64_t S = segments_for(segment_kmers);
-    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, run_sink{nullptr, d_cover, 0}, RUNS_COVER, S);
-    if (S) ++m_segmented_launches;  // (counted once the launches are made: a call that threw is none)
+    run_kernel_call(device, d_read_offsets, n_reads, total_bases, stream, segment_kmers, nullptr, 0, [&](hipStream_t s, uint64_t nb, uint64_t S) {
+        launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, nb, d_report, s, nullptr, run_sink{nullptr, d_cover, 0}, RUNS_COVER, S);
+    });
 }
 
 /* How often the reads hold each k-mer of the dictionary (sshash_streaming_depth_device): the depth form of the run kernel, one launch,
@@ -1526,13 +1526,9 @@ void engine::streaming_depth_device(int device, char const* d_bases, uint64_t co
     /* (a run is measured along the STRING, which a shard holds whole: behind a k-mer of its own it runs on through k-mers of other
        shards, and the shards' arrays added would hold those twice. The cover does not mind -- OR --, a count does.) */
     if (m_idx->num_shards > 1) throw error(error_kind::argument, "a minimizer shard counts per k-mer: use the host call (sshash_streaming_depth)");
-    device_guard guard(device);
-    hipStream_t s = hipStream_t(stream);
-    total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
-    if (total_bases == 0) return;  // empty reads only: no k-mer
-    const uint64_t S = segments_for(segment_kmers);
-    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, run_sink{nullptr, d_deltas, 0}, RUNS_DEPTH, S);
-    if (S) ++m_segmented_launches;  // (counted once the launches are made: a call that threw is none)
+    run_kernel_call(device, d_read_offsets, n_reads, total_bases, stream, segment_kmers, nullptr, 0, [&](hipStream_t s, uint64_t nb, uint64_t S) {
+        launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, nb, d_report, s, nullptr, run_sink{nullptr, d_deltas, 0}, RUNS_DEPTH, S);
+    });
 }
 
 /* The prefix sums of a value per k-mer (sshash_value_prefix_device): widened, word num_kmers zero, scanned in place. */
@@ -1558,16 +1554,9 @@ void engine::streaming_sums_device(int device, char const* d_bases, uint64_t con
     if (!d_prefix || !d_sums) throw error(error_kind::argument, "prefix or sums pointer is null");
     /* (as the depth: a shard's run kernel follows a run through k-mers of other shards, and the shards' rows added would hold those twice) */
     if (m_idx->num_shards > 1) throw error(error_kind::argument, "a minimizer shard counts per k-mer: use the host call (sshash_streaming_sums)");
-    device_guard guard(device);
-    hipStream_t s = hipStream_t(stream);
-    total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
-    if (total_bases == 0) {  // empty reads only: their rows are zero
-        HIP_CHECK(hipMemsetAsync(d_sums, 0, n_reads * 2 * sizeof(uint64_t), s));
-        return;
-    }
-    const uint64_t S = segments_for(segment_kmers);
-    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, run_sink{nullptr, d_sums, 0, d_prefix, nullptr}, RUNS_SUMS, S);
-    if (S) ++m_segmented_launches;  // (counted once the launches are made: a call that threw is none)
+    run_kernel_call(device, d_read_offsets, n_reads, total_bases, stream, segment_kmers, d_sums, 2 * sizeof(uint64_t), [&](hipStream_t s, uint64_t nb, uint64_t S) {
+        launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, nb, d_report, s, nullptr, run_sink{nullptr, d_sums, 0, d_prefix, nullptr}, RUNS_SUMS, S);
+    });
 }
 
 /* Per read, its positive k-mers by class of string (sshash_streaming_classes_device): the classes form of the run kernel, a memset and
@@ -1581,16 +1570,9 @@ void engine::streaming_classes_device(int device, char const* d_bases, uint64_t 
     if (num_classes == 0 || num_classes > MAX_CLASSES) throw error(error_kind::argument, "num_classes must be 1 .. 4096");
     /* (as the depth and the sums: a shard's run kernel follows a run through k-mers of other shards, and the shards' rows added would hold those twice) */
     if (m_idx->num_shards > 1) throw error(error_kind::argument, "a minimizer shard counts per k-mer: use the host call (sshash_streaming_classes)");
-    device_guard guard(device);
-    hipStream_t s = hipStream_t(stream);
-    total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
-    if (total_bases == 0) {  // empty reads only: their rows are zero
-        HIP_CHECK(hipMemsetAsync(d_rows, 0, n_reads * num_classes * sizeof(uint32_t), s));
-        return;
-    }
-    const uint64_t S = segments_for(segment_kmers);
-    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, class_sink(d_labels, num_classes, d_rows), RUNS_CLASSES, S);
-    if (S) ++m_segmented_launches;  // (counted once the launches are made: a call that threw is none)
+    run_kernel_call(device, d_read_offsets, n_reads, total_bases, stream, segment_kmers, d_rows, num_classes * sizeof(uint32_t), [&](hipStream_t s, uint64_t nb, uint64_t S) {
+        launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, nb, d_report, s, nullptr, class_sink(d_labels, num_classes, d_rows), RUNS_CLASSES, S);
+    });
 }
 
 /* a shard's run kernel follows a run through k-mers it does not own, and the longest runs of the shards do not combine into the whole
@@ -1609,14 +1591,9 @@ void engine::streaming_best_run_device(int device, char const* d_bases, uint64_t
     if (n_reads == 0) return;
     if (!d_best) throw error(error_kind::argument, "best pointer is null");
     best_run_refuse_shard(*m_idx);
-    device_guard guard(device);
-    hipStream_t s = hipStream_t(stream);
-    total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
-    if (total_bases == 0) {  // empty reads only: no run
-        HIP_CHECK(hipMemsetAsync(d_best, 0, n_reads * 32, s));
-        return;
-    }
-    launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, run_sink{nullptr, d_best, 0}, RUNS_BEST_RUN);
+    run_kernel_call(device, d_read_offsets, n_reads, total_bases, stream, 0 /* never over segments */, d_best, 32, [&](hipStream_t s, uint64_t nb, uint64_t) {
+        launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, nb, d_report, s, nullptr, run_sink{nullptr, d_best, 0}, RUNS_BEST_RUN);
+    });
 }
 
 void engine::depth_finish_device(int device, uint32_t const* d_deltas, uint32_t* d_depth, void* stream) const {
@@ -2409,13 +2386,12 @@ void engine::runs_best_device(int device, uint64_t const* d_run_offsets, void co
 }
 
 void engine::streaming_lookup_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads,
-                                     uint64_t total_bases, result_view const& d_out, uint64_t* d_report, void* stream, uint64_t* d_rows,
-                                     run_sink const* runs, uint64_t* d_cover, uint32_t* d_deltas, uint64_t const* d_prefix, uint64_t* d_sums,
-                                     uint32_t const* d_labels, uint32_t num_classes, uint32_t* d_class_rows) const {
+                                     uint64_t total_bases, result_view const& d_out, uint64_t* d_report, void* stream, per_kmer_outputs const& more) const {
     device_replica const* rep = replica(device);
-    if ((d_prefix != nullptr) != (d_sums != nullptr)) throw error(error_kind::internal, "the sums go with their prefix");
-    if ((d_labels != nullptr) != (d_class_rows != nullptr) || (d_labels && num_classes == 0)) throw error(error_kind::internal, "the class rows go with their labels");
-    if (!d_out.kmer_id && !d_report && !d_rows && !runs && !d_cover && !d_deltas && !d_sums && !d_class_rows) throw error(error_kind::argument, "neither a kmer_id array nor a report to fill");
+    run_sink const* const runs = more.runs;
+    if ((more.prefix != nullptr) != (more.sums != nullptr)) throw error(error_kind::internal, "the sums go with their prefix");
+    if ((more.labels != nullptr) != (more.class_rows != nullptr) || (more.labels && more.num_classes == 0)) throw error(error_kind::internal, "the class rows go with their labels");
+    if (!d_out.kmer_id && !d_report && !more.rows && !runs && !more.cover && !more.deltas && !more.sums && !more.class_rows) throw error(error_kind::argument, "neither a kmer_id array nor a report to fill");
     if (d_out.minimizer_found) throw error(error_kind::argument, "the streaming lookup does not report minimizer_found");
     if (n_reads == 0 || total_bases == 0) return;
     device_guard guard(device);
@@ -2457,27 +2433,27 @@ void engine::streaming_lookup_device(int device, char const* d_bases, uint64_t c
                            advance(out, first), sid + first, ori + first, d_report, first != 0);
         HIP_CHECK(hipGetLastError());
     }
-    if (d_rows) {
+    if (more.rows) {
         hipLaunchKernelGGL(stream_classify_rows_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, flags, total_bases, ids, sid, ori,
-                           d_read_offsets, n_reads, d_rows);
+                           d_read_offsets, n_reads, more.rows);
         HIP_CHECK(hipGetLastError());
     }
-    if (d_cover) {
-        hipLaunchKernelGGL(cover_mark_ids_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, flags, ids, total_bases, d_cover);
+    if (more.cover) {
+        hipLaunchKernelGGL(cover_mark_ids_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, flags, ids, total_bases, more.cover);
         HIP_CHECK(hipGetLastError());
     }
-    if (d_deltas) {
-        hipLaunchKernelGGL(depth_mark_ids_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, flags, ids, total_bases, d.num_kmers, d_deltas);
+    if (more.deltas) {
+        hipLaunchKernelGGL(depth_mark_ids_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, flags, ids, total_bases, d.num_kmers, more.deltas);
         HIP_CHECK(hipGetLastError());
     }
-    if (d_sums) {
-        hipLaunchKernelGGL(sums_add_ids_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, flags, ids, total_bases, d.num_kmers, d_prefix,
-                           d_read_offsets, n_reads, d_sums);
+    if (more.sums) {
+        hipLaunchKernelGGL(sums_add_ids_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, flags, ids, total_bases, d.num_kmers, more.prefix,
+                           d_read_offsets, n_reads, more.sums);
         HIP_CHECK(hipGetLastError());
     }
-    if (d_class_rows) {
-        hipLaunchKernelGGL(classes_add_ids_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, flags, ids, sid, total_bases, d.num_kmers, d_labels,
-                           num_classes, d_read_offsets, n_reads, d_class_rows);
+    if (more.class_rows) {
+        hipLaunchKernelGGL(classes_add_ids_kernel, dim3(uint32_t((total_bases + 255) / 256)), dim3(256), 0, s, flags, ids, sid, total_bases, d.num_kmers, more.labels,
+                           more.num_classes, d_read_offsets, n_reads, more.class_rows);
         HIP_CHECK(hipGetLastError());
     }
     if (runs) {
@@ -2601,10 +2577,17 @@ uint64_t piece_segments(uint64_t const* offsets, uint64_t n_reads, uint32_t k, u
     return 0;
 }
 
+/* Does a piece take the per-k-mer pipeline, and not the run kernel? One that holds a long read which is not cut into segments; and, of a
+   call that COUNTS per k-mer (`counts`: depth, sums, classes), every piece of a minimizer shard -- only that pipeline asks of every k-mer
+   whether the shard owns it (streaming_depth_device). */
+bool takes_per_kmer_pipeline(engine const& eng, bool long_read, uint64_t segments, bool counts) {
+    return (long_read && !segments) || (counts && eng.index().num_shards > 1);
+}
+
 /* the six counters of one staged piece, added to d_report */
 void piece_totals(engine const& eng, int device, bool long_read, uint64_t segments, char const* d_bases, uint64_t const* d_offsets, uint64_t n_reads,
                   uint64_t n_bases, uint64_t* d_report, hipStream_t s) {
-    if (long_read && !segments) eng.streaming_lookup_device(device, d_bases, d_offsets, n_reads, n_bases, result_view{}, d_report, s);
+    if (takes_per_kmer_pipeline(eng, long_read, segments, false)) eng.streaming_lookup_device(device, d_bases, d_offsets, n_reads, n_bases, result_view{}, d_report, s);
     else eng.streaming_query_device(device, d_bases, d_offsets, n_reads, n_bases, d_report, s, segments);
 }
 
@@ -2676,264 +2659,213 @@ streaming_report run_piece_lanes(engine const& eng, char const* bases, uint64_t 
     return total;
 }
 
+/* A piece's records, `row_bytes` a read at p.d_extra, come back through the lane's pinned block (the caller's array is pageable) to the
+   piece's first read in `h_rows`. */
+void piece_rows_back(staged_piece const& p, uint64_t row_bytes, void* h_rows) {
+    HIP_CHECK(hipMemcpyAsync(p.h_extra, p.d_extra, p.n * row_bytes, hipMemcpyDeviceToHost, p.s));
+    HIP_CHECK(hipStreamSynchronize(p.s));
+    std::memcpy(static_cast<char*>(h_rows) + p.first * row_bytes, p.h_extra, p.n * row_bytes);
+}
+
+/* The calls that return one record per read (rows, sums, classes, the best run), for one piece: the records are made at p.d_extra --
+   zeroed where the per-k-mer pass (`by_ids`) will add to them or, no bases, no kernel runs at all; else the run kernel (`by_runs`)
+   writes every one of them -- and come back. */
+template <class ByIds, class ByRuns>
+void piece_rows(staged_piece const& p, bool per_kmer, uint64_t row_bytes, void* h_rows, ByIds const& by_ids, ByRuns const& by_runs) {
+    if (per_kmer || p.nb == 0) HIP_CHECK(hipMemsetAsync(p.d_extra, 0, p.n * row_bytes, p.s));
+    if (per_kmer) by_ids();
+    else if (p.nb) by_runs();
+    piece_rows_back(p, row_bytes, h_rows);
+}
+
 }  // namespace
 
 streaming_report engine::streaming_query_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads) const {
-    return streaming_query_per_read_host(bases, read_offsets, n_reads, nullptr);
-}
-
-/* With `rows` (n_reads x 6 words, host) a lane's device block also holds a row for every read of the largest piece, and a piece's rows
-   come back into the caller's array at the piece's first read. With `cover` (and no rows) a piece's k-mers are marked in the bitmap
-   that `cover` keeps on the lane's device: the lanes of a device share it, OR commutes. With `depth` (and neither) its runs are added to
-   the deltas that `depth` keeps there: addition commutes as well. With `sums` (and `prefix`, and none of those) a lane's device block
-   holds two words for every read of the largest piece, out of the prefix sums that `prefix` keeps there, and they come back as the rows
-   do. (A minimizer shard takes the per-k-mer route for every piece: only
-   that one asks of every k-mer whether the shard owns it -- streaming_depth_device.) */
-streaming_report engine::streaming_query_per_read_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* rows,
-                                                       cover_bitmaps const* cover, depth_arrays const* depth, value_prefixes const* prefix,
-                                                       uint64_t* sums) const {
     if (n_reads == 0) return {};
-    const piece_cuts pieces = cut_lane_pieces(read_offsets, n_reads);
-    const uint64_t row_bytes = 6 * sizeof(uint64_t), sum_bytes = 2 * sizeof(uint64_t);
-    const uint64_t extra_bytes = rows ? pieces.max_reads * row_bytes : sums ? pieces.max_reads * sum_bytes : 0;
-    return run_piece_lanes(*this, bases, read_offsets, pieces, extra_bytes, [&](staged_piece const& p) {
-        const bool per_kmer = p.long_read && !p.segments;  // (no segments: a long read's piece takes the position-parallel pipeline)
-        if (rows) {
-            uint64_t* d_rows = reinterpret_cast<uint64_t*>(p.d_extra);
-            if (per_kmer || p.nb == 0) HIP_CHECK(hipMemsetAsync(d_rows, 0, p.n * row_bytes, p.s));  // (the classify pass adds to its rows; no bases: no kernel at all)
-            if (per_kmer) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, d_rows);
-            else if (p.nb) streaming_query_per_read_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, d_rows, p.d_report, p.s, p.segments);
-            HIP_CHECK(hipMemcpyAsync(p.h_extra, d_rows, p.n * row_bytes, hipMemcpyDeviceToHost, p.s));  // (through the lane's pinned block: the caller's array is pageable)
-        } else if (cover) {
-            if (per_kmer) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, nullptr, nullptr, cover->on(p.device));
-            else if (p.nb) streaming_cover_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, cover->on(p.device), p.d_report, p.s, p.segments);
-        } else if (depth) {
-            if (per_kmer || m_idx->num_shards > 1) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, nullptr, nullptr, nullptr, depth->on(p.device));
-            else if (p.nb) streaming_depth_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, depth->on(p.device), p.d_report, p.s, p.segments);
-        } else if (sums) {
-            uint64_t* d_sums = reinterpret_cast<uint64_t*>(p.d_extra);
-            const bool by_ids = per_kmer || m_idx->num_shards > 1;
-            if (by_ids || p.nb == 0) HIP_CHECK(hipMemsetAsync(d_sums, 0, p.n * sum_bytes, p.s));  // (the per-k-mer pass adds to its rows; no bases: no kernel at all)
-            if (by_ids) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, nullptr, nullptr, nullptr, nullptr, prefix->on(p.device), d_sums);
-            else if (p.nb) streaming_sums_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, prefix->on(p.device), d_sums, p.d_report, p.s, p.segments);
-            HIP_CHECK(hipMemcpyAsync(p.h_extra, d_sums, p.n * sum_bytes, hipMemcpyDeviceToHost, p.s));
-        } else {
-            piece_totals(*this, p.device, p.long_read, p.segments, p.d_bases, p.d_offsets, p.n, p.nb, p.d_report, p.s);
-        }
+    return run_piece_lanes(*this, bases, read_offsets, cut_lane_pieces(read_offsets, n_reads), 0, [&](staged_piece const& p) {
+        piece_totals(*this, p.device, p.long_read, p.segments, p.d_bases, p.d_offsets, p.n, p.nb, p.d_report, p.s);
         HIP_CHECK(hipStreamSynchronize(p.s));
-        if (rows) std::memcpy(rows + 6 * p.first, p.h_extra, p.n * row_bytes);
-        else if (sums) std::memcpy(sums + 2 * p.first, p.h_extra, p.n * sum_bytes);
     });
 }
 
-/* ---- the cover bitmaps of a host call: one per resident replica, zeroed, in HBM for as long as the object lives (a call over host
-        buffers, or a whole query file), ORed into the caller's host bitmap at the end ---- */
-cover_bitmaps::cover_bitmaps(engine const& eng) : m_words((eng.index().num_kmers + 63) / 64), m_devices(resident_devices(eng)) {
+/* A lane's device block also holds a row for every read of the largest piece, and a piece's rows come back into the caller's array at
+   the piece's first read. */
+streaming_report engine::streaming_query_per_read_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* rows) const {
+    if (!rows) return streaming_query_host(bases, read_offsets, n_reads);
+    if (n_reads == 0) return {};
+    const piece_cuts pieces = cut_lane_pieces(read_offsets, n_reads);
+    const uint64_t row_bytes = 6 * sizeof(uint64_t);
+    return run_piece_lanes(*this, bases, read_offsets, pieces, pieces.max_reads * row_bytes, [&](staged_piece const& p) {
+        uint64_t* d_rows = reinterpret_cast<uint64_t*>(p.d_extra);
+        piece_rows(p, takes_per_kmer_pipeline(*this, p.long_read, p.segments, false), row_bytes, rows,
+                   [&] {
+                       per_kmer_outputs more;
+                       more.rows = d_rows;
+                       streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, more);
+                   },
+                   [&] { streaming_query_per_read_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, d_rows, p.d_report, p.s, p.segments); });
+    });
+}
+
+/* ---- one device array per resident replica (engine.hpp) ---- */
+static void* replica_alloc(uint64_t bytes) {
+    void* p = nullptr;
+    HIP_CHECK(hipMalloc(&p, bytes));
+    return p;
+}
+
+/* (a fill) zeroed by the time it returns: the lanes' streams do not wait for the null stream */
+static void zero_now(int, void* p, uint64_t bytes) {
+    HIP_CHECK(hipMemsetAsync(p, 0, bytes, nullptr));
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+}
+
+template <class T>
+replica_arrays<T>::replica_arrays(engine const& eng, uint64_t count, char const* none_here, fill_fn const& fill)
+    : m_count(count), m_devices(resident_devices(eng)), m_none_here(none_here) {
     int prev = 0;
     HIP_CHECK(hipGetDevice(&prev));
     try {
         for (int device : m_devices) {
             HIP_CHECK(hipSetDevice(device));
-            void* p = nullptr;
-            HIP_CHECK(hipMalloc(&p, std::max<uint64_t>(m_words, 1) * sizeof(uint64_t)));
-            m_bitmaps.push_back(static_cast<uint64_t*>(p));
-            HIP_CHECK(hipMemsetAsync(p, 0, std::max<uint64_t>(m_words, 1) * sizeof(uint64_t), nullptr));
-            HIP_CHECK(hipStreamSynchronize(nullptr));  // (the lanes' streams do not wait for the null stream)
+            const uint64_t bytes = std::max<uint64_t>(count, 1) * sizeof(T);
+            m_arrays.push_back(static_cast<T*>(replica_alloc(bytes)));
+            fill(device, m_arrays.back(), bytes);
         }
     } catch (...) {
-        for (size_t i = 0; i < m_bitmaps.size(); ++i) {
-            (void)hipSetDevice(m_devices[i]);
-            (void)hipFree(m_bitmaps[i]);
-        }
-        (void)hipSetDevice(prev);
+        free_all(prev);
         throw;
     }
     (void)hipSetDevice(prev);
 }
 
-cover_bitmaps::~cover_bitmaps() {
-    int prev = 0;
-    if (hipGetDevice(&prev) != hipSuccess) return;
-    for (size_t i = 0; i < m_bitmaps.size(); ++i) {
+template <class T>
+void replica_arrays<T>::free_all(int then_device) {
+    for (size_t i = 0; i < m_arrays.size(); ++i) {
         (void)hipSetDevice(m_devices[i]);
-        (void)hipFree(m_bitmaps[i]);
+        (void)hipFree(m_arrays[i]);
     }
-    (void)hipSetDevice(prev);
+    (void)hipSetDevice(then_device);
 }
 
-uint64_t* cover_bitmaps::on(int device) const {
-    for (size_t i = 0; i < m_devices.size(); ++i)
-        if (m_devices[i] == device) return m_bitmaps[i];
-    throw error(error_kind::internal, "no cover bitmap on this device");
+template <class T>
+replica_arrays<T>::~replica_arrays() {
+    int prev = 0;
+    if (hipGetDevice(&prev) == hipSuccess) free_all(prev);
 }
+
+template <class T>
+T* replica_arrays<T>::on(int device) const {
+    for (size_t i = 0; i < m_devices.size(); ++i)
+        if (m_devices[i] == device) return m_arrays[i];
+    throw error(error_kind::internal, m_none_here);
+}
+
+template class replica_arrays<uint32_t>;
+template class replica_arrays<uint64_t>;
+
+/* ---- the cover bitmaps of a host call: zeroed, ORed into the caller's host bitmap at the end ---- */
+cover_bitmaps::cover_bitmaps(engine const& eng) : replica_arrays(eng, (eng.index().num_kmers + 63) / 64, "no cover bitmap on this device", zero_now) {}
 
 void cover_bitmaps::or_into(uint64_t* h_cover) const {
     const uint64_t chunk = uint64_t(1) << 21;  // 16 MiB of words at a time: the host side stays bounded
-    std::vector<uint64_t> part(std::min(chunk, m_words));
+    std::vector<uint64_t> part(std::min(chunk, m_count));
     for (size_t i = 0; i < m_devices.size(); ++i) {
         device_guard guard(m_devices[i]);
-        for (uint64_t at = 0; at < m_words; at += chunk) {
-            const uint64_t n = std::min(chunk, m_words - at);
-            HIP_CHECK(hipMemcpy(part.data(), m_bitmaps[i] + at, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        for (uint64_t at = 0; at < m_count; at += chunk) {
+            const uint64_t n = std::min(chunk, m_count - at);
+            HIP_CHECK(hipMemcpy(part.data(), m_arrays[i] + at, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
             for (uint64_t j = 0; j < n; ++j) h_cover[at + j] |= part[j];
         }
     }
 }
 
+/* A piece's k-mers are marked in the bitmap that `cover` keeps on the lane's device: the lanes of a device share it, OR commutes. */
 streaming_report engine::streaming_cover_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, cover_bitmaps const& cover) const {
-    return streaming_query_per_read_host(bases, read_offsets, n_reads, nullptr, &cover);
-}
-
-/* ---- the depth arrays of a host call: the deltas of one depth array per resident replica, zeroed, in HBM for as long as the object
-        lives; at the end every replica finishes its own on the device and the depths are added into the caller's host array ---- */
-depth_arrays::depth_arrays(engine const& eng) : m_eng(eng), m_kmers(eng.index().num_kmers), m_devices(resident_devices(eng)) {
-    int prev = 0;
-    HIP_CHECK(hipGetDevice(&prev));
-    const uint64_t bytes = std::max<uint64_t>(m_kmers, 1) * sizeof(uint32_t);
-    try {
-        for (int device : m_devices) {
-            HIP_CHECK(hipSetDevice(device));
-            void* p = nullptr;
-            HIP_CHECK(hipMalloc(&p, bytes));
-            m_deltas.push_back(static_cast<uint32_t*>(p));
-            HIP_CHECK(hipMemsetAsync(p, 0, bytes, nullptr));
-            HIP_CHECK(hipStreamSynchronize(nullptr));  // (the lanes' streams do not wait for the null stream)
+    if (n_reads == 0) return {};
+    return run_piece_lanes(*this, bases, read_offsets, cut_lane_pieces(read_offsets, n_reads), 0, [&](staged_piece const& p) {
+        if (takes_per_kmer_pipeline(*this, p.long_read, p.segments, false)) {
+            per_kmer_outputs more;
+            more.cover = cover.on(p.device);
+            streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, more);
+        } else if (p.nb) {
+            streaming_cover_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, cover.on(p.device), p.d_report, p.s, p.segments);
         }
-    } catch (...) {
-        for (size_t i = 0; i < m_deltas.size(); ++i) {
-            (void)hipSetDevice(m_devices[i]);
-            (void)hipFree(m_deltas[i]);
-        }
-        (void)hipSetDevice(prev);
-        throw;
-    }
-    (void)hipSetDevice(prev);
+        HIP_CHECK(hipStreamSynchronize(p.s));
+    });
 }
 
-depth_arrays::~depth_arrays() {
-    int prev = 0;
-    if (hipGetDevice(&prev) != hipSuccess) return;
-    for (size_t i = 0; i < m_deltas.size(); ++i) {
-        (void)hipSetDevice(m_devices[i]);
-        (void)hipFree(m_deltas[i]);
-    }
-    (void)hipSetDevice(prev);
-}
-
-uint32_t* depth_arrays::on(int device) const {
-    for (size_t i = 0; i < m_devices.size(); ++i)
-        if (m_devices[i] == device) return m_deltas[i];
-    throw error(error_kind::internal, "no depth array on this device");
-}
+/* ---- the depth arrays of a host call: deltas, zeroed; at the end every replica finishes its own on the device and the depths are added
+        into the caller's host array ---- */
+depth_arrays::depth_arrays(engine const& eng) : replica_arrays(eng, eng.index().num_kmers, "no depth array on this device", zero_now), m_eng(eng) {}
 
 void depth_arrays::add_into(uint32_t* h_depth) const {
     const uint64_t chunk = uint64_t(1) << 22;  // 16 MiB of words at a time: the host side stays bounded
-    std::vector<uint32_t> part(std::min(chunk, m_kmers));
+    std::vector<uint32_t> part(std::min(chunk, m_count));
     for (size_t i = 0; i < m_devices.size(); ++i) {
-        if (m_kmers == 0) break;
+        if (m_count == 0) break;
         device_guard guard(m_devices[i]);
-        m_eng.depth_finish_device(m_devices[i], m_deltas[i], m_deltas[i], nullptr);  // in place: the deltas are gone
+        m_eng.depth_finish_device(m_devices[i], m_arrays[i], m_arrays[i], nullptr);  // in place: the deltas are gone
         HIP_CHECK(hipStreamSynchronize(nullptr));
-        for (uint64_t at = 0; at < m_kmers; at += chunk) {
-            const uint64_t n = std::min(chunk, m_kmers - at);
-            HIP_CHECK(hipMemcpy(part.data(), m_deltas[i] + at, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (uint64_t at = 0; at < m_count; at += chunk) {
+            const uint64_t n = std::min(chunk, m_count - at);
+            HIP_CHECK(hipMemcpy(part.data(), m_arrays[i] + at, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
             for (uint64_t j = 0; j < n; ++j) h_depth[at + j] += part[j];
         }
     }
 }
 
+/* A piece's runs are added to the deltas that `depth` keeps on the lane's device: addition commutes as the cover's OR does. */
+streaming_report engine::streaming_depth_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, depth_arrays const& depth) const {
+    if (n_reads == 0) return {};
+    return run_piece_lanes(*this, bases, read_offsets, cut_lane_pieces(read_offsets, n_reads), 0, [&](staged_piece const& p) {
+        if (takes_per_kmer_pipeline(*this, p.long_read, p.segments, true)) {
+            per_kmer_outputs more;
+            more.deltas = depth.on(p.device);
+            streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, more);
+        } else if (p.nb) {
+            streaming_depth_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, depth.on(p.device), p.d_report, p.s, p.segments);
+        }
+        HIP_CHECK(hipStreamSynchronize(p.s));
+    });
+}
+
 /* ---- the prefix sums of a host call's values: uploaded to every resident replica and built there; the 4-byte copy goes, the 8 bytes per
-        k-mer stay in HBM for as long as the object lives ---- */
-value_prefixes::value_prefixes(engine const& eng, uint32_t const* h_values, uint32_t at_least) : m_devices(resident_devices(eng)) {
-    const uint64_t n = eng.index().num_kmers;
-    int prev = 0;
-    HIP_CHECK(hipGetDevice(&prev));
-    void* values = nullptr;
-    try {
-        for (int device : m_devices) {
-            HIP_CHECK(hipSetDevice(device));
-            void* p = nullptr;
-            HIP_CHECK(hipMalloc(&p, (n + 1) * sizeof(uint64_t)));
-            m_prefix.push_back(static_cast<uint64_t*>(p));
-            HIP_CHECK(hipMalloc(&values, std::max<uint64_t>(n, 1) * sizeof(uint32_t)));
-            HIP_CHECK(hipMemcpy(values, h_values, n * sizeof(uint32_t), hipMemcpyHostToDevice));
-            eng.value_prefix_device(device, static_cast<uint32_t const*>(values), at_least, m_prefix.back(), nullptr);
-            HIP_CHECK(hipStreamSynchronize(nullptr));  // (the lanes' streams do not wait for the null stream)
-            HIP_CHECK(hipFree(values));
-            values = nullptr;
-        }
-    } catch (...) {
-        if (values) (void)hipFree(values);
-        for (size_t i = 0; i < m_prefix.size(); ++i) {
-            (void)hipSetDevice(m_devices[i]);
-            (void)hipFree(m_prefix[i]);
-        }
-        (void)hipSetDevice(prev);
-        throw;
-    }
-    (void)hipSetDevice(prev);
-}
+        k-mer stay ---- */
+value_prefixes::value_prefixes(engine const& eng, uint32_t const* h_values, uint32_t at_least)
+    : replica_arrays(eng, eng.index().num_kmers + 1, "no value prefix on this device", [&](int device, uint64_t* prefix, uint64_t) {
+          const uint64_t n = eng.index().num_kmers;
+          const std::unique_ptr<void, void (*)(void*)> values(replica_alloc(std::max<uint64_t>(n, 1) * sizeof(uint32_t)), [](void* p) { (void)hipFree(p); });
+          HIP_CHECK(hipMemcpy(values.get(), h_values, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+          eng.value_prefix_device(device, static_cast<uint32_t const*>(values.get()), at_least, prefix, nullptr);
+          HIP_CHECK(hipStreamSynchronize(nullptr));  // (the lanes' streams do not wait for the null stream)
+      }) {}
 
-value_prefixes::~value_prefixes() {
-    int prev = 0;
-    if (hipGetDevice(&prev) != hipSuccess) return;
-    for (size_t i = 0; i < m_prefix.size(); ++i) {
-        (void)hipSetDevice(m_devices[i]);
-        (void)hipFree(m_prefix[i]);
-    }
-    (void)hipSetDevice(prev);
-}
-
-uint64_t const* value_prefixes::on(int device) const {
-    for (size_t i = 0; i < m_devices.size(); ++i)
-        if (m_devices[i] == device) return m_prefix[i];
-    throw error(error_kind::internal, "no value prefix on this device");
-}
-
+/* A lane's device block holds two words for every read of the largest piece, out of the prefix sums that `prefix` keeps on its device;
+   they come back as the rows do. */
 streaming_report engine::streaming_sums_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, value_prefixes const& prefix,
                                              uint64_t* sums) const {
-    return streaming_query_per_read_host(bases, read_offsets, n_reads, nullptr, nullptr, nullptr, &prefix, sums);
+    if (n_reads == 0) return {};
+    const piece_cuts pieces = cut_lane_pieces(read_offsets, n_reads);
+    const uint64_t row_bytes = 2 * sizeof(uint64_t);
+    return run_piece_lanes(*this, bases, read_offsets, pieces, pieces.max_reads * row_bytes, [&](staged_piece const& p) {
+        uint64_t* d_sums = reinterpret_cast<uint64_t*>(p.d_extra);
+        piece_rows(p, takes_per_kmer_pipeline(*this, p.long_read, p.segments, true), row_bytes, sums,
+                   [&] {
+                       per_kmer_outputs more;
+                       more.prefix = prefix.on(p.device);
+                       more.sums = d_sums;
+                       streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, more);
+                   },
+                   [&] { streaming_sums_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, prefix.on(p.device), d_sums, p.d_report, p.s, p.segments); });
+    });
 }
 
-/* ---- the labels of a host call: one copy in the HBM of every resident replica for as long as the object lives ---- */
-class_labels_on_devices::class_labels_on_devices(engine const& eng, uint32_t const* h_labels) : m_devices(resident_devices(eng)) {
-    const uint64_t n = eng.index().num_strings;
-    int prev = 0;
-    HIP_CHECK(hipGetDevice(&prev));
-    try {
-        for (int device : m_devices) {
-            HIP_CHECK(hipSetDevice(device));
-            void* p = nullptr;
-            HIP_CHECK(hipMalloc(&p, std::max<uint64_t>(n, 1) * sizeof(uint32_t)));
-            m_labels.push_back(static_cast<uint32_t*>(p));
-            HIP_CHECK(hipMemcpy(p, h_labels, n * sizeof(uint32_t), hipMemcpyHostToDevice));  // (synchronous: the lanes' streams find it there)
-        }
-    } catch (...) {
-        for (size_t i = 0; i < m_labels.size(); ++i) {
-            (void)hipSetDevice(m_devices[i]);
-            (void)hipFree(m_labels[i]);
-        }
-        (void)hipSetDevice(prev);
-        throw;
-    }
-    (void)hipSetDevice(prev);
-}
-
-class_labels_on_devices::~class_labels_on_devices() {
-    int prev = 0;
-    if (hipGetDevice(&prev) != hipSuccess) return;
-    for (size_t i = 0; i < m_labels.size(); ++i) {
-        (void)hipSetDevice(m_devices[i]);
-        (void)hipFree(m_labels[i]);
-    }
-    (void)hipSetDevice(prev);
-}
-
-uint32_t const* class_labels_on_devices::on(int device) const {
-    for (size_t i = 0; i < m_devices.size(); ++i)
-        if (m_devices[i] == device) return m_labels[i];
-    throw error(error_kind::internal, "no labels on this device");
-}
+/* ---- the labels of a host call: one copy on every resident replica ---- */
+class_labels_on_devices::class_labels_on_devices(engine const& eng, uint32_t const* h_labels)
+    : replica_arrays(eng, eng.index().num_strings, "no labels on this device", [&](int, uint32_t* labels, uint64_t) {
+          HIP_CHECK(hipMemcpy(labels, h_labels, eng.index().num_strings * sizeof(uint32_t), hipMemcpyHostToDevice));  // (synchronous: the lanes' streams find it there)
+      }) {}
 
 /* The rows travel as the sums' do, through `num_classes` words a read of the lane's blocks; a piece holds no more reads than make
    CLASS_PIECE_BYTES of rows (beside cut_lane_pieces' bytes of bases and its hook: 4096 reads at the cap of 4096 classes). */
@@ -2946,19 +2878,23 @@ streaming_report engine::streaming_classes_host(char const* bases, uint64_t cons
     const piece_cuts pieces = cut_lane_pieces(read_offsets, n_reads, CLASS_PIECE_BYTES / row_bytes);
     return run_piece_lanes(*this, bases, read_offsets, pieces, pieces.max_reads * row_bytes, [&](staged_piece const& p) {
         uint32_t* d_rows = reinterpret_cast<uint32_t*>(p.d_extra);
-        const bool by_ids = (p.long_read && !p.segments) || m_idx->num_shards > 1;
-        if (by_ids || p.nb == 0) HIP_CHECK(hipMemsetAsync(d_rows, 0, p.n * row_bytes, p.s));  // (the per-k-mer pass adds to its rows; no bases: no kernel at all)
-        if (by_ids) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                            labels.on(p.device), num_classes, d_rows);
-        else if (p.nb) streaming_classes_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, labels.on(p.device), num_classes, d_rows, p.d_report, p.s, p.segments);
-        HIP_CHECK(hipMemcpyAsync(p.h_extra, d_rows, p.n * row_bytes, hipMemcpyDeviceToHost, p.s));
-        HIP_CHECK(hipStreamSynchronize(p.s));
-        std::memcpy(rows + p.first * num_classes, p.h_extra, p.n * row_bytes);
+        piece_rows(p, takes_per_kmer_pipeline(*this, p.long_read, p.segments, true), row_bytes, rows,
+                   [&] {
+                       per_kmer_outputs more;
+                       more.labels = labels.on(p.device);
+                       more.num_classes = num_classes;
+                       more.class_rows = d_rows;
+                       streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, more);
+                   },
+                   [&] { streaming_classes_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, labels.on(p.device), num_classes, d_rows, p.d_report, p.s, p.segments); });
     });
 }
 
-streaming_report engine::streaming_depth_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, depth_arrays const& depth) const {
-    return streaming_query_per_read_host(bases, read_offsets, n_reads, nullptr, nullptr, &depth);
+/* the per-k-mer pipeline with the reads' runs for its one output: what the run records and the best run take for a piece with a long read */
+static void piece_runs_by_ids(engine const& eng, staged_piece const& p, run_sink const& sink, uint64_t* d_report) {
+    per_kmer_outputs more;
+    more.runs = &sink;
+    eng.streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, d_report, p.s, more);
 }
 
 /* The runs of every read, host buffers (sshash_streaming_runs): pieces and lanes as above (run_piece_lanes). A piece's
@@ -2981,10 +2917,9 @@ streaming_report engine::streaming_runs_host(char const* bases, uint64_t const* 
     const streaming_report report = run_piece_lanes(*this, bases, read_offsets, pieces, (pieces.max_reads + 1) * sizeof(uint64_t), [&](staged_piece const& p) {
         uint64_t* d_counts = reinterpret_cast<uint64_t*>(p.d_extra);
         uint64_t const* counts = reinterpret_cast<uint64_t const*>(p.h_extra);
-        const run_sink counting{d_counts, nullptr, 0};
         if (p.nb == 0) HIP_CHECK(hipMemsetAsync(d_counts, 0, (p.n + 1) * sizeof(uint64_t), p.s));
-        else if (p.long_read) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, nullptr, &counting);
-        else streaming_runs_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, d_counts, nullptr, 0, p.d_report, p.s);  // (run records are never segmented)
+        else if (p.long_read) piece_runs_by_ids(*this, p, run_sink{d_counts, nullptr, 0}, p.d_report);  // (run records are never segmented: a long read's piece takes the per-k-mer pipeline)
+        else streaming_runs_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, d_counts, nullptr, 0, p.d_report, p.s);
         HIP_CHECK(hipMemcpyAsync(p.h_extra, d_counts, (p.n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, p.s));
         HIP_CHECK(hipStreamSynchronize(p.s));
         const uint64_t total = counts[p.n];
@@ -2996,7 +2931,7 @@ streaming_report engine::streaming_runs_host(char const* bases, uint64_t const* 
             device_buffers records(replica(p.device), p.s);
             void* d_records = records.alloc<uint64_t>(total * (RECORD_BYTES / 8));
             const run_sink writing{d_counts, d_records, total};
-            if (p.long_read) streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, nullptr, p.s, nullptr, &writing);
+            if (p.long_read) piece_runs_by_ids(*this, p, writing, nullptr);
             else streaming_runs_passes(*this, p.device, p.d_bases, p.d_offsets, p.n, p.nb, writing, nullptr, p.s, false, true);
             HIP_CHECK(hipMemcpyAsync(mine.data(), d_records, total * RECORD_BYTES, hipMemcpyDeviceToHost, p.s));
             HIP_CHECK(hipStreamSynchronize(p.s));
@@ -3032,29 +2967,21 @@ streaming_report engine::streaming_best_run_host(char const* bases, uint64_t con
     const piece_cuts pieces = cut_lane_pieces(read_offsets, n_reads);
     return run_piece_lanes(*this, bases, read_offsets, pieces, pieces.max_reads * RECORD_BYTES, [&](staged_piece const& p) {
         void* d_best = p.d_extra;
-        device_buffers tmp(replica(p.device), p.s);  // (stream-ordered; freed behind the piece's last launch)
-        if (p.nb == 0) {  // (no bases: no kernel at all)
-            HIP_CHECK(hipMemsetAsync(d_best, 0, p.n * RECORD_BYTES, p.s));
-        } else if (p.long_read) {
-            uint64_t* d_counts = tmp.alloc<uint64_t>(p.n + 1);
-            const run_sink counting{d_counts, nullptr, 0};
-            streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, p.d_report, p.s, nullptr, &counting);
-            uint64_t* const h_total = reinterpret_cast<uint64_t*>(p.h_extra);  // (the pinned block's first word, until the records come back into it)
-            HIP_CHECK(hipMemcpyAsync(h_total, d_counts + p.n, sizeof(uint64_t), hipMemcpyDeviceToHost, p.s));
-            HIP_CHECK(hipStreamSynchronize(p.s));
-            const uint64_t total = *h_total;
-            void* d_records = tmp.alloc<uint64_t>(std::max<uint64_t>(total, 1) * (RECORD_BYTES / 8));
-            if (total) {
-                const run_sink writing{d_counts, d_records, total};
-                streaming_lookup_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, result_view{}, nullptr, p.s, nullptr, &writing);
-            }
-            runs_best_device(p.device, d_counts, d_records, p.n, d_best, p.s);
-        } else {
-            streaming_best_run_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, d_best, p.d_report, p.s);
+        if (!p.long_read) {
+            piece_rows(p, false, RECORD_BYTES, best, [] {}, [&] { streaming_best_run_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, d_best, p.d_report, p.s); });
+            return;
         }
-        HIP_CHECK(hipMemcpyAsync(p.h_extra, d_best, p.n * RECORD_BYTES, hipMemcpyDeviceToHost, p.s));
+        device_buffers tmp(replica(p.device), p.s);  // (stream-ordered; freed behind the piece's last launch)
+        uint64_t* d_counts = tmp.alloc<uint64_t>(p.n + 1);
+        piece_runs_by_ids(*this, p, run_sink{d_counts, nullptr, 0}, p.d_report);
+        uint64_t* const h_total = reinterpret_cast<uint64_t*>(p.h_extra);  // (the pinned block's first word, until the records come back into it)
+        HIP_CHECK(hipMemcpyAsync(h_total, d_counts + p.n, sizeof(uint64_t), hipMemcpyDeviceToHost, p.s));
         HIP_CHECK(hipStreamSynchronize(p.s));
-        std::memcpy(static_cast<char*>(best) + p.first * RECORD_BYTES, p.h_extra, p.n * RECORD_BYTES);
+        const uint64_t total = *h_total;
+        void* d_records = tmp.alloc<uint64_t>(std::max<uint64_t>(total, 1) * (RECORD_BYTES / 8));
+        if (total) piece_runs_by_ids(*this, p, run_sink{d_counts, d_records, total}, nullptr);
+        runs_best_device(p.device, d_counts, d_records, p.n, d_best, p.s);
+        piece_rows_back(p, RECORD_BYTES, best);
     });
 }
 

@@ -290,6 +290,16 @@ def case_segments(d, sequences, k, S):
         os.environ["SSHASH_AMD_TEST_HOOKS"] = hook
         same(everything(d, reads, False), want_host, f"S = {S}, host calls, {hook}")
         same(everything(d, reads, True), want_device, f"S = {S}, device calls, {hook}")
+    # five pieces of four reads, the third without a base: nothing is launched for it (totals, rows, cover, depth), its rows are zeros
+    picks = [i for i, r in enumerate(reads) if len(r) >= k][:16]
+    batch = [reads[i] for i in picks[:8]] + [""] * 4 + [reads[i] for i in picks[8:]]
+    batch_rows = np.concatenate([want_rows[picks[:8]], np.zeros((4, 6), dtype=np.uint64), want_rows[picks[8:]]])
+    batch_totals, batch_ids = batch_rows.sum(0), np.concatenate([ids[i] for i in picks])
+    assert batch_rows[:8, 1].sum() > 0 and batch_rows[12:, 1].sum() > 0
+    want_batch = {"totals": batch_totals, "rows": batch_rows, "rows_report": batch_totals, "cover": bitmap_of(batch_ids, d.cover_words()),
+                  "cover_report": batch_totals, "depth": depth_of(batch_ids, d.num_kmers()), "depth_report": batch_totals}
+    os.environ["SSHASH_AMD_TEST_HOOKS"] = "stream_piece_reads=4"
+    same(everything(d, batch, False), want_batch, f"S = {S}, host calls, a piece of reads without a base")
     del os.environ["SSHASH_AMD_TEST_HOOKS"]
     # ---- no reads, reads without a base ----
     d.streaming_depth_device(0, 0, 0, 0, 0)

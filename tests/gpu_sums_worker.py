@@ -355,6 +355,13 @@ def main():
         assert got.tobytes() == want.tobytes() and (report_row(rep) == want_report).all(), hook
         got, rep = device_sums(d, reads, p_prefix, report=[0] * 6)
         assert got.tobytes() == want.tobytes() and (rep == want_report).all(), hook
+    # five pieces of four reads, the third without a base: nothing is launched for it, and its rows come back as zeros at their reads
+    os.environ["SSHASH_AMD_TEST_HOOKS"] = "stream_piece_reads=4"
+    picks = [i for i in range(n) if i != long_at and lengths[i] >= k][:16]
+    assert hits[picks[:8]].sum() > 0 and hits[picks[8:]].sum() > 0
+    got, rep = d.streaming_sums([reads[i] for i in picks[:8]] + [""] * 4 + [reads[i] for i in picks[8:]], random_values)
+    want_batch = np.concatenate([want[picks[:8]], np.zeros(4, dtype=want.dtype), want[picks[8:]]])
+    assert got.tobytes() == want_batch.tobytes() and (report_row(rep) == per_read_rows[picks].sum(0)).all(), "a piece of reads without a base"
     del os.environ["SSHASH_AMD_TEST_HOOKS"]
 
     # ---- segments: many lanes add into one row ----

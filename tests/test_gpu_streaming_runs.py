@@ -240,6 +240,14 @@ def test_accounting(case_name, request, monkeypatch):
         monkeypatch.setenv("SSHASH_AMD_TEST_HOOKS", "stream_piece_reads=" + piece)
         ro, runs, report = d.streaming_runs(reads)
         assert (ro == want_offsets).all() and same_records(runs, want_runs) and report_row(report) == total_report.tolist(), piece
+    # five pieces of four reads, the third without a base: nothing is launched for it, its reads have no run and the stitching goes on behind it
+    with_runs = [i for i in range(len(reads)) if want_offsets[i + 1] > want_offsets[i]][:16]
+    batch = [reads[i] for i in with_runs[:8]] + [""] * 4 + [reads[i] for i in with_runs[8:]]
+    batch_offsets, batch_runs = oracle_runs(case.oracle, batch)
+    assert len(with_runs) == 16 and (np.diff(batch_offsets)[8:12] == 0).all() and batch_offsets[8] > 0 and batch_offsets[-1] > batch_offsets[12]
+    monkeypatch.setenv("SSHASH_AMD_TEST_HOOKS", "stream_piece_reads=4")
+    ro, runs, report = d.streaming_runs(batch)
+    assert (ro == batch_offsets).all() and same_records(runs, batch_runs) and report == d.streaming_query(batch), "a piece of reads without a base"
     monkeypatch.delenv("SSHASH_AMD_TEST_HOOKS")
     # reads without any base, and no reads at all
     dro, druns, rep = device_runs(d, ["", "", ""], capacity=4, report=[1] * 6, total_bases=0)
