@@ -15,7 +15,6 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
-#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -259,9 +258,7 @@ public:
 
     /* include/dictionary.hpp:81-82 */
     streaming_query_report streaming_query_from_file(std::string const& filename, bool multiline) const {
-        sshash_streaming_report s;
-        check(sshash_streaming_query_from_file(m_h, filename.c_str(), multiline, &s));
-        return to_report(s);
+        return reported([&](sshash_streaming_report* s) { return sshash_streaming_query_from_file(m_h, filename.c_str(), multiline, s); });
     }
 
     /* The streaming query's report for every read on its own (sshash_streaming_query_per_read; no reference counterpart as a call:
@@ -317,9 +314,7 @@ public:
     }
     streaming_query_report streaming_cover(char const* bases, uint64_t const* read_offsets, uint64_t num_reads, std::vector<uint64_t>& cover) const {
         cover.resize(cover_words(), 0);
-        sshash_streaming_report s;
-        check(sshash_streaming_cover(m_h, bases, read_offsets, num_reads, cover.data(), &s));
-        return to_report(s);
+        return reported([&](sshash_streaming_report* s) { return sshash_streaming_cover(m_h, bases, read_offsets, num_reads, cover.data(), s); });
     }
     /* device buffers, asynchronous on hip_stream (sshash_streaming_cover_device): d_cover -- cover_words() uint64 -- is ORed into,
        d_report -- may be null -- six counters (accumulated into) */
@@ -330,9 +325,7 @@ public:
     /* a query file into one bitmap (sshash_streaming_cover_from_file) */
     streaming_query_report streaming_cover_from_file(std::string const& filename, bool multiline, std::vector<uint64_t>& cover) const {
         cover.resize(cover_words(), 0);
-        sshash_streaming_report s;
-        check(sshash_streaming_cover_from_file(m_h, filename.c_str(), multiline, cover.data(), &s));
-        return to_report(s);
+        return reported([&](sshash_streaming_report* s) { return sshash_streaming_cover_from_file(m_h, filename.c_str(), multiline, cover.data(), s); });
     }
     /* covered k-mers per string and in all (sshash_cover_string_counts: CPU, no GPU needed; _device: device buffers, asynchronous) */
     uint64_t cover_string_counts(std::vector<uint64_t> const& cover, std::vector<uint64_t>& counts) const {
@@ -352,9 +345,7 @@ public:
        words zero) and added into. Returns the batch's report. */
     streaming_query_report streaming_depth(char const* bases, uint64_t const* read_offsets, uint64_t num_reads, std::vector<uint32_t>& depth) const {
         depth.resize(num_kmers(), 0);
-        sshash_streaming_report s;
-        check(sshash_streaming_depth(m_h, bases, read_offsets, num_reads, depth.data(), &s));
-        return to_report(s);
+        return reported([&](sshash_streaming_report* s) { return sshash_streaming_depth(m_h, bases, read_offsets, num_reads, depth.data(), s); });
     }
     /* device buffers, asynchronous on hip_stream (sshash_streaming_depth_device): d_deltas -- num_kmers() uint32, a difference array -- is
        added into, d_report -- may be null -- six counters (accumulated into); depth_finish_device turns deltas into depths (d_depth may
@@ -386,9 +377,7 @@ public:
     /* a query file into one depth array (sshash_streaming_depth_from_file) */
     streaming_query_report streaming_depth_from_file(std::string const& filename, bool multiline, std::vector<uint32_t>& depth) const {
         depth.resize(num_kmers(), 0);
-        sshash_streaming_report s;
-        check(sshash_streaming_depth_from_file(m_h, filename.c_str(), multiline, depth.data(), &s));
-        return to_report(s);
+        return reported([&](sshash_streaming_report* s) { return sshash_streaming_depth_from_file(m_h, filename.c_str(), multiline, depth.data(), s); });
     }
     /* the sum of depth over every string's ids, and over all (sshash_depth_string_sums: CPU, no GPU needed; _device: device buffers,
        asynchronous); the mean depth of string s is sums[s] / string_size(s) */
@@ -413,9 +402,9 @@ public:
         if (values.size() < num_kmers()) throw std::invalid_argument("values has fewer than num_kmers() words");
         sums.assign(num_reads, sshash_read_sum{0, 0});
         std::vector<uint32_t> no_values(1);
-        sshash_streaming_report s;
-        check(sshash_streaming_sums(m_h, bases, read_offsets, num_reads, values.empty() ? no_values.data() : values.data(), at_least, sums.data(), &s));
-        return to_report(s);
+        return reported([&](sshash_streaming_report* s) {
+            return sshash_streaming_sums(m_h, bases, read_offsets, num_reads, values.empty() ? no_values.data() : values.data(), at_least, sums.data(), s);
+        });
     }
     /* device buffers, asynchronous on hip_stream: d_prefix (num_kmers() + 1 uint64) out of d_values (sshash_value_prefix_device), and the
        rows out of d_prefix (sshash_streaming_sums_device): d_sums -- num_reads rows -- is overwritten, d_report -- may be null -- six
@@ -433,18 +422,11 @@ public:
     streaming_query_report streaming_sums_from_file(std::string const& filename, bool multiline, std::vector<uint32_t> const& values, uint32_t at_least,
                                                     Fn&& fn) const {
         if (values.size() < num_kmers()) throw std::invalid_argument("values has fewer than num_kmers() words");
-        struct context {
-            std::remove_reference_t<Fn>* fn;
-        } ctx{&fn};
+        auto cb = callback_of<sshash_read_sum>(fn);
         std::vector<uint32_t> no_values(1);
-        sshash_streaming_report s;
-        check(sshash_streaming_sums_from_file(
-            m_h, filename.c_str(), multiline, values.empty() ? no_values.data() : values.data(), at_least,
-            [](void* c, uint64_t first_read, uint64_t n, const sshash_read_sum* rows) -> int {
-                return int((*static_cast<context*>(c)->fn)(first_read, rows, n));
-            },
-            &ctx, &s));
-        return to_report(s);
+        return reported([&](sshash_streaming_report* s) {
+            return sshash_streaming_sums_from_file(m_h, filename.c_str(), multiline, values.empty() ? no_values.data() : values.data(), at_least, cb.thunk, &cb, s);
+        });
     }
 
     /* CLASSES (sshash_streaming_classes; the definitions are in include/sshash_amd.h): per read, its positive k-mers by class of string.
@@ -455,10 +437,10 @@ public:
         if (labels.size() < num_strings()) throw std::invalid_argument("labels has fewer than num_strings() words");
         rows.assign(num_reads * uint64_t(num_classes), 0u);
         std::vector<uint32_t> spare(1);
-        sshash_streaming_report s;
-        check(sshash_streaming_classes(m_h, bases, read_offsets, num_reads, labels.empty() ? spare.data() : labels.data(), num_classes,
-                                       rows.empty() ? spare.data() : rows.data(), &s));
-        return to_report(s);
+        return reported([&](sshash_streaming_report* s) {
+            return sshash_streaming_classes(m_h, bases, read_offsets, num_reads, labels.empty() ? spare.data() : labels.data(), num_classes,
+                                            rows.empty() ? spare.data() : rows.data(), s);
+        });
     }
     /* device buffers, asynchronous on hip_stream: d_rows -- num_reads x num_classes uint32 -- is overwritten, d_labels -- num_strings()
        uint32 -- only read, d_report -- may be null -- six counters (accumulated into) */
@@ -472,16 +454,11 @@ public:
     streaming_query_report streaming_classes_from_file(std::string const& filename, bool multiline, std::vector<uint32_t> const& labels,
                                                        uint32_t num_classes, Fn&& fn) const {
         if (labels.size() < num_strings()) throw std::invalid_argument("labels has fewer than num_strings() words");
-        struct context {
-            std::remove_reference_t<Fn>* fn;
-        } ctx{&fn};
+        auto cb = callback_of<uint32_t>(fn);
         std::vector<uint32_t> spare(1);
-        sshash_streaming_report s;
-        check(sshash_streaming_classes_from_file(
-            m_h, filename.c_str(), multiline, labels.empty() ? spare.data() : labels.data(), num_classes,
-            [](void* c, uint64_t first_read, uint64_t n, const uint32_t* rows) -> int { return int((*static_cast<context*>(c)->fn)(first_read, rows, n)); },
-            &ctx, &s));
-        return to_report(s);
+        return reported([&](sshash_streaming_report* s) {
+            return sshash_streaming_classes_from_file(m_h, filename.c_str(), multiline, labels.empty() ? spare.data() : labels.data(), num_classes, cb.thunk, &cb, s);
+        });
     }
     /* the finish of the rows (sshash_class_best, sshash_class_totals): on the host over host arrays, or device buffers, asynchronous */
     static std::vector<sshash_read_class> class_best(std::vector<uint32_t> const& rows, uint32_t num_classes) {
@@ -508,9 +485,7 @@ public:
        over segments; throws on a minimizer shard. Returns the batch's report. */
     streaming_query_report streaming_best_run(char const* bases, uint64_t const* read_offsets, uint64_t num_reads, std::vector<sshash_streaming_run>& best) const {
         best.assign(num_reads, sshash_streaming_run{});
-        sshash_streaming_report s;
-        check(sshash_streaming_best_run(m_h, bases, read_offsets, num_reads, best.data(), &s));
-        return to_report(s);
+        return reported([&](sshash_streaming_report* s) { return sshash_streaming_best_run(m_h, bases, read_offsets, num_reads, best.data(), s); });
     }
     /* device buffers, asynchronous on hip_stream: d_best -- num_reads records -- is overwritten, d_report -- may be null -- six counters
        (accumulated into) */
@@ -522,15 +497,8 @@ public:
        a non-zero return stops the query (std::runtime_error). Fn: int(uint64_t, sshash_streaming_run const*, uint64_t). */
     template <typename Fn>
     streaming_query_report streaming_best_run_from_file(std::string const& filename, bool multiline, Fn&& fn) const {
-        struct context {
-            std::remove_reference_t<Fn>* fn;
-        } ctx{&fn};
-        sshash_streaming_report s;
-        check(sshash_streaming_best_run_from_file(
-            m_h, filename.c_str(), multiline,
-            [](void* c, uint64_t first_read, uint64_t n, const sshash_streaming_run* best) -> int { return int((*static_cast<context*>(c)->fn)(first_read, best, n)); },
-            &ctx, &s));
-        return to_report(s);
+        auto cb = callback_of<sshash_streaming_run>(fn);
+        return reported([&](sshash_streaming_report* s) { return sshash_streaming_best_run_from_file(m_h, filename.c_str(), multiline, cb.thunk, &cb, s); });
     }
     /* the finish over a complete CSR of run records (sshash_runs_best): on the host over host arrays, or device buffers, asynchronous */
     static std::vector<sshash_streaming_run> runs_best(std::vector<uint64_t> const& run_offsets, std::vector<sshash_streaming_run> const& runs) {
@@ -549,19 +517,13 @@ public:
     template <typename Fn>
     streaming_query_report streaming_query_from_file_per_read(std::string const& filename, bool multiline, Fn&& fn) const {
         static_assert(sizeof(streaming_query_report) == sizeof(sshash_streaming_report), "the same six counters");
-        struct context {
-            std::remove_reference_t<Fn>* fn;
-        } ctx{&fn};
-        sshash_streaming_report s;
-        check(sshash_streaming_query_from_file_per_read(
-            m_h, filename.c_str(), multiline,
-            [](void* c, uint64_t first_read, uint64_t n, const sshash_streaming_report* rows) -> int {
-                std::vector<streaming_query_report> mine(n);
-                for (uint64_t i = 0; i < n; ++i) mine[i] = to_report(rows[i]);
-                return int((*static_cast<context*>(c)->fn)(first_read, static_cast<streaming_query_report const*>(mine.data()), n));
-            },
-            &ctx, &s));
-        return to_report(s);
+        auto converted = [&fn](uint64_t first_read, const sshash_streaming_report* rows, uint64_t n) {  // (the C rows as this header's type)
+            std::vector<streaming_query_report> mine(n);
+            for (uint64_t i = 0; i < n; ++i) mine[i] = to_report(rows[i]);
+            return fn(first_read, static_cast<streaming_query_report const*>(mine.data()), n);
+        };
+        auto cb = callback_of<sshash_streaming_report>(converted);
+        return reported([&](sshash_streaming_report* s) { return sshash_streaming_query_from_file_per_read(m_h, filename.c_str(), multiline, cb.thunk, &cb, s); });
     }
 
     /* streaming_query::lookup for every k-mer of every read, batched (sshash_streaming_lookup): `r` gets one entry per
@@ -579,9 +541,7 @@ public:
         std::fill(r.string_end.begin(), r.string_end.end(), constants::invalid_uint64);
         std::fill(r.kmer_orientation.begin(), r.kmer_orientation.end(), int8_t(constants::forward_orientation));
         std::fill(r.minimizer_found.begin(), r.minimizer_found.end(), uint8_t(1));
-        sshash_streaming_report s;
-        check(sshash_streaming_lookup(m_h, bases, read_offsets, num_reads, &out, &s));
-        return to_report(s);
+        return reported([&](sshash_streaming_report* s) { return sshash_streaming_lookup(m_h, bases, read_offsets, num_reads, &out, s); });
     }
 
     /* dictionary::iterator -- include/dictionary.hpp:84-94: (kmer id, k-mer) pairs of an id range in id order. It decodes
@@ -656,6 +616,26 @@ private:
     }
     static void check(sshash_status s) {
         if (s != SSHASH_OK) throw std::runtime_error(sshash_last_error());
+    }
+    /* a streaming call of the C ABI, `call(report)`: checked, its report by value */
+    template <typename Call>
+    static streaming_query_report reported(Call&& call) {
+        sshash_streaming_report s;
+        check(call(&s));
+        return to_report(s);
+    }
+    /* any callable fn(first_read, rows, n) as the (function, ctx) pair of a sshash_*_fn with rows of Row: `thunk` is the function, the
+       object itself the ctx; it points at `fn`, which outlives the call */
+    template <typename Row, typename Fn>
+    struct row_callback {
+        Fn* fn;
+        static int thunk(void* ctx, uint64_t first_read, uint64_t n, const Row* rows) {
+            return int((*static_cast<row_callback*>(ctx)->fn)(first_read, rows, n));
+        }
+    };
+    template <typename Row, typename Fn>
+    static row_callback<Row, Fn> callback_of(Fn& fn) {
+        return {&fn};
     }
     void reset() {
         sshash_free(m_h);

@@ -118,6 +118,96 @@ MAX_CLASSES = 4096  # SSHASH_MAX_CLASSES
 NO_CLASS = 0xFFFFFFFF  # SSHASH_NO_CLASS: best_class of a row of zeros
 
 
+# The C ABI as ctypes sees it: name -> (restype, argtypes), one entry per function of include/sshash_amd.h (tests/test_capi.py holds
+# the names against the header). _load() binds every one of them.
+_P = C.c_void_p
+_SIGNATURES = {
+    "sshash_last_error": (C.c_char_p, []),
+    "sshash_build_info": (C.c_char_p, []),
+    "sshash_build_config_default": (None, [C.POINTER(_BuildConfig)]),
+    "sshash_build_from_fasta": (C.c_int, [C.c_char_p, C.POINTER(_BuildConfig), C.POINTER(_P)]),
+    "sshash_build_from_packed": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(_BuildConfig), C.POINTER(_P)]),
+    "sshash_save": (C.c_int, [_P, C.c_char_p]),
+    "sshash_load": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
+    "sshash_free": (None, [_P]),
+    "sshash_get_info": (C.c_int, [_P, C.POINTER(_Info)]),
+    "sshash_bucket_stats": (C.c_int, [_P, C.POINTER(C.c_uint64 * 64)]),
+    "sshash_device_count": (C.c_int, []),
+    "sshash_to_device": (C.c_int, [_P, C.c_int]),
+    "sshash_to_device_table_shard": (C.c_int, [_P, C.c_int, C.c_uint32, C.c_uint32]),
+    "sshash_device_bytes": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
+    "sshash_device_stats": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64 * 16)]),
+    "sshash_device_table_histogram": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64 * 32)]),
+    "sshash_sharded_lookup_device": (C.c_int, [_P, C.c_int, C.c_uint32, C.c_int, _P, C.c_uint64, C.c_int, _P, C.POINTER(_Exchange), _P]),
+    "sshash_sharded_lookup_rccl": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint64, C.c_int, _P, _P]),
+    "sshash_streaming_lookup_device": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, C.c_uint64, C.POINTER(_Results), _P, _P]),
+    "sshash_streaming_lookup": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(_Results), C.POINTER(_Report)]),
+    "sshash_lookup_packed_device": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.c_int, C.POINTER(_Results), _P]),
+    "sshash_lookup_ascii_device": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.c_int, C.POINTER(_Results), _P]),
+    "sshash_lookup_packed": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.POINTER(_Results)]),
+    "sshash_lookup_ascii": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.POINTER(_Results)]),
+    "sshash_neighbours_packed_device": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.c_int, C.POINTER(_Results), _P]),
+    "sshash_neighbours_packed": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.POINTER(_Results)]),
+    "sshash_string_neighbours": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.POINTER(_Results)]),
+    "sshash_string_size": (C.c_int, [_P, _P, C.c_uint64, _P]),
+    "sshash_string_offsets": (C.c_int, [_P, _P, C.c_uint64, _P, _P]),
+    "sshash_is_member_packed_device": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.c_int, _P, _P]),
+    "sshash_is_member_packed": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _P]),
+    "sshash_is_member_ascii": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _P]),
+    "sshash_weight": (C.c_int, [_P, _P, C.c_uint64, _P]),
+    "sshash_weight_device": (C.c_int, [_P, C.c_int, _P, C.c_uint64, _P, _P]),
+    "sshash_access": (C.c_int, [_P, C.c_uint64, _P]),
+    "sshash_access_packed": (C.c_int, [_P, _P, C.c_uint64, _P]),
+    "sshash_access_packed_device": (C.c_int, [_P, C.c_int, _P, C.c_uint64, _P, _P]),
+    "sshash_streaming_query_from_file": (C.c_int, [_P, C.c_char_p, C.c_int, C.POINTER(_Report)]),
+    "sshash_streaming_query": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(_Report)]),
+    "sshash_streaming_query_device": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, C.c_uint64, _P, _P]),
+    "sshash_streaming_query_per_read_device": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, C.c_uint64, _P, _P, _P]),
+    "sshash_streaming_query_per_read": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.POINTER(_Report)]),
+    "sshash_streaming_query_from_file_per_read": (C.c_int, [_P, C.c_char_p, C.c_int, _PerReadFn, _P, C.POINTER(_Report)]),
+    "sshash_streaming_runs_device": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, C.c_uint64, _P, _P, C.c_uint64, _P, _P]),
+    "sshash_streaming_runs": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, C.c_uint64, C.POINTER(_Report)]),
+    "sshash_cover_words": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "sshash_streaming_cover_device": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, C.c_uint64, _P, _P, _P]),
+    "sshash_streaming_cover": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.POINTER(_Report)]),
+    "sshash_streaming_cover_from_file": (C.c_int, [_P, C.c_char_p, C.c_int, _P, C.POINTER(_Report)]),
+    "sshash_cover_string_counts_device": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
+    "sshash_cover_string_counts": (C.c_int, [_P, _P, _P, C.POINTER(C.c_uint64)]),
+    "sshash_streaming_depth_device": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, C.c_uint64, _P, _P, _P]),
+    "sshash_depth_finish_device": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "sshash_set_read_segments": (C.c_int, [_P, C.c_uint64, C.c_int]),
+    "sshash_get_read_segments": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    "sshash_streaming_depth": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.POINTER(_Report)]),
+    "sshash_streaming_depth_from_file": (C.c_int, [_P, C.c_char_p, C.c_int, _P, C.POINTER(_Report)]),
+    "sshash_depth_string_sums_device": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
+    "sshash_depth_string_sums": (C.c_int, [_P, _P, _P, C.POINTER(C.c_uint64)]),
+    "sshash_value_prefix_device": (C.c_int, [_P, C.c_int, _P, C.c_uint32, _P, _P]),
+    "sshash_streaming_sums_device": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, C.c_uint64, _P, _P, _P, _P]),
+    "sshash_streaming_sums": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint32, _P, C.POINTER(_Report)]),
+    "sshash_streaming_sums_from_file": (C.c_int, [_P, C.c_char_p, C.c_int, _P, C.c_uint32, _PerReadFn, _P, C.POINTER(_Report)]),
+    "sshash_streaming_classes_device": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, C.c_uint64, _P, C.c_uint32, _P, _P, _P]),
+    "sshash_streaming_classes": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint32, _P, C.POINTER(_Report)]),
+    "sshash_streaming_classes_from_file": (C.c_int, [_P, C.c_char_p, C.c_int, _P, C.c_uint32, _PerReadFn, _P, C.POINTER(_Report)]),
+    "sshash_class_best_device": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.c_uint32, _P, _P]),
+    "sshash_class_best": (C.c_int, [_P, C.c_uint64, C.c_uint32, _P]),
+    "sshash_class_totals_device": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.c_uint32, _P, _P]),
+    "sshash_class_totals": (C.c_int, [_P, C.c_uint64, C.c_uint32, _P]),
+    "sshash_streaming_best_run_device": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, C.c_uint64, _P, _P, _P]),
+    "sshash_streaming_best_run": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.POINTER(_Report)]),
+    "sshash_streaming_best_run_from_file": (C.c_int, [_P, C.c_char_p, C.c_int, _PerReadFn, _P, C.POINTER(_Report)]),
+    "sshash_runs_best_device": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, _P, _P]),
+    "sshash_runs_best": (C.c_int, [_P, _P, C.c_uint64, _P]),
+    "sshash_route_packed_device": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.c_uint32, _P, _P, _P]),
+    "sshash_route_bucket_device": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.c_uint32, C.c_int, _P, _P, _P, _P]),
+    "sshash_route_bucket_by_key_device": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.c_uint32, _P, _P, _P, _P]),
+    "sshash_route_combine_device": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, _P, _P]),
+    "sshash_iterate_packed": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P]),
+    "sshash_iterate_packed_device": (C.c_int, [_P, C.c_int, C.c_uint64, C.c_uint64, _P, _P]),
+    "sshash_check_device": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64 * 8)]),
+}
+C_ABI_SYMBOLS = tuple(_SIGNATURES)
+
+
 def _preload_hip_runtime() -> None:
     """One HIP runtime per process. PyTorch-ROCm wheels bundle their own libamdhip64.so (same SONAME
     as the system one); if libsshash_amd.so pulled in /opt/rocm's copy first, a later `import torch`
@@ -153,121 +243,12 @@ def _load() -> C.CDLL:
         )
     _preload_hip_runtime()
     lib = C.CDLL(path)
-    P = C.c_void_p
-    sigs = {
-        "sshash_last_error": (C.c_char_p, []),
-        "sshash_build_info": (C.c_char_p, []),
-        "sshash_build_config_default": (None, [C.POINTER(_BuildConfig)]),
-        "sshash_build_from_fasta": (C.c_int, [C.c_char_p, C.POINTER(_BuildConfig), C.POINTER(P)]),
-        "sshash_build_from_packed": (C.c_int, [P, P, C.c_uint64, C.POINTER(_BuildConfig), C.POINTER(P)]),
-        "sshash_save": (C.c_int, [P, C.c_char_p]),
-        "sshash_load": (C.c_int, [C.c_char_p, C.POINTER(P)]),
-        "sshash_free": (None, [P]),
-        "sshash_get_info": (C.c_int, [P, C.POINTER(_Info)]),
-        "sshash_bucket_stats": (C.c_int, [P, C.POINTER(C.c_uint64 * 64)]),
-        "sshash_device_count": (C.c_int, []),
-        "sshash_to_device": (C.c_int, [P, C.c_int]),
-        "sshash_to_device_table_shard": (C.c_int, [P, C.c_int, C.c_uint32, C.c_uint32]),
-        "sshash_device_bytes": (C.c_int, [P, C.c_int, C.POINTER(C.c_uint64)]),
-        "sshash_device_stats": (C.c_int, [P, C.c_int, C.POINTER(C.c_uint64 * 16)]),
-        "sshash_device_table_histogram": (C.c_int, [P, C.c_int, C.POINTER(C.c_uint64 * 32)]),
-        "sshash_sharded_lookup_device": (C.c_int, [P, C.c_int, C.c_uint32, C.c_int, P, C.c_uint64, C.c_int, P, C.POINTER(_Exchange), P]),
-        "sshash_sharded_lookup_rccl": (C.c_int, [P, C.c_int, P, C.c_int, P, C.c_uint64, C.c_int, P, P]),
-        "sshash_streaming_lookup_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, C.POINTER(_Results), P, P]),
-        "sshash_streaming_lookup": (C.c_int, [P, P, P, C.c_uint64, C.POINTER(_Results), C.POINTER(_Report)]),
-        "sshash_lookup_packed_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_int, C.POINTER(_Results), P]),
-        "sshash_lookup_ascii_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_int, C.POINTER(_Results), P]),
-        "sshash_lookup_packed": (C.c_int, [P, P, C.c_uint64, C.c_int, C.POINTER(_Results)]),
-        "sshash_lookup_ascii": (C.c_int, [P, P, C.c_uint64, C.c_int, C.POINTER(_Results)]),
-        "sshash_neighbours_packed_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_int, C.POINTER(_Results), P]),
-        "sshash_neighbours_packed": (C.c_int, [P, P, C.c_uint64, C.c_int, C.POINTER(_Results)]),
-        "sshash_string_neighbours": (C.c_int, [P, P, C.c_uint64, C.c_int, C.POINTER(_Results)]),
-        "sshash_string_size": (C.c_int, [P, P, C.c_uint64, P]),
-        "sshash_string_offsets": (C.c_int, [P, P, C.c_uint64, P, P]),
-        "sshash_is_member_packed_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_int, P, P]),
-        "sshash_is_member_packed": (C.c_int, [P, P, C.c_uint64, C.c_int, P]),
-        "sshash_is_member_ascii": (C.c_int, [P, P, C.c_uint64, C.c_int, P]),
-        "sshash_weight": (C.c_int, [P, P, C.c_uint64, P]),
-        "sshash_weight_device": (C.c_int, [P, C.c_int, P, C.c_uint64, P, P]),
-        "sshash_access": (C.c_int, [P, C.c_uint64, P]),
-        "sshash_access_packed": (C.c_int, [P, P, C.c_uint64, P]),
-        "sshash_access_packed_device": (C.c_int, [P, C.c_int, P, C.c_uint64, P, P]),
-        "sshash_streaming_query_from_file": (C.c_int, [P, C.c_char_p, C.c_int, C.POINTER(_Report)]),
-        "sshash_streaming_query": (C.c_int, [P, P, P, C.c_uint64, C.POINTER(_Report)]),
-        "sshash_streaming_query_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, P]),
-        "sshash_streaming_query_per_read_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, P, P]),
-        "sshash_streaming_query_per_read": (C.c_int, [P, P, P, C.c_uint64, P, C.POINTER(_Report)]),
-        "sshash_streaming_query_from_file_per_read": (C.c_int, [P, C.c_char_p, C.c_int, _PerReadFn, P, C.POINTER(_Report)]),
-        "sshash_streaming_runs_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, P, C.c_uint64, P, P]),
-        "sshash_streaming_runs": (C.c_int, [P, P, P, C.c_uint64, P, P, C.c_uint64, C.POINTER(_Report)]),
-        "sshash_cover_words": (C.c_int, [P, C.POINTER(C.c_uint64)]),
-        "sshash_streaming_cover_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, P, P]),
-        "sshash_streaming_cover": (C.c_int, [P, P, P, C.c_uint64, P, C.POINTER(_Report)]),
-        "sshash_streaming_cover_from_file": (C.c_int, [P, C.c_char_p, C.c_int, P, C.POINTER(_Report)]),
-        "sshash_cover_string_counts_device": (C.c_int, [P, C.c_int, P, P, P, P]),
-        "sshash_cover_string_counts": (C.c_int, [P, P, P, C.POINTER(C.c_uint64)]),
-        "sshash_streaming_depth_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, P, P]),
-        "sshash_depth_finish_device": (C.c_int, [P, C.c_int, P, P, P]),
-        "sshash_set_read_segments": (C.c_int, [P, C.c_uint64, C.c_int]),
-        "sshash_get_read_segments": (C.c_int, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
-        "sshash_streaming_depth": (C.c_int, [P, P, P, C.c_uint64, P, C.POINTER(_Report)]),
-        "sshash_streaming_depth_from_file": (C.c_int, [P, C.c_char_p, C.c_int, P, C.POINTER(_Report)]),
-        "sshash_depth_string_sums_device": (C.c_int, [P, C.c_int, P, P, P, P]),
-        "sshash_depth_string_sums": (C.c_int, [P, P, P, C.POINTER(C.c_uint64)]),
-        "sshash_value_prefix_device": (C.c_int, [P, C.c_int, P, C.c_uint32, P, P]),
-        "sshash_streaming_sums_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, P, P, P]),
-        "sshash_streaming_sums": (C.c_int, [P, P, P, C.c_uint64, P, C.c_uint32, P, C.POINTER(_Report)]),
-        "sshash_streaming_sums_from_file": (C.c_int, [P, C.c_char_p, C.c_int, P, C.c_uint32, _PerReadFn, P, C.POINTER(_Report)]),
-        "sshash_streaming_classes_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, C.c_uint32, P, P, P]),
-        "sshash_streaming_classes": (C.c_int, [P, P, P, C.c_uint64, P, C.c_uint32, P, C.POINTER(_Report)]),
-        "sshash_streaming_classes_from_file": (C.c_int, [P, C.c_char_p, C.c_int, P, C.c_uint32, _PerReadFn, P, C.POINTER(_Report)]),
-        "sshash_class_best_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P]),
-        "sshash_class_best": (C.c_int, [P, C.c_uint64, C.c_uint32, P]),
-        "sshash_class_totals_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P]),
-        "sshash_class_totals": (C.c_int, [P, C.c_uint64, C.c_uint32, P]),
-        "sshash_streaming_best_run_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, C.c_uint64, P, P, P]),
-        "sshash_streaming_best_run": (C.c_int, [P, P, P, C.c_uint64, P, C.POINTER(_Report)]),
-        "sshash_streaming_best_run_from_file": (C.c_int, [P, C.c_char_p, C.c_int, _PerReadFn, P, C.POINTER(_Report)]),
-        "sshash_runs_best_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, P, P]),
-        "sshash_runs_best": (C.c_int, [P, P, C.c_uint64, P]),
-        "sshash_route_packed_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P, P]),
-        "sshash_route_bucket_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, C.c_int, P, P, P, P]),
-        "sshash_route_bucket_by_key_device": (C.c_int, [P, C.c_int, P, C.c_uint64, C.c_uint32, P, P, P, P]),
-        "sshash_route_combine_device": (C.c_int, [P, C.c_int, P, P, C.c_uint64, P, P]),
-        "sshash_iterate_packed": (C.c_int, [P, C.c_uint64, C.c_uint64, P]),
-        "sshash_iterate_packed_device": (C.c_int, [P, C.c_int, C.c_uint64, C.c_uint64, P, P]),
-        "sshash_check_device": (C.c_int, [P, C.c_int, C.POINTER(C.c_uint64 * 8)]),
-    }
-    for name, (res, args) in sigs.items():
+    for name, (res, args) in _SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError here == ABI symbol missing: fail loudly
         fn.restype = res
         fn.argtypes = args
     _lib = lib
     return lib
-
-
-C_ABI_SYMBOLS = (
-    "sshash_last_error sshash_build_info sshash_build_config_default sshash_build_from_fasta sshash_build_from_packed sshash_save "
-    "sshash_load sshash_free sshash_get_info sshash_bucket_stats sshash_device_count sshash_to_device sshash_to_device_table_shard sshash_device_bytes sshash_device_stats sshash_device_table_histogram "
-    "sshash_lookup_packed_device sshash_lookup_ascii_device sshash_lookup_packed sshash_lookup_ascii "
-    "sshash_neighbours_packed_device sshash_neighbours_packed sshash_string_neighbours sshash_string_size sshash_string_offsets "
-    "sshash_is_member_packed_device sshash_is_member_packed sshash_is_member_ascii sshash_access sshash_access_packed "
-    "sshash_access_packed_device sshash_weight sshash_weight_device "
-    "sshash_streaming_query_from_file sshash_streaming_query sshash_streaming_query_device "
-    "sshash_streaming_query_per_read sshash_streaming_query_per_read_device sshash_streaming_query_from_file_per_read "
-    "sshash_streaming_runs sshash_streaming_runs_device "
-    "sshash_cover_words sshash_streaming_cover sshash_streaming_cover_device sshash_streaming_cover_from_file "
-    "sshash_cover_string_counts sshash_cover_string_counts_device "
-    "sshash_streaming_depth sshash_streaming_depth_device sshash_depth_finish_device sshash_streaming_depth_from_file "
-    "sshash_depth_string_sums sshash_depth_string_sums_device sshash_set_read_segments sshash_get_read_segments "
-    "sshash_value_prefix_device sshash_streaming_sums sshash_streaming_sums_device sshash_streaming_sums_from_file "
-    "sshash_streaming_classes sshash_streaming_classes_device sshash_streaming_classes_from_file "
-    "sshash_class_best sshash_class_best_device sshash_class_totals sshash_class_totals_device "
-    "sshash_streaming_best_run sshash_streaming_best_run_device sshash_streaming_best_run_from_file sshash_runs_best sshash_runs_best_device "
-    "sshash_streaming_lookup sshash_streaming_lookup_device sshash_sharded_lookup_device sshash_sharded_lookup_rccl "
-    "sshash_route_packed_device sshash_route_bucket_device sshash_route_bucket_by_key_device sshash_route_combine_device "
-    "sshash_iterate_packed sshash_iterate_packed_device sshash_check_device"
-).split()
 
 
 def _check(status: int) -> None:
@@ -322,6 +303,42 @@ def encode_kmers(kmers: Sequence[Union[str, bytes]], k: int) -> np.ndarray:
 
 
 KmerBatch = Union[np.ndarray, Sequence[str], Sequence[bytes], str, bytes]
+
+
+def _reads_arrays(reads: Sequence[Union[str, bytes]]):
+    """Reads in memory as the streaming calls want them -> (bases, offsets, n): the reads back to back as uint8 (one spare byte when
+    there is none), the n + 1 uint64 offsets of their first bases, and their number."""
+    chunks = [s.encode("ascii", "replace") if isinstance(s, str) else bytes(s) for s in reads]
+    offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
+    if chunks:
+        offsets[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
+    return np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8), offsets, len(chunks)
+
+
+def _owned(pointer, ctype, shape) -> np.ndarray:
+    """A copy of the C array at `pointer` (the library's rows live only as long as the callback that receives them)."""
+    return np.ctypeslib.as_array(C.cast(pointer, C.POINTER(ctype)), shape=shape).copy()
+
+
+def _u32_per_id(array, n: int, noun: str, per: str) -> np.ndarray:
+    """`array` as n contiguous uint32, one per k-mer id or string id; refused where a cast would change a value."""
+    array = np.asarray(array)
+    if array.ndim != 1 or array.size != n or array.dtype.kind not in "ui":
+        raise ValueError(f"{noun}: {n} unsigned integers, one per {per}")
+    if array.dtype != np.uint32:
+        if array.size and (int(array.min()) < 0 or int(array.max()) >> 32):
+            raise ValueError(f"{noun}: every one of them within 32 bits")
+        array = array.astype(np.uint32)
+    return np.ascontiguousarray(array)
+
+
+def _accumulator(array, n: int, dtype, noun: str, size: str) -> np.ndarray:
+    """The caller's array that a call ORs or adds into (None: a zeroed one): n contiguous words of `dtype`, used in place."""
+    if array is None:
+        return np.zeros(n, dtype=dtype)
+    if not (isinstance(array, np.ndarray) and array.dtype == dtype and array.ndim == 1 and array.size == n and array.flags.c_contiguous):
+        raise ValueError(f"{noun}: a contiguous {np.dtype(dtype).name} array of {size} = {n} words")
+    return array
 
 
 class Dictionary:
@@ -708,52 +725,58 @@ class Dictionary:
         uint64 array (the columns of StreamingQueryReport), row i for record first_read + i of the file -- every record has a row,
         those shorter than k included. A return value other than None / 0 stops the query (SSHashError, status 1); an exception
         raised by the callable stops it too and is raised again here."""
-        r = _Report()
-        if per_read is None:
+        if per_read is None:  # (the C ABI's own total: the only file call with the parallel FASTQ reader)
+            r = _Report()
             _check(_load().sshash_streaming_query_from_file(self._h, os.fsencode(filename), 1 if multiline else 0, C.byref(r)))
             return self._report(r)
-        raised = []
+        return self._rows_from_file(
+            lambda fn, r: _load().sshash_streaming_query_from_file_per_read(self._h, os.fsencode(filename), 1 if multiline else 0, fn, None, r),
+            lambda rows, n: _owned(rows, C.c_uint64, (n, 6)), per_read, None)
+
+    def _rows_from_file(self, call, block_of, per_read, empty):
+        """The file calls that return a row per record. `call(fn, report)` is the bound C call with everything but the callback and the
+        report filled in; `block_of(pointer, n)` makes the owned numpy block of one batch's rows. per_read(first_read, block) gets one
+        batch after the other -> StreamingQueryReport; per_read=None: the blocks are kept -> (all of them, or `empty`;
+        StreamingQueryReport). An exception of the callable is parked while the C frames return and raised again here."""
+        r = _Report()
+        raised, kept = [], []
 
         def hand_over(_ctx, first_read, n, rows):
             try:
-                block = np.ctypeslib.as_array(C.cast(rows, C.POINTER(C.c_uint64)), shape=(int(n), 6)).copy()
+                block = block_of(rows, int(n))
+                if per_read is None:
+                    kept.append(block)
+                    return 0
                 stop = per_read(int(first_read), block)
                 return int(stop) if stop else 0
             except BaseException as e:  # (must not travel through the C frames)
                 raised.append(e)
                 return -1
 
-        fn = _PerReadFn(hand_over)
-        status = _load().sshash_streaming_query_from_file_per_read(self._h, os.fsencode(filename), 1 if multiline else 0, fn, None, C.byref(r))
+        status = call(_PerReadFn(hand_over), C.byref(r))
         if raised:
             raise raised[0]
         _check(status)
+        if per_read is None:
+            return (np.concatenate(kept) if kept else empty), self._report(r)
         return self._report(r)
 
     def streaming_query(self, reads: Sequence[Union[str, bytes]]) -> StreamingQueryReport:
         """One streaming_query per read (reset between reads), reads given in memory."""
-        chunks = [s.encode("ascii", "replace") if isinstance(s, str) else bytes(s) for s in reads]
-        offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
-        if chunks:
-            offsets[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
-        bases = np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8)
+        bases, offsets, n = _reads_arrays(reads)
         r = _Report()
-        _check(_load().sshash_streaming_query(self._h, bases.ctypes.data, offsets.ctypes.data, len(chunks), C.byref(r)))
+        _check(_load().sshash_streaming_query(self._h, bases.ctypes.data, offsets.ctypes.data, n, C.byref(r)))
         return self._report(r)
 
     def streaming_query_per_read(self, reads: Sequence[Union[str, bytes]]):
         """The streaming query's report for every read on its own -> (rows, StreamingQueryReport): rows is an (n, 6) uint64 array,
         row r = (num_kmers, num_positive_kmers, num_negative_kmers, num_invalid_kmers, num_searches, num_extensions) of read r (six
         zeros for a read shorter than k); the report is the batch's, the column sums of the rows."""
-        chunks = [s.encode("ascii", "replace") if isinstance(s, str) else bytes(s) for s in reads]
-        offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
-        if chunks:
-            offsets[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
-        bases = np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8)
-        rows = np.zeros((len(chunks), 6), dtype=np.uint64)
+        bases, offsets, n = _reads_arrays(reads)
+        rows = np.zeros((n, 6), dtype=np.uint64)
         r = _Report()
-        _check(_load().sshash_streaming_query_per_read(self._h, bases.ctypes.data, offsets.ctypes.data, len(chunks),
-                                                       rows.ctypes.data if len(chunks) else None, C.byref(r)))
+        _check(_load().sshash_streaming_query_per_read(self._h, bases.ctypes.data, offsets.ctypes.data, n,
+                                                       rows.ctypes.data if n else None, C.byref(r)))
         return rows, self._report(r)
 
     def streaming_query_per_read_device(self, device: int, d_bases: int, d_read_offsets: int, num_reads: int, d_rows: int,
@@ -769,17 +792,13 @@ class Dictionary:
         the extensions behind it; sshash_streaming_runs in include/sshash_amd.h). run_offsets: len(reads) + 1 uint64, CSR; runs: a
         RUN_DTYPE array, the records of read r at runs[run_offsets[r]:run_offsets[r + 1]] in increasing read_pos. expand_runs() gives
         the per-k-mer results back."""
-        chunks = [s.encode("ascii", "replace") if isinstance(s, str) else bytes(s) for s in reads]
-        offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
-        if chunks:
-            offsets[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
-        bases = np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8)
-        run_offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
-        capacity = 2 * len(chunks) + 64  # a first guess; run_offsets says whether it was enough
+        bases, offsets, n = _reads_arrays(reads)
+        run_offsets = np.zeros(n + 1, dtype=np.uint64)
+        capacity = 2 * n + 64  # a first guess; run_offsets says whether it was enough
         while True:
             runs = np.zeros(capacity, dtype=RUN_DTYPE)
             r = _Report()
-            _check(_load().sshash_streaming_runs(self._h, bases.ctypes.data, offsets.ctypes.data, len(chunks), run_offsets.ctypes.data,
+            _check(_load().sshash_streaming_runs(self._h, bases.ctypes.data, offsets.ctypes.data, n, run_offsets.ctypes.data,
                                                  runs.ctypes.data, capacity, C.byref(r)))
             total = int(run_offsets[-1])
             if total <= capacity:
@@ -803,25 +822,16 @@ class Dictionary:
         return int(words.value)
 
     def _cover_array(self, cover) -> np.ndarray:
-        words = self.cover_words()
-        if cover is None:
-            return np.zeros(words, dtype=np.uint64)
-        if not (isinstance(cover, np.ndarray) and cover.dtype == np.uint64 and cover.ndim == 1 and cover.size == words and cover.flags.c_contiguous):
-            raise ValueError(f"cover: a contiguous uint64 array of cover_words() = {words} words")
-        return cover
+        return _accumulator(cover, self.cover_words(), np.uint64, "cover", "cover_words()")
 
     def streaming_cover(self, reads: Sequence[Union[str, bytes]], cover: Optional[np.ndarray] = None):
         """WHICH k-mers of the dictionary the reads hold -> (cover, StreamingQueryReport): the ids of all positive k-mers of the reads
         (the kmer_id values streaming_lookup returns, INVALID_U64 aside) as a bitmap of cover_words() uint64; `cover` (None: a zeroed one)
         is ORed into, in place, and returned. cover_to_ids() lists the ids."""
-        chunks = [s.encode("ascii", "replace") if isinstance(s, str) else bytes(s) for s in reads]
-        offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
-        if chunks:
-            offsets[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
-        bases = np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8)
+        bases, offsets, n = _reads_arrays(reads)
         cover = self._cover_array(cover)
         r = _Report()
-        _check(_load().sshash_streaming_cover(self._h, bases.ctypes.data, offsets.ctypes.data, len(chunks), cover.ctypes.data, C.byref(r)))
+        _check(_load().sshash_streaming_cover(self._h, bases.ctypes.data, offsets.ctypes.data, n, cover.ctypes.data, C.byref(r)))
         return cover, self._report(r)
 
     def streaming_cover_device(self, device: int, d_bases: int, d_read_offsets: int, num_reads: int, d_cover: int, d_report: int = 0,
@@ -853,25 +863,16 @@ class Dictionary:
 
     # ---- streaming depth: how often a read set holds each k-mer of the dictionary ---------------------
     def _depth_array(self, depth) -> np.ndarray:
-        n = self.num_kmers()
-        if depth is None:
-            return np.zeros(n, dtype=np.uint32)
-        if not (isinstance(depth, np.ndarray) and depth.dtype == np.uint32 and depth.ndim == 1 and depth.size == n and depth.flags.c_contiguous):
-            raise ValueError(f"depth: a contiguous uint32 array of num_kmers() = {n} words")
-        return depth
+        return _accumulator(depth, self.num_kmers(), np.uint32, "depth", "num_kmers()")
 
     def streaming_depth(self, reads: Sequence[Union[str, bytes]], depth: Optional[np.ndarray] = None):
         """HOW OFTEN the reads hold each k-mer of the dictionary -> (depth, StreamingQueryReport): depth[i] grows by the number of places
         where streaming_lookup over the same reads returns kmer_id == i (either strand, every occurrence; modulo 2^32, nothing
         saturates). `depth` (None: a zeroed one), num_kmers() uint32, is added into, in place, and returned."""
-        chunks = [s.encode("ascii", "replace") if isinstance(s, str) else bytes(s) for s in reads]
-        offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
-        if chunks:
-            offsets[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
-        bases = np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8)
+        bases, offsets, n = _reads_arrays(reads)
         depth = self._depth_array(depth)
         r = _Report()
-        _check(_load().sshash_streaming_depth(self._h, bases.ctypes.data, offsets.ctypes.data, len(chunks), depth.ctypes.data, C.byref(r)))
+        _check(_load().sshash_streaming_depth(self._h, bases.ctypes.data, offsets.ctypes.data, n, depth.ctypes.data, C.byref(r)))
         return depth, self._report(r)
 
     def streaming_depth_device(self, device: int, d_bases: int, d_read_offsets: int, num_reads: int, d_deltas: int, d_report: int = 0,
@@ -937,14 +938,7 @@ class Dictionary:
                     raise ValueError("a weight does not fit 32 bits")
                 out[at:at + w.size] = w
             return out
-        values = np.asarray(values)
-        if values.ndim != 1 or values.size != n or values.dtype.kind not in "ui":
-            raise ValueError(f"values: {n} unsigned integers, one per k-mer id")
-        if values.dtype != np.uint32:
-            if values.size and (int(values.min()) < 0 or int(values.max()) >> 32):
-                raise ValueError("values: every one of them within 32 bits")
-            values = values.astype(np.uint32)
-        return np.ascontiguousarray(values)
+        return _u32_per_id(values, n, "values", "k-mer id")
 
     def value_prefix_device(self, device: int, d_values: int, d_prefix: int, at_least: int = 0, stream: int = 0) -> None:
         """Device buffers: d_prefix (num_kmers() + 1 uint64, overwritten) becomes the exclusive prefix sums of d_values (num_kmers()
@@ -964,16 +958,12 @@ class Dictionary:
         occurrence; modulo 2^64) -- at_least >= 1: the number of those with values[id] >= at_least --, `positive_kmers` = the number of
         those places. `values`: num_kmers() integers within 32 bits (a depth array, say); None: the weights of a weighted dictionary."""
         values = self._values_array(values)
-        chunks = [s.encode("ascii", "replace") if isinstance(s, str) else bytes(s) for s in reads]
-        offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
-        if chunks:
-            offsets[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
-        bases = np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8)
-        sums = np.zeros(len(chunks), dtype=READ_SUM_DTYPE)
+        bases, offsets, n = _reads_arrays(reads)
+        sums = np.zeros(n, dtype=READ_SUM_DTYPE)
         r = _Report()
-        _check(_load().sshash_streaming_sums(self._h, bases.ctypes.data, offsets.ctypes.data, len(chunks),
+        _check(_load().sshash_streaming_sums(self._h, bases.ctypes.data, offsets.ctypes.data, n,
                                              values.ctypes.data if values.size else bases.ctypes.data, int(at_least),
-                                             sums.ctypes.data if len(chunks) else None, C.byref(r)))
+                                             sums.ctypes.data if n else None, C.byref(r)))
         return sums, self._report(r)
 
     def streaming_sums_from_file(self, filename: str, values=None, at_least: int = 0, multiline: bool = False,
@@ -983,47 +973,18 @@ class Dictionary:
         than None / 0 stops the query (SSHashError), an exception raised by the callable stops it too and is raised again here.
         per_read=None: -> (sums of the whole file, StreamingQueryReport); otherwise -> StreamingQueryReport."""
         values = self._values_array(values)
-        r = _Report()
-        raised, kept = [], []
-
-        def hand_over(_ctx, first_read, n, rows):
-            try:
-                words = np.ctypeslib.as_array(C.cast(rows, C.POINTER(C.c_uint64)), shape=(int(n), 2)).copy()
-                block = words.view(READ_SUM_DTYPE).reshape(int(n))
-                if per_read is None:
-                    kept.append(block)
-                    return 0
-                stop = per_read(int(first_read), block)
-                return int(stop) if stop else 0
-            except BaseException as e:  # (must not travel through the C frames)
-                raised.append(e)
-                return -1
-
-        fn = _PerReadFn(hand_over)
         spare = np.zeros(1, dtype=np.uint32)
-        status = _load().sshash_streaming_sums_from_file(self._h, os.fsencode(filename), 1 if multiline else 0,
-                                                         values.ctypes.data if values.size else spare.ctypes.data, int(at_least), fn, None, C.byref(r))
-        if raised:
-            raise raised[0]
-        _check(status)
-        if per_read is None:
-            return (np.concatenate(kept) if kept else np.zeros(0, dtype=READ_SUM_DTYPE)), self._report(r)
-        return self._report(r)
+        return self._rows_from_file(
+            lambda fn, r: _load().sshash_streaming_sums_from_file(self._h, os.fsencode(filename), 1 if multiline else 0,
+                                                                  values.ctypes.data if values.size else spare.ctypes.data, int(at_least), fn, None, r),
+            lambda rows, n: _owned(rows, C.c_uint64, (n, 2)).view(READ_SUM_DTYPE).reshape(n), per_read, np.zeros(0, dtype=READ_SUM_DTYPE))
 
     # ---- streaming classes: a read's positive k-mers by class of string --------------------------------
     def _labels_array(self, labels, num_classes: int) -> np.ndarray:
         """`labels` as the calls want it: num_strings() uint32, contiguous."""
-        n = self.num_strings()
         if not 1 <= int(num_classes) <= MAX_CLASSES:
             raise ValueError(f"num_classes: 1 .. {MAX_CLASSES}")
-        labels = np.asarray(labels)
-        if labels.ndim != 1 or labels.size != n or labels.dtype.kind not in "ui":
-            raise ValueError(f"labels: {n} unsigned integers, one per string id")
-        if labels.dtype != np.uint32:
-            if labels.size and (int(labels.min()) < 0 or int(labels.max()) >> 32):
-                raise ValueError("labels: every one of them within 32 bits")
-            labels = labels.astype(np.uint32)
-        return np.ascontiguousarray(labels)
+        return _u32_per_id(labels, self.num_strings(), "labels", "string id")
 
     def streaming_classes_device(self, device: int, d_bases: int, d_read_offsets: int, num_reads: int, d_labels: int, num_classes: int,
                                  d_rows: int, d_report: int = 0, stream: int = 0, total_bases: int = 0) -> None:
@@ -1038,16 +999,12 @@ class Dictionary:
         places of read r where streaming_lookup returns a k-mer whose string s has labels[s] == c (either strand, every occurrence;
         modulo 2^32). `labels`: num_strings() integers within 32 bits; a label >= num_classes is no class and counted in no column."""
         labels = self._labels_array(labels, num_classes)
-        chunks = [s.encode("ascii", "replace") if isinstance(s, str) else bytes(s) for s in reads]
-        offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
-        if chunks:
-            offsets[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
-        bases = np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8)
-        rows = np.zeros((len(chunks), int(num_classes)), dtype=np.uint32)
+        bases, offsets, n = _reads_arrays(reads)
+        rows = np.zeros((n, int(num_classes)), dtype=np.uint32)
         r = _Report()
-        _check(_load().sshash_streaming_classes(self._h, bases.ctypes.data, offsets.ctypes.data, len(chunks),
+        _check(_load().sshash_streaming_classes(self._h, bases.ctypes.data, offsets.ctypes.data, n,
                                                 labels.ctypes.data if labels.size else bases.ctypes.data, int(num_classes),
-                                                rows.ctypes.data if len(chunks) else None, C.byref(r)))
+                                                rows.ctypes.data if n else None, C.byref(r)))
         return rows, self._report(r)
 
     def streaming_classes_from_file(self, filename: str, labels, num_classes: int, multiline: bool = False,
@@ -1057,32 +1014,11 @@ class Dictionary:
         return value other than None / 0 stops the query (SSHashError), an exception raised by the callable stops it too and is raised
         again here. per_read=None: -> (rows of the whole file, StreamingQueryReport); otherwise -> StreamingQueryReport."""
         labels = self._labels_array(labels, num_classes)
-        r = _Report()
-        raised, kept = [], []
-
-        def hand_over(_ctx, first_read, n, rows):
-            try:
-                block = np.ctypeslib.as_array(C.cast(rows, C.POINTER(C.c_uint32)), shape=(int(n), int(num_classes))).copy()
-                if per_read is None:
-                    kept.append(block)
-                    return 0
-                stop = per_read(int(first_read), block)
-                return int(stop) if stop else 0
-            except BaseException as e:  # (must not travel through the C frames)
-                raised.append(e)
-                return -1
-
-        fn = _PerReadFn(hand_over)
         spare = np.zeros(1, dtype=np.uint32)
-        status = _load().sshash_streaming_classes_from_file(self._h, os.fsencode(filename), 1 if multiline else 0,
-                                                            labels.ctypes.data if labels.size else spare.ctypes.data, int(num_classes), fn, None,
-                                                            C.byref(r))
-        if raised:
-            raise raised[0]
-        _check(status)
-        if per_read is None:
-            return (np.concatenate(kept) if kept else np.zeros((0, int(num_classes)), dtype=np.uint32)), self._report(r)
-        return self._report(r)
+        return self._rows_from_file(
+            lambda fn, r: _load().sshash_streaming_classes_from_file(self._h, os.fsencode(filename), 1 if multiline else 0,
+                                                                     labels.ctypes.data if labels.size else spare.ctypes.data, int(num_classes), fn, None, r),
+            lambda rows, n: _owned(rows, C.c_uint32, (n, int(num_classes))), per_read, np.zeros((0, int(num_classes)), dtype=np.uint32))
 
     def class_best_device(self, device: int, d_rows: int, num_reads: int, num_classes: int, d_best: int, stream: int = 0) -> None:
         """Device buffers: d_best receives num_reads rows of READ_CLASS_DTYPE (overwritten) out of d_rows (num_reads x num_classes uint32)."""
@@ -1106,15 +1042,11 @@ class Dictionary:
         """The one place per read -> (best, StreamingQueryReport): best is a RUN_DTYPE array, best[r] the longest run of read r (the
         record of streaming_runs with the largest num_kmers & 0x7FFFFFFF, among equals the first in read order); a read without a hit
         has a record of zeros, num_kmers == 0."""
-        chunks = [s.encode("ascii", "replace") if isinstance(s, str) else bytes(s) for s in reads]
-        offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
-        if chunks:
-            offsets[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
-        bases = np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8)
-        best = np.zeros(len(chunks), dtype=RUN_DTYPE)
+        bases, offsets, n = _reads_arrays(reads)
+        best = np.zeros(n, dtype=RUN_DTYPE)
         r = _Report()
-        _check(_load().sshash_streaming_best_run(self._h, bases.ctypes.data, offsets.ctypes.data, len(chunks),
-                                                 best.ctypes.data if len(chunks) else None, C.byref(r)))
+        _check(_load().sshash_streaming_best_run(self._h, bases.ctypes.data, offsets.ctypes.data, n,
+                                                 best.ctypes.data if n else None, C.byref(r)))
         return best, self._report(r)
 
     def streaming_best_run_from_file(self, filename: str, multiline: bool = False,
@@ -1123,29 +1055,9 @@ class Dictionary:
         in file order, best a RUN_DTYPE array with record i for record first_read + i of the file (every record has one); a return
         value other than None / 0 stops the query (SSHashError), an exception raised by the callable stops it too and is raised again
         here. per_read=None: -> (the records of the whole file, StreamingQueryReport); otherwise -> StreamingQueryReport."""
-        r = _Report()
-        raised, kept = [], []
-
-        def hand_over(_ctx, first_read, n, best):
-            try:
-                block = np.ctypeslib.as_array(C.cast(best, C.POINTER(C.c_uint8)), shape=(int(n) * RUN_DTYPE.itemsize,)).copy().view(RUN_DTYPE)
-                if per_read is None:
-                    kept.append(block)
-                    return 0
-                stop = per_read(int(first_read), block)
-                return int(stop) if stop else 0
-            except BaseException as e:  # (must not travel through the C frames)
-                raised.append(e)
-                return -1
-
-        fn = _PerReadFn(hand_over)
-        status = _load().sshash_streaming_best_run_from_file(self._h, os.fsencode(filename), 1 if multiline else 0, fn, None, C.byref(r))
-        if raised:
-            raise raised[0]
-        _check(status)
-        if per_read is None:
-            return (np.concatenate(kept) if kept else np.zeros(0, dtype=RUN_DTYPE)), self._report(r)
-        return self._report(r)
+        return self._rows_from_file(
+            lambda fn, r: _load().sshash_streaming_best_run_from_file(self._h, os.fsencode(filename), 1 if multiline else 0, fn, None, r),
+            lambda best, n: _owned(best, C.c_uint8, (n * RUN_DTYPE.itemsize,)).view(RUN_DTYPE), per_read, np.zeros(0, dtype=RUN_DTYPE))
 
     def runs_best_device(self, device: int, d_run_offsets: int, d_runs: int, num_reads: int, d_best: int, stream: int = 0) -> None:
         """Device buffers: d_best receives num_reads records of RUN_DTYPE (overwritten), the longest of every read's records of a complete
@@ -1156,11 +1068,7 @@ class Dictionary:
     def streaming_lookup(self, reads: Sequence[Union[str, bytes]], full: bool = False):
         """streaming_query::lookup for every k-mer of every read (reference include/streaming_query.hpp:56-109), batched.
         -> (list of LookupResult, one per read, len(read) - k + 1 entries each; StreamingQueryReport)."""
-        chunks = [s.encode("ascii", "replace") if isinstance(s, str) else bytes(s) for s in reads]
-        offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
-        if chunks:
-            offsets[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
-        bases = np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8)
+        bases, offsets, n = _reads_arrays(reads)
         total = max(int(offsets[-1]), 1)
         arrays = {"kmer_id": np.full(total, INVALID_U64, dtype=np.uint64)}
         if full:
@@ -1171,13 +1079,13 @@ class Dictionary:
         for name, a in arrays.items():
             setattr(r, name, a.ctypes.data)
         rep = _Report()
-        _check(_load().sshash_streaming_lookup(self._h, bases.ctypes.data, offsets.ctypes.data, len(chunks), C.byref(r), C.byref(rep)))
+        _check(_load().sshash_streaming_lookup(self._h, bases.ctypes.data, offsets.ctypes.data, n, C.byref(r), C.byref(rep)))
         per_read = []
         k = self.k()
-        for i, c in enumerate(chunks):
+        for i in range(n):
             lo = int(offsets[i])
-            n = max(0, len(c) - k + 1)
-            per_read.append(LookupResult(**{name: a[lo:lo + n] for name, a in arrays.items()}))
+            kmers = max(0, int(offsets[i + 1]) - lo - k + 1)
+            per_read.append(LookupResult(**{name: a[lo:lo + kmers] for name, a in arrays.items()}))
         return per_read, self._report(rep)
 
     def streaming_lookup_device(self, device: int, d_bases: int, d_read_offsets: int, num_reads: int, total_bases: int,

@@ -91,13 +91,35 @@ bool wants_full(sshash_results const* r) {  // any array besides kmer_id
     return any;
 }
 
-void fill_report(sshash_streaming_report* report, streaming_report const& r) {
-    report->num_kmers = r.num_kmers;
-    report->num_positive_kmers = r.num_positive_kmers;
-    report->num_negative_kmers = r.num_negative_kmers;
-    report->num_invalid_kmers = r.num_invalid_kmers;
-    report->num_searches = r.num_searches;
-    report->num_extensions = r.num_extensions;
+/* The optional report of a streaming call: zeroed when the call's arguments have passed (before anything can throw), filled with the
+   counters so far by every fill() after that. */
+struct report_out {
+    sshash_streaming_report* const report;
+    explicit report_out(sshash_streaming_report* r) : report(r) {
+        if (report) std::memset(report, 0, sizeof(*report));
+    }
+    void fill(streaming_report const& r) const {
+        if (!report) return;
+        report->num_kmers = r.num_kmers;
+        report->num_positive_kmers = r.num_positive_kmers;
+        report->num_negative_kmers = r.num_negative_kmers;
+        report->num_invalid_kmers = r.num_invalid_kmers;
+        report->num_searches = r.num_searches;
+        report->num_extensions = r.num_extensions;
+    }
+};
+
+/* The query file of a file call, opened (it throws when it cannot be) and handed to `use(read_stream&)` -- every_record: the calls with a
+   row per record want the reads shorter than k as well, row i is record i. An extension that is no supported format: the message of
+   src/query.cpp:169-171 on stderr and `use` is not called; the call then returns with its zeroed report. */
+template <typename Use>
+void with_query_file(sshash_dict const* d, const char* filename, int multiline, bool every_record, Use&& use) {
+    read_stream in(filename, multiline != 0, d->idx->k, every_record);
+    if (!in.supported()) {
+        fprintf(stderr, "unsupported query file format\n");
+        return;
+    }
+    use(in);
 }
 
 /* The sequential reader of a query file, a batch ahead of whoever uses the batches: `per_batch(read_batch const&)` is called for one
@@ -172,6 +194,39 @@ void for_each_batch(read_stream& in, Fn&& per_batch) {
         fprintf(stderr, "[sshash_amd] file query: %llu batches; waiting for the reader %.3f s, devices at work %.3f s\n",
                 (unsigned long long)batches, waited, worked);
     if (reader_error) std::rethrow_exception(reader_error);
+}
+
+/* The file calls with a row per record: one batch of the file after the other through `per_batch(batch, rows)` -- the engine call, which
+   fills `row_words` Rows per read and returns the batch's report -- and on to the caller's `fn`, in file order. The report is filled after
+   every batch, before `fn` is called: a callback that stops the call leaves the totals so far. */
+template <typename Row, typename Fn, typename PerBatch>
+void rows_from_file(read_stream& in, uint64_t row_words, Fn fn, void* ctx, report_out const& rep, PerBatch&& per_batch) {
+    streaming_report total;
+    uint64_t first_read = 0;
+    std::vector<Row> rows;
+    for_each_batch(in, [&](read_batch const& batch) {
+        const uint64_t n = batch.num_reads();
+        if (n == 0) return;
+        rows.resize(n * row_words);
+        rep.fill(total += per_batch(batch, rows.data()));
+        const int stop = fn(ctx, first_read, n, rows.data());
+        if (stop) throw error(error_kind::argument, "the per-read callback returned " + std::to_string(stop));
+        first_read += n;
+    });
+}
+
+/* The file calls that accumulate over the whole file (cover, depth): a Holder on the devices from the first batch to the last -- every kind
+   of file takes the sequential reader --, `per_batch(batch, holder)` the engine call, `into(holder)` the holder's own or_into / add_into
+   once the batches are through. */
+template <typename Holder, typename PerBatch, typename Into>
+void accumulate_from_file(sshash_dict const* d, const char* filename, int multiline, report_out const& rep, PerBatch&& per_batch, Into&& into) {
+    with_query_file(d, filename, multiline, false, [&](read_stream& in) {
+        const Holder on_devices(*d->eng);
+        streaming_report total;
+        for_each_batch(in, [&](read_batch const& batch) { total += per_batch(batch, on_devices); });
+        into(on_devices);
+        rep.fill(total);
+    });
 }
 
 }  // namespace
@@ -463,26 +518,22 @@ sshash_status sshash_check_device(const sshash_dict* d, int device, uint64_t out
 sshash_status sshash_streaming_query_from_file(const sshash_dict* d, const char* filename, int multiline,
                                                sshash_streaming_report* report) {
     if (!d || !filename || !report) return fail(SSHASH_ERR_ARGUMENT, "null argument");
-    std::memset(report, 0, sizeof(*report));
+    const report_out rep(report);
     return guarded([&] {
-        read_stream in(filename, multiline != 0, d->idx->k);
-        if (!in.supported()) {
-            /* src/query.cpp:169-171: unsupported extension -> message on stderr, empty report */
-            fprintf(stderr, "unsupported query file format\n");
-            return;
-        }
-        /* an uncompressed FASTQ is read and parsed by all the lanes at once (reads.hpp: fastq_pieces); a file that is not four
-           lines per record comes back here and takes the sequential reader */
-        if (!multiline && fastq_pieces::applicable(filename) && !test_hook_u64("sequential_reader", 0, 0, 1)) {
-            streaming_report r;
-            if (d->eng->streaming_query_fastq_pieces(filename, r)) {
-                fill_report(report, r);
-                return;
+        with_query_file(d, filename, multiline, false, [&](read_stream& in) {
+            /* an uncompressed FASTQ is read and parsed by all the lanes at once (reads.hpp: fastq_pieces); a file that is not four
+               lines per record comes back here and takes the sequential reader */
+            if (!multiline && fastq_pieces::applicable(filename) && !test_hook_u64("sequential_reader", 0, 0, 1)) {
+                streaming_report r;
+                if (d->eng->streaming_query_fastq_pieces(filename, r)) {
+                    rep.fill(r);
+                    return;
+                }
             }
-        }
-        streaming_report total;
-        for_each_batch(in, [&](read_batch const& batch) {
-            fill_report(report, total += d->eng->streaming_query_host(batch.bases.data(), batch.offsets.data(), batch.num_reads()));
+            streaming_report total;
+            for_each_batch(in, [&](read_batch const& batch) {
+                rep.fill(total += d->eng->streaming_query_host(batch.bases.data(), batch.offsets.data(), batch.num_reads()));
+            });
         });
     });
 }
@@ -490,26 +541,13 @@ sshash_status sshash_streaming_query_from_file(const sshash_dict* d, const char*
 sshash_status sshash_streaming_query_from_file_per_read(const sshash_dict* d, const char* filename, int multiline,
                                                         sshash_per_read_fn fn, void* ctx, sshash_streaming_report* report) {
     if (!d || !filename || !fn) return fail(SSHASH_ERR_ARGUMENT, "null argument");
-    if (report) std::memset(report, 0, sizeof(*report));
+    const report_out rep(report);
     return guarded([&] {
-        read_stream in(filename, multiline != 0, d->idx->k, true);  // (every record of the file: row i is record i)
-        if (!in.supported()) {
-            fprintf(stderr, "unsupported query file format\n");
-            return;
-        }
-        static_assert(sizeof(sshash_streaming_report) == 6 * sizeof(uint64_t), "a row is six words");
-        streaming_report total;
-        uint64_t first_read = 0;
-        std::vector<sshash_streaming_report> rows;
-        for_each_batch(in, [&](read_batch const& batch) {
-            const uint64_t n = batch.num_reads();
-            if (n == 0) return;
-            rows.resize(n);
-            total += d->eng->streaming_query_per_read_host(batch.bases.data(), batch.offsets.data(), n, reinterpret_cast<uint64_t*>(rows.data()));
-            if (report) fill_report(report, total);
-            const int stop = fn(ctx, first_read, n, rows.data());
-            if (stop) throw error(error_kind::argument, "the per-read callback returned " + std::to_string(stop));
-            first_read += n;
+        with_query_file(d, filename, multiline, true, [&](read_stream& in) {
+            static_assert(sizeof(sshash_streaming_report) == 6 * sizeof(uint64_t), "a row is six words");
+            rows_from_file<sshash_streaming_report>(in, 1, fn, ctx, rep, [&](read_batch const& b, sshash_streaming_report* rows) {
+                return d->eng->streaming_query_per_read_host(b.bases.data(), b.offsets.data(), b.num_reads(), reinterpret_cast<uint64_t*>(rows));
+            });
         });
     });
 }
@@ -517,10 +555,8 @@ sshash_status sshash_streaming_query_from_file_per_read(const sshash_dict* d, co
 sshash_status sshash_streaming_query(const sshash_dict* d, const char* bases, const uint64_t* read_offsets,
                                      uint64_t num_reads, sshash_streaming_report* report) {
     if (!d || !report || (num_reads && (!bases || !read_offsets))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
-    std::memset(report, 0, sizeof(*report));
-    return guarded([&] {
-        fill_report(report, d->eng->streaming_query_host(bases, read_offsets, num_reads));
-    });
+    const report_out rep(report);
+    return guarded([&] { rep.fill(d->eng->streaming_query_host(bases, read_offsets, num_reads)); });
 }
 
 sshash_status sshash_streaming_query_device(const sshash_dict* d, int device, const char* bases,
@@ -543,10 +579,9 @@ sshash_status sshash_streaming_query_per_read(const sshash_dict* d, const char* 
                                               uint64_t num_reads, sshash_streaming_report* per_read,
                                               sshash_streaming_report* report) {
     if (!d || (num_reads && (!bases || !read_offsets || !per_read))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
-    if (report) std::memset(report, 0, sizeof(*report));
+    const report_out rep(report);
     return guarded([&] {
-        const streaming_report r = d->eng->streaming_query_per_read_host(bases, read_offsets, num_reads, reinterpret_cast<uint64_t*>(per_read));
-        if (report) fill_report(report, r);
+        rep.fill(d->eng->streaming_query_per_read_host(bases, read_offsets, num_reads, reinterpret_cast<uint64_t*>(per_read)));
     });
 }
 
@@ -565,10 +600,9 @@ sshash_status sshash_streaming_runs(const sshash_dict* d, const char* bases, con
                                     uint64_t* run_offsets, sshash_streaming_run* runs, uint64_t runs_capacity,
                                     sshash_streaming_report* report) {
     if (!d || (num_reads && (!bases || !read_offsets || !run_offsets)) || (!runs && runs_capacity)) return fail(SSHASH_ERR_ARGUMENT, "null argument");
-    if (report) std::memset(report, 0, sizeof(*report));
+    const report_out rep(report);
     return guarded([&] {
-        const streaming_report r = d->eng->streaming_runs_host(bases, read_offsets, num_reads, run_offsets, runs, runs_capacity);
-        if (report) fill_report(report, r);
+        rep.fill(d->eng->streaming_runs_host(bases, read_offsets, num_reads, run_offsets, runs, runs_capacity));
     });
 }
 
@@ -587,35 +621,25 @@ sshash_status sshash_streaming_cover_device(const sshash_dict* d, int device, co
 sshash_status sshash_streaming_cover(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
                                      uint64_t* cover, sshash_streaming_report* report) {
     if (!d || (num_reads && (!bases || !read_offsets || !cover))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
-    if (report) std::memset(report, 0, sizeof(*report));
+    const report_out rep(report);
     return guarded([&] {
         if (num_reads == 0) return;
         const cover_bitmaps on_devices(*d->eng);
         const streaming_report r = d->eng->streaming_cover_host(bases, read_offsets, num_reads, on_devices);
         on_devices.or_into(cover);
-        if (report) fill_report(report, r);
+        rep.fill(r);
     });
 }
 
 sshash_status sshash_streaming_cover_from_file(const sshash_dict* d, const char* filename, int multiline, uint64_t* cover,
                                                sshash_streaming_report* report) {
     if (!d || !filename || !cover) return fail(SSHASH_ERR_ARGUMENT, "null argument");
-    if (report) std::memset(report, 0, sizeof(*report));
+    const report_out rep(report);
     return guarded([&] {
-        read_stream in(filename, multiline != 0, d->idx->k);
-        if (!in.supported()) {
-            fprintf(stderr, "unsupported query file format\n");
-            return;
-        }
-        /* every kind of file takes the sequential reader (as sshash_streaming_query_from_file_per_read); the bitmaps stay on the
-           devices from the first batch to the last */
-        const cover_bitmaps on_devices(*d->eng);
-        streaming_report total;
-        for_each_batch(in, [&](read_batch const& batch) {
-            total += d->eng->streaming_cover_host(batch.bases.data(), batch.offsets.data(), batch.num_reads(), on_devices);
-        });
-        on_devices.or_into(cover);
-        if (report) fill_report(report, total);
+        accumulate_from_file<cover_bitmaps>(
+            d, filename, multiline, rep,
+            [&](read_batch const& b, cover_bitmaps const& bitmaps) { return d->eng->streaming_cover_host(b.bases.data(), b.offsets.data(), b.num_reads(), bitmaps); },
+            [&](cover_bitmaps const& bitmaps) { bitmaps.or_into(cover); });
     });
 }
 
@@ -664,34 +688,25 @@ sshash_status sshash_depth_finish_device(const sshash_dict* d, int device, const
 sshash_status sshash_streaming_depth(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
                                      uint32_t* depth, sshash_streaming_report* report) {
     if (!d || (num_reads && (!bases || !read_offsets || !depth))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
-    if (report) std::memset(report, 0, sizeof(*report));
+    const report_out rep(report);
     return guarded([&] {
         if (num_reads == 0) return;
         const depth_arrays on_devices(*d->eng);
         const streaming_report r = d->eng->streaming_depth_host(bases, read_offsets, num_reads, on_devices);
         on_devices.add_into(depth);
-        if (report) fill_report(report, r);
+        rep.fill(r);
     });
 }
 
 sshash_status sshash_streaming_depth_from_file(const sshash_dict* d, const char* filename, int multiline, uint32_t* depth,
                                                sshash_streaming_report* report) {
     if (!d || !filename || !depth) return fail(SSHASH_ERR_ARGUMENT, "null argument");
-    if (report) std::memset(report, 0, sizeof(*report));
+    const report_out rep(report);
     return guarded([&] {
-        read_stream in(filename, multiline != 0, d->idx->k);
-        if (!in.supported()) {
-            fprintf(stderr, "unsupported query file format\n");
-            return;
-        }
-        /* the sequential reader, as sshash_streaming_cover_from_file; the deltas stay on the devices from the first batch to the last */
-        const depth_arrays on_devices(*d->eng);
-        streaming_report total;
-        for_each_batch(in, [&](read_batch const& batch) {
-            total += d->eng->streaming_depth_host(batch.bases.data(), batch.offsets.data(), batch.num_reads(), on_devices);
-        });
-        on_devices.add_into(depth);
-        if (report) fill_report(report, total);
+        accumulate_from_file<depth_arrays>(
+            d, filename, multiline, rep,
+            [&](read_batch const& b, depth_arrays const& deltas) { return d->eng->streaming_depth_host(b.bases.data(), b.offsets.data(), b.num_reads(), deltas); },
+            [&](depth_arrays const& deltas) { deltas.add_into(depth); });
     });
 }
 
@@ -737,39 +752,24 @@ sshash_status sshash_streaming_sums_device(const sshash_dict* d, int device, con
 sshash_status sshash_streaming_sums(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
                                     const uint32_t* values, uint32_t at_least, sshash_read_sum* sums, sshash_streaming_report* report) {
     if (!d || (num_reads && (!bases || !read_offsets || !values || !sums))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
-    if (report) std::memset(report, 0, sizeof(*report));
+    const report_out rep(report);
     return guarded([&] {
         if (num_reads == 0) return;
         const value_prefixes on_devices(*d->eng, values, at_least);
-        const streaming_report r = d->eng->streaming_sums_host(bases, read_offsets, num_reads, on_devices, reinterpret_cast<uint64_t*>(sums));
-        if (report) fill_report(report, r);
+        rep.fill(d->eng->streaming_sums_host(bases, read_offsets, num_reads, on_devices, reinterpret_cast<uint64_t*>(sums)));
     });
 }
 
 sshash_status sshash_streaming_sums_from_file(const sshash_dict* d, const char* filename, int multiline, const uint32_t* values,
                                               uint32_t at_least, sshash_read_sums_fn fn, void* ctx, sshash_streaming_report* report) {
     if (!d || !filename || !values || !fn) return fail(SSHASH_ERR_ARGUMENT, "null argument");
-    if (report) std::memset(report, 0, sizeof(*report));
+    const report_out rep(report);
     return guarded([&] {
-        read_stream in(filename, multiline != 0, d->idx->k, true);  // (every record of the file: row i is record i)
-        if (!in.supported()) {
-            fprintf(stderr, "unsupported query file format\n");
-            return;
-        }
-        /* the sequential reader, as sshash_streaming_query_from_file_per_read; the prefix stays on the devices from the first batch to the last */
-        const value_prefixes on_devices(*d->eng, values, at_least);
-        streaming_report total;
-        uint64_t first_read = 0;
-        std::vector<sshash_read_sum> rows;
-        for_each_batch(in, [&](read_batch const& batch) {
-            const uint64_t n = batch.num_reads();
-            if (n == 0) return;
-            rows.resize(n);
-            total += d->eng->streaming_sums_host(batch.bases.data(), batch.offsets.data(), n, on_devices, reinterpret_cast<uint64_t*>(rows.data()));
-            if (report) fill_report(report, total);
-            const int stop = fn(ctx, first_read, n, rows.data());
-            if (stop) throw error(error_kind::argument, "the per-read callback returned " + std::to_string(stop));
-            first_read += n;
+        with_query_file(d, filename, multiline, true, [&](read_stream& in) {
+            const value_prefixes on_devices(*d->eng, values, at_least);  // (the prefix stays on the devices from the first batch to the last)
+            rows_from_file<sshash_read_sum>(in, 1, fn, ctx, rep, [&](read_batch const& b, sshash_read_sum* rows) {
+                return d->eng->streaming_sums_host(b.bases.data(), b.offsets.data(), b.num_reads(), on_devices, reinterpret_cast<uint64_t*>(rows));
+            });
         });
     });
 }
@@ -793,12 +793,11 @@ sshash_status sshash_streaming_classes(const sshash_dict* d, const char* bases, 
                                        const uint32_t* labels, uint32_t num_classes, uint32_t* rows, sshash_streaming_report* report) {
     if (!d || (num_reads && (!bases || !read_offsets || !labels || !rows))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
     if (!classes_in_range(num_classes)) return fail(SSHASH_ERR_ARGUMENT, "num_classes must be 1 .. SSHASH_MAX_CLASSES");
-    if (report) std::memset(report, 0, sizeof(*report));
+    const report_out rep(report);
     return guarded([&] {
         if (num_reads == 0) return;
         const class_labels_on_devices on_devices(*d->eng, labels);
-        const streaming_report r = d->eng->streaming_classes_host(bases, read_offsets, num_reads, on_devices, num_classes, rows);
-        if (report) fill_report(report, r);
+        rep.fill(d->eng->streaming_classes_host(bases, read_offsets, num_reads, on_devices, num_classes, rows));
     });
 }
 
@@ -806,27 +805,13 @@ sshash_status sshash_streaming_classes_from_file(const sshash_dict* d, const cha
                                                  uint32_t num_classes, sshash_read_classes_fn fn, void* ctx, sshash_streaming_report* report) {
     if (!d || !filename || !labels || !fn) return fail(SSHASH_ERR_ARGUMENT, "null argument");
     if (!classes_in_range(num_classes)) return fail(SSHASH_ERR_ARGUMENT, "num_classes must be 1 .. SSHASH_MAX_CLASSES");
-    if (report) std::memset(report, 0, sizeof(*report));
+    const report_out rep(report);
     return guarded([&] {
-        read_stream in(filename, multiline != 0, d->idx->k, true);  // (every record of the file: row i is record i)
-        if (!in.supported()) {
-            fprintf(stderr, "unsupported query file format\n");
-            return;
-        }
-        /* the sequential reader, as sshash_streaming_sums_from_file; the labels stay on the devices from the first batch to the last */
-        const class_labels_on_devices on_devices(*d->eng, labels);
-        streaming_report total;
-        uint64_t first_read = 0;
-        std::vector<uint32_t> rows;
-        for_each_batch(in, [&](read_batch const& batch) {
-            const uint64_t n = batch.num_reads();
-            if (n == 0) return;
-            rows.resize(n * num_classes);
-            total += d->eng->streaming_classes_host(batch.bases.data(), batch.offsets.data(), n, on_devices, num_classes, rows.data());
-            if (report) fill_report(report, total);
-            const int stop = fn(ctx, first_read, n, rows.data());
-            if (stop) throw error(error_kind::argument, "the per-read callback returned " + std::to_string(stop));
-            first_read += n;
+        with_query_file(d, filename, multiline, true, [&](read_stream& in) {
+            const class_labels_on_devices on_devices(*d->eng, labels);  // (the labels stay on the devices from the first batch to the last)
+            rows_from_file<uint32_t>(in, num_classes, fn, ctx, rep, [&](read_batch const& b, uint32_t* rows) {
+                return d->eng->streaming_classes_host(b.bases.data(), b.offsets.data(), b.num_reads(), on_devices, num_classes, rows);
+            });
         });
     });
 }
@@ -889,38 +874,23 @@ sshash_status sshash_streaming_best_run_device(const sshash_dict* d, int device,
 sshash_status sshash_streaming_best_run(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
                                         sshash_streaming_run* best, sshash_streaming_report* report) {
     if (!d || (num_reads && (!bases || !read_offsets || !best))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
-    if (report) std::memset(report, 0, sizeof(*report));
+    const report_out rep(report);
     return guarded([&] {
         if (num_reads == 0) return;
-        const streaming_report r = d->eng->streaming_best_run_host(bases, read_offsets, num_reads, best);
-        if (report) fill_report(report, r);
+        rep.fill(d->eng->streaming_best_run_host(bases, read_offsets, num_reads, best));
     });
 }
 
 sshash_status sshash_streaming_best_run_from_file(const sshash_dict* d, const char* filename, int multiline, sshash_read_best_run_fn fn,
                                                   void* ctx, sshash_streaming_report* report) {
     if (!d || !filename || !fn) return fail(SSHASH_ERR_ARGUMENT, "null argument");
-    if (report) std::memset(report, 0, sizeof(*report));
+    const report_out rep(report);
     return guarded([&] {
         d->eng->best_run_ready();  // (no replica, a minimizer shard: said before the file is opened)
-        read_stream in(filename, multiline != 0, d->idx->k, true);  // (every record of the file: record i of the output is record i of the file)
-        if (!in.supported()) {
-            fprintf(stderr, "unsupported query file format\n");
-            return;
-        }
-        /* the sequential reader, as sshash_streaming_sums_from_file */
-        streaming_report total;
-        uint64_t first_read = 0;
-        std::vector<sshash_streaming_run> best;
-        for_each_batch(in, [&](read_batch const& batch) {
-            const uint64_t n = batch.num_reads();
-            if (n == 0) return;
-            best.resize(n);
-            total += d->eng->streaming_best_run_host(batch.bases.data(), batch.offsets.data(), n, best.data());
-            if (report) fill_report(report, total);
-            const int stop = fn(ctx, first_read, n, best.data());
-            if (stop) throw error(error_kind::argument, "the per-read callback returned " + std::to_string(stop));
-            first_read += n;
+        with_query_file(d, filename, multiline, true, [&](read_stream& in) {
+            rows_from_file<sshash_streaming_run>(in, 1, fn, ctx, rep, [&](read_batch const& b, sshash_streaming_run* best) {
+                return d->eng->streaming_best_run_host(b.bases.data(), b.offsets.data(), b.num_reads(), best);
+            });
         });
     });
 }
@@ -961,10 +931,9 @@ sshash_status sshash_streaming_lookup_device(const sshash_dict* d, int device, c
 sshash_status sshash_streaming_lookup(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
                                       const sshash_results* out, sshash_streaming_report* report) {
     if (!d || !out || (num_reads && (!bases || !read_offsets))) return fail(SSHASH_ERR_ARGUMENT, "null argument");
-    if (report) std::memset(report, 0, sizeof(*report));
+    const report_out rep(report);
     return guarded([&] {
-        const streaming_report r = d->eng->streaming_lookup_host(bases, read_offsets, num_reads, to_view(out));
-        if (report) fill_report(report, r);
+        rep.fill(d->eng->streaming_lookup_host(bases, read_offsets, num_reads, to_view(out)));
     });
 }
 

@@ -199,7 +199,7 @@ int main(int argc, char** argv) {
         bool stopped = false;
         try {
             dict.streaming_best_run_from_file(path, false, [&](uint64_t, sshash_streaming_run const*, uint64_t) { return ++calls, 7; });
-        } catch (std::exception const&) {
+        } catch (std::runtime_error const&) {  // (the facade's error type, and no other)
             stopped = true;
         }
         std::remove(path.c_str());

@@ -241,7 +241,7 @@ int main(int argc, char** argv) {
         bool stopped = false;
         try {
             dict.streaming_classes_from_file(path, false, labels, C, [&](uint64_t, uint32_t const*, uint64_t) { return ++calls, 7; });
-        } catch (std::exception const&) {
+        } catch (std::runtime_error const&) {  // (the facade's error type, and no other)
             stopped = true;
         }
         std::remove(path.c_str());

@@ -3,7 +3,8 @@
 //       the same reads, word for word; no bit at or above num_kmers is set; its report is the batch's report of streaming_query_per_read;
 //   [B] the bitmap is ORed into: a second batch into the bitmap of the first gives the union, bits set by the caller survive;
 //   [C] the same bitmap out of the runs of streaming_runs (forward: [kmer_id, kmer_id + n), backward: (kmer_id - n, kmer_id]);
-//   [D] cover_string_counts: per string the set bits among its ids, their sum the bitmap's popcount.
+//   [D] cover_string_counts: per string the set bits among its ids, their sum the bitmap's popcount;
+//   [E] streaming_cover_from_file over the second batch written as FASTA, into the bitmap of the first: the union of [B], the same report.
 // Reads: those of check_runs.cpp (windows of the dictionary's own strings, either strand, with substitutions and N's; two windows glued
 // together; random reads; reads shorter than k), a whole string, its reverse complement.
 // Usage: check_cover <input.fa[.gz]> <k> <m> [--canonical]
@@ -12,6 +13,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <filesystem>
+#include <fstream>
 #include <iostream>
 #include <random>
 #include <string>
@@ -152,7 +155,7 @@ int main(int argc, char** argv) {
         /* [B] */
         std::vector<uint64_t> both = cover, want_both(cover.size());
         for (uint64_t w = 0; w < cover.size(); ++w) want_both[w] = want_one[w] | want_two[w];
-        dict.streaming_cover(two.bases.data(), two.offsets.data(), two.size(), both);
+        const streaming_query_report rep_two = dict.streaming_cover(two.bases.data(), two.offsets.data(), two.size(), both);
         ok = ok && same(both, want_both, "[B] the second batch into the bitmap of the first");
         std::vector<uint64_t> kept(cover.size(), 0), want_kept = want_two;
         for (uint64_t w = 0; w < kept.size(); w += 3) {
@@ -193,6 +196,23 @@ int main(int argc, char** argv) {
         ok = ok && same(counts, want_counts, "[D] counts per string (CPU)");
         if (total != want_total) {
             std::cerr << "[D] total " << total << ", expected " << want_total << std::endl;
+            ok = false;
+        }
+
+        /* [E] */
+        const std::string path = (std::filesystem::temp_directory_path() / ("check_cover_" + std::to_string(k) + (cfg.canonical ? "c" : "r") + ".fa")).string();
+        {
+            std::ofstream f(path);
+            for (uint64_t r = 0; r < two.size(); ++r)
+                if (two.offsets[r + 1] > two.offsets[r]) f << ">" << r << "\n" << two.bases.substr(two.offsets[r], two.offsets[r + 1] - two.offsets[r]) << "\n";
+        }
+        std::vector<uint64_t> from_file = cover;
+        const streaming_query_report file_rep = dict.streaming_cover_from_file(path, false, from_file);
+        std::remove(path.c_str());
+        ok = ok && same(from_file, want_both, "[E] the file of the second batch into the bitmap of the first");
+        if (file_rep.num_kmers != rep_two.num_kmers || file_rep.num_positive_kmers != rep_two.num_positive_kmers || file_rep.num_searches != rep_two.num_searches ||
+            file_rep.num_extensions != rep_two.num_extensions || file_rep.num_positive_kmers == 0) {
+            std::cerr << "[E] the file's report differs from the in-memory call's: " << file_rep.num_positive_kmers << " positive against " << rep_two.num_positive_kmers << std::endl;
             ok = false;
         }
         if (ok) std::cout << "EVERYTHING OK! " << set_bits << " of " << dict.num_kmers() << " k-mers covered by the first batch, " << want_total << " by both" << std::endl;

@@ -4,7 +4,8 @@
 //   [B] the array is added into: a second batch into the array of the first gives the sum, values set by the caller survive (modulo 2^32);
 //   [C] the same array out of the runs of streaming_runs, as a difference array: +1 at a run's first id, -1 behind its last, a prefix sum;
 //       (depth != 0) is the bitmap of streaming_cover;
-//   [D] depth_string_sums: per string the 64-bit sum over its ids, their sum the array's.
+//   [D] depth_string_sums: per string the 64-bit sum over its ids, their sum the array's;
+//   [E] streaming_depth_from_file over the second batch written as FASTA, into the array of the first: the sum of [B], the same report.
 // Reads: those of check_cover.cpp (windows of the dictionary's own strings, either strand, with substitutions and N's; two windows glued
 // together; random reads; reads shorter than k), a whole string, its reverse complement, and one window many times.
 // Usage: check_depth <input.fa[.gz]> <k> <m> [--canonical]
@@ -13,6 +14,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <filesystem>
+#include <fstream>
 #include <iostream>
 #include <random>
 #include <string>
@@ -153,7 +156,7 @@ int main(int argc, char** argv) {
         /* [B] */
         std::vector<uint32_t> both = depth, want_both(n);
         for (uint64_t i = 0; i < n; ++i) want_both[i] = want_one[i] + want_two[i];
-        dict.streaming_depth(two.bases.data(), two.offsets.data(), two.size(), both);
+        const streaming_query_report rep_two = dict.streaming_depth(two.bases.data(), two.offsets.data(), two.size(), both);
         ok = ok && same(both, want_both, "[B] the second batch into the array of the first");
         std::vector<uint32_t> kept(n, 0), want_kept = want_two;
         for (uint64_t i = 0; i < n; i += 3) {
@@ -205,6 +208,22 @@ int main(int argc, char** argv) {
         ok = ok && same(sums, want_sums, "[D] sums per string (CPU)");
         if (total != want_total || (want_total >> 32) == 0) {
             std::cerr << "[D] total " << total << ", expected " << want_total << " (and more than 32 bits of it)" << std::endl;
+            ok = false;
+        }
+        /* [E] */
+        const std::string path = (std::filesystem::temp_directory_path() / ("check_depth_" + std::to_string(k) + (cfg.canonical ? "c" : "r") + ".fa")).string();
+        {
+            std::ofstream f(path);
+            for (uint64_t r = 0; r < two.size(); ++r)
+                if (two.offsets[r + 1] > two.offsets[r]) f << ">" << r << "\n" << two.bases.substr(two.offsets[r], two.offsets[r + 1] - two.offsets[r]) << "\n";
+        }
+        std::vector<uint32_t> from_file = depth;
+        const streaming_query_report file_rep = dict.streaming_depth_from_file(path, false, from_file);
+        std::remove(path.c_str());
+        ok = ok && same(from_file, want_both, "[E] the file of the second batch into the array of the first");
+        if (file_rep.num_kmers != rep_two.num_kmers || file_rep.num_positive_kmers != rep_two.num_positive_kmers || file_rep.num_searches != rep_two.num_searches ||
+            file_rep.num_extensions != rep_two.num_extensions || file_rep.num_positive_kmers == 0) {
+            std::cerr << "[E] the file's report differs from the in-memory call's: " << file_rep.num_positive_kmers << " positive against " << rep_two.num_positive_kmers << std::endl;
             ok = false;
         }
         if (ok) std::cout << "EVERYTHING OK! " << held << " of " << n << " k-mers held by the first batch, " << sum << " times in all, one of them " << deepest << " times" << std::endl;

@@ -172,6 +172,11 @@ int main(int argc, char** argv) {
             std::cerr << "the file's rows differ from the in-memory call's (" << expect << " of " << n << " records seen, report " << from_file << ")" << std::endl;
             ok = false;
         }
+        const streaming_query_report whole_file = dict.streaming_query_from_file(path, false);  // (the total alone, through the parallel FASTQ reader)
+        if (!same(whole_file, total)) {
+            std::cerr << "streaming_query_from_file reports " << whole_file << ", the in-memory call " << total << std::endl;
+            ok = false;
+        }
         bool stopped = false;
         uint64_t calls_after = 0;
         try {

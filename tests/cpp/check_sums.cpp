@@ -217,7 +217,7 @@ int main(int argc, char** argv) {
         bool stopped = false;
         try {
             dict.streaming_sums_from_file(path, false, values, 0, [&](uint64_t, sshash_read_sum const*, uint64_t) { return ++calls, 7; });
-        } catch (std::exception const&) {
+        } catch (std::runtime_error const&) {  // (the facade's error type, and no other)
             stopped = true;
         }
         std::remove(path.c_str());

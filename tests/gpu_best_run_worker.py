@@ -391,6 +391,20 @@ def main():
         raise AssertionError("a callback's non-zero return did not stop the query")
     except sshash_amd.SSHashError as e:
         assert e.status == 1 and len(calls) == 1, (e, calls)
+    os.environ["SSHASH_AMD_TEST_HOOKS"] = "query_batch_bases=100000"
+    calls = []
+
+    def broken(first, best):
+        calls.append(first)
+        if len(calls) == 2:
+            raise KeyError("mine")
+
+    try:
+        d.streaming_best_run_from_file(own, per_read=broken)
+        raise AssertionError("a callback's exception did not stop the query")
+    except KeyError as e:
+        assert e.args == ("mine",) and len(calls) == 2 and calls[0] == 0 and calls[1] > 0, (e, calls)
+    del os.environ["SSHASH_AMD_TEST_HOOKS"]
 
     # ---- the finish on the device: the device call's own CSR, and the CSR made by hand of the CPU test ----
     dev_offsets, dev_runs = device_runs(d, reads)

@@ -410,6 +410,18 @@ def main():
         raise AssertionError("a callback's non-zero return did not stop the query")
     except sshash_amd.SSHashError as e:
         assert e.status == 1 and len(calls) == 1, (e, calls)
+    calls = []
+
+    def broken(first, rows):
+        calls.append(first)
+        if len(calls) == 2:
+            raise KeyError("mine")
+
+    try:
+        d.streaming_sums_from_file(own, random_values, per_read=broken)
+        raise AssertionError("a callback's exception did not stop the query")
+    except KeyError as e:
+        assert e.args == ("mine",) and len(calls) == 2 and calls[0] == 0 and calls[1] > 0, (e, calls)
     del os.environ["SSHASH_AMD_TEST_HOOKS"]
 
     print(json.dumps({"ok": True, "reads": n, "positive": int(want["positive_kmers"].sum(dtype=np.uint64)), "num_kmers": n_kmers,

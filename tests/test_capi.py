@@ -26,6 +26,8 @@ def test_every_declared_symbol_is_exported():
     for name in names:
         assert hasattr(lib, name), f"{name} declared in include/sshash_amd.h but not exported"
     assert set(_binding.C_ABI_SYMBOLS) == set(names)
+    # the names are those of the table _load() binds: one list, held against the header here
+    assert _binding.C_ABI_SYMBOLS == tuple(_binding._SIGNATURES) and len(set(_binding.C_ABI_SYMBOLS)) == len(names)
 
 
 def test_only_c_types_in_signatures():

@@ -174,6 +174,33 @@ def test_a_dictionary_that_is_not_resident_is_no_device(tmp_path):
     assert (room == GUARD).all() and (rep == 9).all()
 
 
+def test_an_unsupported_extension_comes_behind_the_readiness_check(tmp_path):
+    """a query file whose extension says nothing, on a dictionary that is resident nowhere: SSHASH_ERR_NO_DEVICE, not the empty report
+    of the other file calls -- best_run_ready() comes before the file is opened --; the report is zeroed all the same, per_read is
+    never called"""
+    rng = np.random.default_rng(3)
+    path = str(tmp_path / "tiny.fa")
+    with open(path, "w") as f:
+        for i in range(40):
+            f.write(f">{i}\n{''.join('ACGT'[c] for c in rng.integers(0, 4, int(rng.integers(15, 300))))}\n")
+    d = sshash_amd.Dictionary.build(path, k=15, m=7)
+    q = tmp_path / "q.txt"
+    q.write_text("ACGT\n")
+    seen = []
+    for per_read in (None, lambda first, best: seen.append(first)):
+        with pytest.raises(sshash_amd.SSHashError) as e:
+            d.streaming_best_run_from_file(str(q), per_read=per_read)
+        assert e.value.status == ERR_NO_DEVICE
+    rep = B._Report(1, 2, 3, 4, 5, 6)
+    fn = B._PerReadFn(lambda ctx, first, n, rows: seen.append(first) or 0)
+    assert B._load().sshash_streaming_best_run_from_file(d._h, os.fsencode(str(q)), 0, fn, None, C.byref(rep)) == ERR_NO_DEVICE
+    assert d._report(rep) == B.StreamingQueryReport() and seen == []
+    assert B._load().sshash_streaming_best_run_from_file(d._h, os.fsencode(str(q)), 0, fn, None, None) == ERR_NO_DEVICE
+    with pytest.raises(sshash_amd.SSHashError) as e:  # (nor is a file that cannot be opened looked for before that)
+        d.streaming_best_run_from_file(str(tmp_path / "missing.fa"))
+    assert e.value.status == ERR_NO_DEVICE
+
+
 def test_runs_best_on_the_host_against_numpy_on_a_csr_made_by_hand():
     run_offsets, runs, want_at = hand_made_csr()
     counts = np.diff(run_offsets.astype(np.int64))

@@ -179,6 +179,37 @@ def test_a_dictionary_that_is_not_resident_is_no_device(tmp_path):
     assert (rows == 0x77).all() and (rep == 9).all() and (best.view(np.uint32) == 0x33).all() and (totals == 0x33).all()
 
 
+def test_an_unsupported_extension_is_an_empty_report_without_any_device(tmp_path):
+    """a query file whose extension says nothing: the call says "unsupported query file format" and returns before any device is asked for -- this dictionary is resident
+    nowhere, and the call succeeds --, the report all zeros, per_read never called, no rows"""
+    rng = np.random.default_rng(3)
+    path = str(tmp_path / "tiny.fa")
+    with open(path, "w") as f:
+        for i in range(40):
+            f.write(f">{i}\n{''.join('ACGT'[c] for c in rng.integers(0, 4, int(rng.integers(15, 300))))}\n")
+    d = sshash_amd.Dictionary.build(path, k=15, m=7)
+    q = tmp_path / "q.txt"
+    q.write_text("ACGT\n")
+    labels = (np.arange(d.num_strings()) % 3).astype(np.uint32)
+    seen = []
+    assert d.streaming_classes_from_file(str(q), labels, 3, per_read=lambda first, rows: seen.append(first)) == B.StreamingQueryReport()
+    assert seen == []
+    got, report = d.streaming_classes_from_file(str(q), labels, 5, multiline=True)
+    assert got.dtype == np.uint32 and got.shape == (0, 5) and report == B.StreamingQueryReport()
+    rep = B._Report(1, 2, 3, 4, 5, 6)
+    fn = B._PerReadFn(lambda ctx, first, n, rows: seen.append(first) or 0)
+    assert B._load().sshash_streaming_classes_from_file(d._h, os.fsencode(str(q)), 0, labels.ctypes.data, 3, fn, None, C.byref(rep)) == 0
+    assert d._report(rep) == B.StreamingQueryReport() and seen == []
+    assert B._load().sshash_streaming_classes_from_file(d._h, os.fsencode(str(q)), 0, labels.ctypes.data, 3, fn, None, None) == 0
+    with pytest.raises(sshash_amd.SSHashError) as e:  # (a file that cannot be opened: said before any device is asked for, too)
+        d.streaming_classes_from_file(str(tmp_path / "missing.fa"), labels, 3, per_read=lambda first, rows: seen.append(first))
+    assert e.value.status == 2 and seen == []
+    # the order of the checks: num_classes is looked at before the report is zeroed
+    rep = B._Report(1, 2, 3, 4, 5, 6)
+    assert B._load().sshash_streaming_classes_from_file(d._h, os.fsencode(str(q)), 0, labels.ctypes.data, 0, fn, None, C.byref(rep)) == ERR_ARGUMENT
+    assert rep.num_kmers == 1 and rep.num_extensions == 6
+
+
 def _numpy_best(rows):
     n, classes = rows.shape
     out = np.zeros(n, dtype=sshash_amd.READ_CLASS_DTYPE)

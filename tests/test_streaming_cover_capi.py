@@ -161,6 +161,31 @@ def test_without_a_device_the_streaming_calls_fail_loudly(case_skew_regular):
     assert (cover == 0x11).all() and (counts == 7).all()
 
 
+def test_an_unsupported_extension_is_an_empty_report_without_any_device(tmp_path):
+    """a query file whose extension says nothing: the call says "unsupported query file format" and returns before any device is asked for -- this dictionary is resident
+    nowhere, and the call succeeds --, the report all zeros, a supplied bitmap untouched"""
+    rng = np.random.default_rng(3)
+    path = str(tmp_path / "tiny.fa")
+    with open(path, "w") as f:
+        for i in range(40):
+            f.write(f">{i}\n{''.join('ACGT'[c] for c in rng.integers(0, 4, int(rng.integers(15, 300))))}\n")
+    d = sshash_amd.Dictionary.build(path, k=15, m=7)
+    q = tmp_path / "q.txt"
+    q.write_text("ACGT\n")
+    cover = np.full(d.cover_words(), 0x11, dtype=np.uint64)
+    got, report = d.streaming_cover_from_file(str(q), cover=cover)
+    assert got is cover and (cover == 0x11).all() and report == B.StreamingQueryReport()
+    got, report = d.streaming_cover_from_file(str(q), multiline=True)
+    assert got.shape == (d.cover_words(),) and not got.any() and report == B.StreamingQueryReport()
+    rep = B._Report(1, 2, 3, 4, 5, 6)
+    assert B._load().sshash_streaming_cover_from_file(d._h, os.fsencode(str(q)), 0, cover.ctypes.data, C.byref(rep)) == 0
+    assert d._report(rep) == B.StreamingQueryReport() and (cover == 0x11).all()
+    assert B._load().sshash_streaming_cover_from_file(d._h, os.fsencode(str(q)), 0, cover.ctypes.data, None) == 0
+    with pytest.raises(sshash_amd.SSHashError) as e:  # (a file that cannot be opened: said before any device is asked for, too)
+        d.streaming_cover_from_file(str(tmp_path / "missing.fa"), cover=cover)
+    assert e.value.status == 2 and (cover == 0x11).all()
+
+
 @pytest.mark.parametrize("case_name", CASES)
 def test_string_counts_against_numpy(case_name, request):
     """the all-zero bitmap, the all-ones bitmap (valid bits only; and with the bits behind num_kmers set as well, which are not counted),

@@ -151,6 +151,31 @@ def test_a_dictionary_that_is_not_resident_is_no_device(tmp_path):
     assert total == 0x11 * d.num_kmers() == int(got.sum())
 
 
+def test_an_unsupported_extension_is_an_empty_report_without_any_device(tmp_path):
+    """a query file whose extension says nothing: the call says "unsupported query file format" and returns before any device is asked for -- this dictionary is resident
+    nowhere, and the call succeeds --, the report all zeros, a supplied depth array untouched"""
+    rng = np.random.default_rng(3)
+    path = str(tmp_path / "tiny.fa")
+    with open(path, "w") as f:
+        for i in range(40):
+            f.write(f">{i}\n{''.join('ACGT'[c] for c in rng.integers(0, 4, int(rng.integers(15, 300))))}\n")
+    d = sshash_amd.Dictionary.build(path, k=15, m=7)
+    q = tmp_path / "q.txt"
+    q.write_text("ACGT\n")
+    depth = np.full(d.num_kmers(), 0x11, dtype=np.uint32)
+    got, report = d.streaming_depth_from_file(str(q), depth=depth)
+    assert got is depth and (depth == 0x11).all() and report == B.StreamingQueryReport()
+    got, report = d.streaming_depth_from_file(str(q), multiline=True)
+    assert got.shape == (d.num_kmers(),) and not got.any() and report == B.StreamingQueryReport()
+    rep = B._Report(1, 2, 3, 4, 5, 6)
+    assert B._load().sshash_streaming_depth_from_file(d._h, os.fsencode(str(q)), 0, depth.ctypes.data, C.byref(rep)) == 0
+    assert d._report(rep) == B.StreamingQueryReport() and (depth == 0x11).all()
+    assert B._load().sshash_streaming_depth_from_file(d._h, os.fsencode(str(q)), 0, depth.ctypes.data, None) == 0
+    with pytest.raises(sshash_amd.SSHashError) as e:  # (a file that cannot be opened: said before any device is asked for, too)
+        d.streaming_depth_from_file(str(tmp_path / "missing.fa"), depth=depth)
+    assert e.value.status == 2 and (depth == 0x11).all()
+
+
 @pytest.mark.parametrize("case_name", CASES)
 def test_string_sums_against_numpy(case_name, request):
     """zeros, ones (the strings' sizes), random words over the whole 32-bit range -- most strings' sums pass 2^32 --, the overwrite rule"""

@@ -75,6 +75,10 @@ def test_argument_errors_come_first(case_skew_regular, tmp_path):
     assert from_file(d._h, os.fsencode(str(fq)), 0, null_fn, None, C.byref(rep)) == ERR_ARGUMENT
     assert from_file(None, os.fsencode(str(fq)), 0, fn, None, C.byref(rep)) == ERR_ARGUMENT
     assert from_file(d._h, None, 0, fn, None, C.byref(rep)) == ERR_ARGUMENT
+    totals = lib.sshash_streaming_query_from_file  # (the total alone: its report is no option)
+    assert totals(None, os.fsencode(str(fq)), 0, C.byref(rep)) == ERR_ARGUMENT
+    assert totals(d._h, None, 0, C.byref(rep)) == ERR_ARGUMENT
+    assert totals(d._h, os.fsencode(str(fq)), 0, None) == ERR_ARGUMENT
     assert called == []
     assert (rows == 0).all()
 
@@ -111,6 +115,9 @@ def test_without_a_device_the_calls_fail_loudly(case_skew_regular, tmp_path):
     with pytest.raises(sshash_amd.SSHashError) as e:
         d.streaming_query_from_file(str(fq), per_read=lambda first, block: seen.append(first))
     assert e.value.status == ERR_NO_DEVICE and seen == []
+    with pytest.raises(sshash_amd.SSHashError) as e:
+        d.streaming_query_from_file(str(fq))
+    assert e.value.status == ERR_NO_DEVICE
 
 
 def test_the_file_query_keeps_its_signature(case_skew_regular, tmp_path):

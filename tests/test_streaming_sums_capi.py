@@ -143,6 +143,33 @@ def test_a_dictionary_that_is_not_resident_is_no_device(tmp_path):
     assert (prefix == 0x55).all() and (sums["sum"] == 0x77).all() and (rep == 9).all()
 
 
+def test_an_unsupported_extension_is_an_empty_report_without_any_device(tmp_path):
+    """a query file whose extension says nothing: the call says "unsupported query file format" and returns before any device is asked for -- this dictionary is resident
+    nowhere, and the call succeeds --, the report all zeros, per_read never called, no rows"""
+    rng = np.random.default_rng(3)
+    path = str(tmp_path / "tiny.fa")
+    with open(path, "w") as f:
+        for i in range(40):
+            f.write(f">{i}\n{''.join('ACGT'[c] for c in rng.integers(0, 4, int(rng.integers(15, 300))))}\n")
+    d = sshash_amd.Dictionary.build(path, k=15, m=7)
+    q = tmp_path / "q.txt"
+    q.write_text("ACGT\n")
+    values = np.full(d.num_kmers(), 3, dtype=np.uint32)
+    seen = []
+    assert d.streaming_sums_from_file(str(q), values, per_read=lambda first, rows: seen.append(first)) == B.StreamingQueryReport()
+    assert seen == []
+    got, report = d.streaming_sums_from_file(str(q), values, at_least=2, multiline=True)
+    assert got.dtype == sshash_amd.READ_SUM_DTYPE and got.shape == (0,) and report == B.StreamingQueryReport()
+    rep = B._Report(1, 2, 3, 4, 5, 6)
+    fn = B._PerReadFn(lambda ctx, first, n, rows: seen.append(first) or 0)
+    assert B._load().sshash_streaming_sums_from_file(d._h, os.fsencode(str(q)), 0, values.ctypes.data, 0, fn, None, C.byref(rep)) == 0
+    assert d._report(rep) == B.StreamingQueryReport() and seen == []
+    assert B._load().sshash_streaming_sums_from_file(d._h, os.fsencode(str(q)), 0, values.ctypes.data, 0, fn, None, None) == 0
+    with pytest.raises(sshash_amd.SSHashError) as e:  # (a file that cannot be opened: said before any device is asked for, too)
+        d.streaming_sums_from_file(str(tmp_path / "missing.fa"), values, per_read=lambda first, rows: seen.append(first))
+    assert e.value.status == 2 and seen == []
+
+
 def test_values_none_wants_a_weighted_dictionary(case_skew_regular):
     """values=None stands for the dictionary's weights: a dictionary that stores none raises before anything else happens"""
     d = case_skew_regular.dict
