@@ -260,23 +260,25 @@ sshash_status sshash_streaming_query_device(const sshash_dict* d, int device, co
  *      SEGMENTS of S k-mers (neighbours overlap by k - 1 bases; nothing is copied), one lane each. What differs is put right on the
  *      device: a segment's first k-mer counts as a search where in the whole read it may be an extension -- the rule of the runs
  *      below --, and a pass over the seams moves those back. The six counters, every per-read row, the cover, the depth, the sums and
- *      the classes are word for word what the uncut reads give.
+ *      the classes are word for word what the uncut reads give, and so are the run records: a run that goes on over a seam is merged on
+ *      the device, without moving a record.
  *      Segmenting is OPT-IN: a new dictionary is at SSHASH_SEGMENTS_OFF with device_calls = 0 and takes the routes it always took.
  *      kmers_per_segment: 0 = the library's default S (256, RESULTS.md: best of 256, 1024, 4096 through the host call; the device calls
  *      favour 1024 slightly); SSHASH_SEGMENTS_OFF = never segment; otherwise 1 .. 2^30 (tiny values are allowed and only slow: tests
  *      put seams into small reads with them). Anything else, or a NULL dictionary, is SSHASH_ERR_ARGUMENT. Needs no device. Not to be changed while a call
  *      on the dictionary is in flight.
- *      Host and file calls (sshash_streaming_query, _per_read, _cover, _depth, _sums, _classes and their _from_file forms), once an S is set: a piece of
+ *      Host and file calls (sshash_streaming_query, _per_read, _runs, _cover, _depth, _sums, _classes and their _from_file forms), once an S is set: a piece of
  *      the batch that holds a read of more than S k-mers takes the run kernel over segments; pieces of shorter reads take exactly the launches they took
  *      before. With SSHASH_SEGMENTS_OFF a piece that holds a read above 2^16 bases goes through the position-parallel pipeline of
  *      sshash_streaming_lookup instead (one point lookup per k-mer, the same results).
- *      Device calls (sshash_streaming_query_device, _per_read_device, _cover_device, _depth_device, _sums_device, _classes_device): segment only with device_calls != 0
+ *      Device calls (sshash_streaming_query_device, _per_read_device, _runs_device, _cover_device, _depth_device, _sums_device, _classes_device): segment only with device_calls != 0
  *      -- they cannot see the reads' lengths without a synchronisation, and building the table costs a batch of short reads three small
- *      launches and a scan. With it: scratch of 24 bytes per segment (72 with rows) for at most num_reads + total_bases / S segments,
+ *      launches and a scan. With it: scratch of 24 bytes per segment (72 with rows; the run records 13 more: the place of a segment's
+ *      first record, the length it hands to the record before, its seam flag) for at most num_reads + total_bases / S segments,
  *      sized from that bound without a synchronisation; the entries past the true count are empty and lie behind the last segment, so
  *      on reads shorter than S the last waves of the launch find nothing to do while the others carry all of it (150-base reads at
  *      S = 256: two fifths of the waves, 4.5 -> 6.3 ms) -- switch it on for long reads. Without it they are launch for launch what they were.
- *      Never segmented: sshash_streaming_runs[_device] (records that span seams want a merge pass), sshash_streaming_lookup[_device], and
+ *      Never segmented: sshash_streaming_best_run[_device] (a longest run is not additive), sshash_streaming_lookup[_device], and
  *      every call on a minimizer shard (num_shards > 1: a shard's run kernel follows a run through k-mers it does not own, which a look
  *      at a seam would miss) -- those keep their routes whatever is set here.
  *      sshash_get_read_segments: the setting (S with the default resolved, or SSHASH_SEGMENTS_OFF), device_calls, and how many
@@ -347,17 +349,36 @@ typedef struct sshash_streaming_run {
  * only enqueues, does not look at the reads' lengths (the host call below does and refuses); a longer read gets wrapped fields. Always the
  * run kernel, as sshash_streaming_query_per_read_device: a counting launch (the runs of every read), a prefix sum, and -- with
  * runs_capacity > 0 -- a second launch that writes the records; scratch beyond that of sshash_streaming_query_device: 8 bytes per
- * 4096 reads. */
+ * 4096 reads. One lane walks one read, whatever its length, unless sshash_set_read_segments has switched segments on for the device
+ * calls: then one lane walks one segment -- the counting launch counts per segment, a pass over the seams tells which segments begin
+ * inside a run, the prefix sum gives every record that STARTS in a segment its final place, the writing launch stores those, and one
+ * 32-bit add per joined seam gives a run that goes on over it its whole length. run_offsets and every record are byte for byte those
+ * of the uncut call, at every capacity. */
 sshash_status sshash_streaming_runs_device(const sshash_dict* d, int device, const char* bases, const uint64_t* read_offsets,
                                            uint64_t num_reads, uint64_t total_bases, uint64_t* run_offsets,
                                            sshash_streaming_run* runs, uint64_t runs_capacity, uint64_t* report, void* hip_stream);
 /* host buffers, sharded over all resident replicas like sshash_streaming_query_per_read (a piece that holds a read above 2^16 bases
- * goes through the position-parallel pipeline of sshash_streaming_lookup and a compaction behind it, which give the same
- * records: the runs are never cut into segments); same capacity rule; report may be NULL. A read of 2^31 bases or more is SSHASH_ERR_ARGUMENT (read_pos / num_kmers could
+ * takes the run kernel over segments -- sshash_set_read_segments, both the counting and the writing pass; with segments off it goes
+ * through the position-parallel pipeline of sshash_streaming_lookup and a compaction behind it --, which gives the same
+ * records); same capacity rule; report may be NULL. A read of 2^31 bases or more is SSHASH_ERR_ARGUMENT (read_pos / num_kmers could
  * not hold it). */
 sshash_status sshash_streaming_runs(const sshash_dict* d, const char* bases, const uint64_t* read_offsets, uint64_t num_reads,
                                     uint64_t* run_offsets, sshash_streaming_run* runs, uint64_t runs_capacity,
                                     sshash_streaming_report* report);
+/* a query file -- a multiline FASTA of contigs mapped onto the unitigs without loading it first: the runs are handed over in batches, IN
+ * FILE ORDER, one call of `fn` at a time, as the rows of sshash_streaming_query_from_file_per_read are. run_offsets (n + 1 words,
+ * run_offsets[0] = 0) is LOCAL TO THE BATCH: the runs of record first_read + i of the file are runs[run_offsets[i] ..
+ * run_offsets[i + 1]). There is an entry for EVERY record of the file; one shorter than k has an empty range. Both arrays are the
+ * library's and valid during the call of `fn` only. A non-zero return of `fn` stops the query: the call returns SSHASH_ERR_ARGUMENT,
+ * sshash_last_error() carries the value and `fn` is not called again. report may be NULL. A NULL dictionary, filename or fn is
+ * SSHASH_ERR_ARGUMENT before anything runs; a record of 2^31 bases or more is SSHASH_ERR_ARGUMENT. Every kind of file takes the
+ * sequential reader: host memory stays bounded by a batch and its runs. Batches go through the route of sshash_streaming_runs -- long
+ * records over segments once sshash_set_read_segments has set an S --, counted once. */
+typedef int (*sshash_read_runs_fn)(void* ctx, uint64_t first_read, uint64_t n,
+                                   const uint64_t* run_offsets /* n + 1 words, [0] = 0, local to the batch */,
+                                   const sshash_streaming_run* runs);
+sshash_status sshash_streaming_runs_from_file(const sshash_dict* d, const char* filename, int multiline,
+                                              sshash_read_runs_fn fn, void* ctx, sshash_streaming_report* report);
 
 /* ---- WHICH k-mers of the dictionary a read set holds: the streaming query seen from the dictionary's side (no reference counterpart
  *      as a call). A COVER is a bitmap over the k-mer ids: ceil(num_kmers / 64) words of 64 bits (sshash_cover_words); k-mer id i is bit

@@ -303,6 +303,19 @@ public:
                                void* hip_stream) const {
         check(sshash_streaming_runs_device(m_h, device, d_bases, d_read_offsets, num_reads, total_bases, d_run_offsets, d_runs, runs_capacity, d_report, hip_stream));
     }
+    /* a query file, the runs of every record, handed over in file order: fn(first_read, run_offsets, runs, n) for one batch after the
+       other -- run_offsets has n + 1 words, [0] = 0, local to the batch; both arrays are valid during the call of fn only --; a non-zero
+       return stops the query (std::runtime_error). Fn: int(uint64_t, uint64_t const*, sshash_streaming_run const*, uint64_t). */
+    template <typename Fn>
+    streaming_query_report streaming_runs_from_file(std::string const& filename, bool multiline, Fn&& fn) const {
+        struct runs_callback {
+            typename std::remove_reference<Fn>::type* fn;
+            static int thunk(void* ctx, uint64_t first_read, uint64_t n, const uint64_t* run_offsets, const sshash_streaming_run* runs) {
+                return int((*static_cast<runs_callback*>(ctx)->fn)(first_read, run_offsets, runs, n));
+            }
+        } cb{&fn};
+        return reported([&](sshash_streaming_report* s) { return sshash_streaming_runs_from_file(m_h, filename.c_str(), multiline, runs_callback::thunk, &cb, s); });
+    }
 
     /* WHICH k-mers of the dictionary the reads hold (sshash_streaming_cover; the bit layout is in include/sshash_amd.h): k-mer id i is
        bit i & 63 of cover[i >> 6]. `cover` is sized to cover_words() if it is not (new words zero) and ORed into. Returns the batch's

@@ -110,6 +110,7 @@ _lib: Optional[C.CDLL] = None
 
 # sshash_per_read_fn: (ctx, first_read, n, rows) -> 0 to go on
 _PerReadFn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p)
+_ReadRunsFn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p)  # sshash_read_runs_fn: (ctx, first_read, n, run_offsets, runs)
 # sshash_read_sum (include/sshash_amd.h): a read's row of streaming_sums
 READ_SUM_DTYPE = np.dtype([("sum", "<u8"), ("positive_kmers", "<u8")])
 # sshash_read_class: a read's row of streaming_classes, finished by class_best
@@ -167,6 +168,7 @@ _SIGNATURES = {
     "sshash_streaming_query_from_file_per_read": (C.c_int, [_P, C.c_char_p, C.c_int, _PerReadFn, _P, C.POINTER(_Report)]),
     "sshash_streaming_runs_device": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, C.c_uint64, _P, _P, C.c_uint64, _P, _P]),
     "sshash_streaming_runs": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, C.c_uint64, C.POINTER(_Report)]),
+    "sshash_streaming_runs_from_file": (C.c_int, [_P, C.c_char_p, C.c_int, _ReadRunsFn, _P, C.POINTER(_Report)]),
     "sshash_cover_words": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "sshash_streaming_cover_device": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, C.c_uint64, _P, _P, _P]),
     "sshash_streaming_cover": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.POINTER(_Report)]),
@@ -813,6 +815,45 @@ class Dictionary:
         _check(_load().sshash_streaming_runs_device(self._h, int(device), C.c_void_p(d_bases), C.c_void_p(d_read_offsets), int(num_reads),
                                                     int(total_bases), C.c_void_p(d_run_offsets), C.c_void_p(d_runs), int(runs_capacity),
                                                     C.c_void_p(d_report), C.c_void_p(stream)))
+
+    def streaming_runs_from_file(self, filename: str, multiline: bool = False,
+                                 per_batch: Optional[Callable[[int, np.ndarray, np.ndarray], Optional[int]]] = None):
+        """A query file answered like streaming_runs -- contigs of a multiline FASTA onto the unitigs, without loading the file first.
+        per_batch(first_read, run_offsets, runs) is called for one batch of the file after the other, in file order: run_offsets has
+        n + 1 uint64, [0] = 0, LOCAL to the batch -- the runs of record first_read + i of the file are runs[run_offsets[i]:
+        run_offsets[i + 1]], a RUN_DTYPE array; every record has an entry, one shorter than k an empty range. A return value other
+        than None / 0 stops the query (SSHashError), an exception raised by the callable stops it too and is raised again here.
+        per_batch=None: -> (run_offsets, runs, StreamingQueryReport) of the whole file, stitched; otherwise -> StreamingQueryReport."""
+        r = _Report()
+        raised, kept = [], []
+
+        def hand_over(_ctx, first_read, n, run_offsets, runs):
+            try:
+                offsets = _owned(run_offsets, C.c_uint64, (int(n) + 1,))
+                total = int(offsets[-1])
+                block = _owned(runs, C.c_uint8, (total * RUN_DTYPE.itemsize,)).view(RUN_DTYPE) if total else np.zeros(0, dtype=RUN_DTYPE)
+                if per_batch is None:
+                    kept.append((offsets, block))
+                    return 0
+                stop = per_batch(int(first_read), offsets, block)
+                return int(stop) if stop else 0
+            except BaseException as e:  # (must not travel through the C frames)
+                raised.append(e)
+                return -1
+
+        status = _load().sshash_streaming_runs_from_file(self._h, os.fsencode(filename), 1 if multiline else 0, _ReadRunsFn(hand_over), None,
+                                                         C.byref(r))
+        if raised:
+            raise raised[0]
+        _check(status)
+        if per_batch is not None:
+            return self._report(r)
+        stitched, base = [np.zeros(1, dtype=np.uint64)], 0
+        for offsets, _ in kept:
+            stitched.append(offsets[1:] + np.uint64(base))
+            base += int(offsets[-1])
+        runs = np.concatenate([block for _, block in kept]) if kept else np.zeros(0, dtype=RUN_DTYPE)
+        return np.concatenate(stitched), runs, self._report(r)
 
     # ---- streaming cover: which k-mers of the dictionary a read set holds ---------------------------
     def cover_words(self) -> int:

@@ -606,6 +606,27 @@ sshash_status sshash_streaming_runs(const sshash_dict* d, const char* bases, con
     });
 }
 
+sshash_status sshash_streaming_runs_from_file(const sshash_dict* d, const char* filename, int multiline, sshash_read_runs_fn fn, void* ctx,
+                                              sshash_streaming_report* report) {
+    if (!d || !filename || !fn) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    const report_out rep(report);
+    return guarded([&] {
+        with_query_file(d, filename, multiline, true, [&](read_stream& in) {
+            streaming_report total;
+            uint64_t first_read = 0;
+            std::vector<uint64_t> run_offsets, records;  // (a batch's, local to it: one counting pass sizes the records, the engine hands both back)
+            for_each_batch(in, [&](read_batch const& batch) {
+                const uint64_t n = batch.num_reads();
+                if (n == 0) return;
+                rep.fill(total += d->eng->streaming_runs_host(batch.bases.data(), batch.offsets.data(), n, run_offsets, records));
+                const int stop = fn(ctx, first_read, n, run_offsets.data(), reinterpret_cast<const sshash_streaming_run*>(records.data()));
+                if (stop) throw error(error_kind::argument, "the per-read callback returned " + std::to_string(stop));
+                first_read += n;
+            });
+        });
+    });
+}
+
 sshash_status sshash_cover_words(const sshash_dict* d, uint64_t* words) {
     if (!d || !words) return fail(SSHASH_ERR_ARGUMENT, "null argument");
     *words = (d->idx->num_kmers + 63) / 64;

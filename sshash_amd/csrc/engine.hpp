@@ -249,13 +249,20 @@ public:
     /* The maximal runs of every read (sshash_streaming_runs[_device] in include/sshash_amd.h): a run is a search and the extensions
        behind it. Device buffers, asynchronous, always the run kernel: count -> scan -> write; `d_run_offsets` (n_reads + 1 words) is
        overwritten, record i is written iff i < runs_capacity, `d_report` (nullable) is accumulated into. Every read below 2^31
-       bases (a record's read_pos and length are 31 bits wide; the host call checks, this one does not). */
+       bases (a record's read_pos and length are 31 bits wide; the host call checks, this one does not). `segment_kmers` as above: over
+       segments the runs that span seams are merged in place, the offsets and the records are those of the whole reads. */
     void streaming_runs_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
-                               uint64_t* d_run_offsets, void* d_runs, uint64_t runs_capacity, uint64_t* d_report, void* stream) const;
-    /* Host buffers, over all resident replicas; a piece that holds a read above 2^16 bases takes the position-parallel pipeline and a
-       compaction behind it, which give the same records. Throws at a read of 2^31 bases or more. Returns the totals. */
+                               uint64_t* d_run_offsets, void* d_runs, uint64_t runs_capacity, uint64_t* d_report, void* stream,
+                               uint64_t segment_kmers = SEGMENTS_AS_SET) const;
+    /* Host buffers, over all resident replicas; a piece that holds a long read takes the run kernel over segments (set_read_segments;
+       off: above 2^16 bases the position-parallel pipeline and a compaction behind it), which give the same records. Throws at a read
+       of 2^31 bases or more. Returns the totals. */
     streaming_report streaming_runs_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* run_offsets, void* runs,
                                          uint64_t runs_capacity) const;
+    /* The same with every record, however many there are: `run_offsets` becomes n_reads + 1 words, `records` four words a record --
+       one counting pass for a caller that cannot size its array before (the file call). */
+    streaming_report streaming_runs_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, std::vector<uint64_t>& run_offsets,
+                                         std::vector<uint64_t>& records) const;
 
     /* WHICH k-mers of the dictionary the reads hold (sshash_streaming_cover[_device] in include/sshash_amd.h): bit i & 63 of word i >> 6
        of `d_cover` (ceil(num_kmers / 64) words) for k-mer id i, ORed into. Device buffers, asynchronous, always the run kernel, its cover

@@ -65,4 +65,32 @@ inline segment_layout segment_scratch(uint64_t n_reads, uint64_t total_bases, ui
     return L;
 }
 
+/* What the run RECORDS over a segment table need besides it, in 8-byte words from their first, for a table of `bound` entries: the
+   runs of every segment, scanned in place into E -- the final index of the first record that starts in the segment -- (`bound` + 1 words,
+   the last the number of records); right behind them, where the record form of the run kernel finds them from E and the number of
+   entries alone, `cont` -- 32 bits a segment: the length of its first run when that continues the run of the segment before -- and the seam
+   flags, a byte a segment; the tile sums of the scan. `words` is the size of it all; 0 when that does not fit 2^61 words (the caller
+   refuses): a bound that segment_bound saturated lands there, nothing wraps. */
+struct segment_runs_layout {
+    uint64_t counts, cont, joined, sums, words;
+};
+
+constexpr uint64_t segment_runs_cont_words(uint64_t bound) { return bound / 2 + (bound & 1); }  // (no bound + 1: that sum may wrap)
+
+inline segment_runs_layout segment_runs_scratch(uint64_t bound, uint64_t scan_tile) {
+    segment_runs_layout R{};
+    if (bound >= (uint64_t(1) << 56) || scan_tile == 0) return R;  // (words = 0)
+    uint64_t at = 0;
+    R.counts = at, at += bound + 1;
+    R.cont = at, at += segment_runs_cont_words(bound);
+    R.joined = at, at += (bound + 7) / 8;
+    R.sums = at, at += (bound + 1 + scan_tile - 1) / scan_tile;
+    R.words = at;
+    return R;
+}
+
+/* A record of 32 bytes as eight words of 32 bits: the one that holds the run's length, the strand in its bit 31 (include/sshash_amd.h:
+   sshash_streaming_run.num_kmers). A run that goes on over a seam gets the rest of its length added there. */
+constexpr uint32_t RUN_RECORD_LENGTH_WORD = 7;
+
 }  // namespace sshash_amd

@@ -332,10 +332,16 @@ __device__ __forceinline__ void row_flush(uint64_t* __restrict__ row, bool parti
                          form's two 16-byte stores (run_record_write), plain, no atomics -- when the run is LONGER; runs come in the
                          order of their place in the read, so the first of equals stays. The hit's string travels across the turn as
                          in the record form, the read's index as in the counting form. Never over segments: a longest run is not
-                         additive. One launch. */
+                         additive. One launch.
+     STREAM_RUN_RECORDS_SEGMENTS  the record form over a segment table ("the run RECORDS over segments" below): the lane that takes
+                         segment g starts its cursor at sink.run_offsets[g] -- here E[g], the final index of the first record that
+                         STARTS in the segment --; the first run of a segment whose seam is joined is the tail of a record that a
+                         segment before it stores: not stored, its length to cont[g] for the merge; every other run is a record,
+                         its read_pos counted from the begin of the READ (sink.read_of, and the reads' offsets in the word of
+                         sink.values_prefix). A form of its own, not a branch of the record form: that one's code stays what it was. */
 enum : int {
     STREAM_TOTALS = 0, STREAM_ROWS = 1, STREAM_RUN_COUNTS = 2, STREAM_RUN_RECORDS = 3, STREAM_COVER = 4, STREAM_DEPTH = 5, STREAM_SUMS = 6,
-    STREAM_CLASSES = 7, STREAM_BEST_RUN = 8
+    STREAM_CLASSES = 7, STREAM_BEST_RUN = 8, STREAM_RUN_RECORDS_SEGMENTS = 9
 };
 
 /* the record (sshash_streaming_run, 32 bytes) of the run of `n` k-mers of read `r` whose first (in read order) starts at base `at` of the
@@ -355,6 +361,21 @@ __device__ __forceinline__ void run_record_store(dict_view const& d, run_sink co
                                                  uint64_t cursor, uint64_t at, uint64_t off, uint32_t sid, int ori, uint64_t n) {
     if (cursor >= sink.capacity || cursor >= sink.run_offsets[r + 1]) return;
     run_record_write(d, sink.records, cursor, begins, r, at, off, sid, ori, n);
+}
+
+/* (the record form over segments) where the lanes find what lies behind E in the scratch (segments.hpp: segment_runs_scratch), from E
+   and the number of entries alone: the sink is as large as it was */
+__device__ __forceinline__ uint32_t* seg_runs_cont(run_sink const& sink, uint64_t bound) { return reinterpret_cast<uint32_t*>(sink.run_offsets + bound + 1); }
+__device__ __forceinline__ const uint8_t* seg_runs_joined(run_sink const& sink, uint64_t bound) {
+    return reinterpret_cast<const uint8_t*>(sink.run_offsets + bound + 1 + segment_runs_cont_words(bound));
+}
+
+/* (the record form over segments) the run of segment `g` to place `cursor`, under the guards of run_record_store -- the caller's room, and
+   the place where the records that start in the next segment begin --, its position counted from the begin of its read */
+__device__ __forceinline__ void seg_record_store(dict_view const& d, run_sink const& sink, uint64_t g, uint64_t cursor, uint64_t at, uint64_t off,
+                                                 uint32_t sid, int ori, uint64_t n) {
+    if (cursor >= sink.capacity || cursor >= sink.run_offsets[g + 1]) return;
+    run_record_write(d, sink.records, cursor, sink.values_prefix /* the reads' offsets */, sink.read_of[g], at, off, sid, ori, n);
 }
 
 /* (the best-run form) the same run over the record of its read, record `r` of sink.records, when it is longer than the longest stored for
@@ -445,7 +466,8 @@ __global__ void __launch_bounds__(256, SSHASH_STREAM_WAVES)
 streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, const uint64_t* __restrict__ packed,
                      const uint64_t* __restrict__ okay, const uint64_t* __restrict__ begins, const uint64_t* __restrict__ ends, const uint64_t n_reads,
                      const uint64_t reads_per_wave, const uint32_t move_out_every, uint64_t* __restrict__ report, const run_sink sink) {
-    constexpr bool PER_READ = MODE == STREAM_ROWS, COUNT_RUNS = MODE == STREAM_RUN_COUNTS, RECORDS = MODE == STREAM_RUN_RECORDS, COVER = MODE == STREAM_COVER,
+    constexpr bool SEG_RECORDS = MODE == STREAM_RUN_RECORDS_SEGMENTS;  // (RECORDS as well: what the two forms share says RECORDS)
+    constexpr bool PER_READ = MODE == STREAM_ROWS, COUNT_RUNS = MODE == STREAM_RUN_COUNTS, RECORDS = MODE == STREAM_RUN_RECORDS || SEG_RECORDS, COVER = MODE == STREAM_COVER,
                    DEPTH = MODE == STREAM_DEPTH, SUMS = MODE == STREAM_SUMS, CLASSES = MODE == STREAM_CLASSES, BEST_RUN = MODE == STREAM_BEST_RUN;
     constexpr bool ROW_INDEX = SUMS || CLASSES;  // the lane keeps the index of its read's row, counted from row_first
     /* (SUMS) when a measured run's two words of P are added to its row: at the end of the turn -- by then the seed's own loads have been
@@ -511,6 +533,7 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
     uint32_t n_runs = 0, hit_sid = 0;
     uint64_t cursor = 0;
     uint32_t best_len = 0;  // (BEST_RUN) the length of the longest run stored for the lane's read so far
+    bool seam_open = false;  // (SEG_RECORDS) the lane's segment begins inside a run, and that run -- its first -- is still to come
     const uint64_t wave_first = wave * reads_per_wave;
     /* (SUMS) the row of the wave's first read: the read itself, or -- segments -- the read of that segment (an empty entry of the table,
        behind the last segment: then so are all of the wave's, and none of them has a k-mer to add) */
@@ -584,7 +607,15 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                 late_row = my_row;
             }
             if constexpr (BEST_RUN) best_run_store(d, sink, begins, wave_first + my_row, best_len, cur - 1, off, hit_sid, ori, run + 1);  // (beside the counting below, not instead of it)
-            if constexpr (RECORDS) {  // (the hit lies a base before cur)
+            if constexpr (SEG_RECORDS) {
+                if (seam_open) {  // (the tail of a record stored by a segment before: its length for the merge, no record, no place taken)
+                    seg_runs_cont(sink, n_reads)[wave_first + my_row] = uint32_t(run + 1);
+                    seam_open = false;
+                } else {
+                    seg_record_store(d, sink, wave_first + my_row, cursor, cur - 1, off, hit_sid, ori, run + 1);
+                    ++cursor;
+                }
+            } else if constexpr (RECORDS) {  // (the hit lies a base before cur)
                 run_record_store(d, sink, begins, wave_first + my_row, cursor, cur - 1, off, hit_sid, ori, run + 1);
                 ++cursor;
             } else if (run >> 15) {  // (past what the lane's 32-bit counter may take in one turn: 2^16 turns lie between two move-outs)
@@ -645,6 +676,10 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                 } else if constexpr (RECORDS) {
                     my_row = uint32_t(r - wave_first);
                     cursor = sink.run_offsets[r];
+                    if constexpr (SEG_RECORDS) {  // (every entry of the table: an empty one is joined to nothing)
+                        seam_open = seg_runs_joined(sink, n_reads)[r] != 0;
+                        seg_runs_cont(sink, n_reads)[r] = 0;  // (a joined segment's first run stores its length over this, the same lane, later)
+                    }
                 } else if constexpr (BEST_RUN) {
                     if (rd_end - cur >= k) {  // (a read without a k-mer has no run: its record keeps the caller's zeros)
                         atomicAdd(wave_moved_out + 4, (unsigned long long)(rd_end - cur - k + 1));
@@ -874,7 +909,17 @@ streaming_run_kernel(const dict_view d, const skew_part_dev* __restrict__ skew, 
                 neg_unknown_mini = false;
                 pending = cur + 1 + k <= valid_end;  // (otherwise nothing can extend it)
                 if constexpr (COUNT_RUNS) ++n_runs;
-                if constexpr (RECORDS) {
+                if constexpr (SEG_RECORDS) {
+                    if (!pending) {  // a run of one
+                        if (seam_open) {
+                            seg_runs_cont(sink, n_reads)[wave_first + my_row] = 1;
+                            seam_open = false;
+                        } else {
+                            seg_record_store(d, sink, wave_first + my_row, cursor, cur, off, hit_sid, ori, 1);
+                            ++cursor;
+                        }
+                    }
+                } else if constexpr (RECORDS) {
                     if (!pending) {  // a run of one
                         run_record_store(d, sink, begins, wave_first + my_row, cursor, cur, off, hit_sid, ori, 1);
                         ++cursor;
@@ -1249,6 +1294,51 @@ stream_segment_rows_kernel(const uint64_t* __restrict__ seg_rows, const uint64_t
         if (v[c]) atomicAdd(row + c, (unsigned long long)v[c]);
 }
 
+/* ---- the run RECORDS over segments: a merge that moves no record ----
+   A run that goes on over a seam arrives from the run kernel as the last run of one segment and the first of the next. joined[g] says
+   exactly that of the seam in front of segment g, so the first run of such a segment is no record of its own, and of the c[g] runs the
+   counting form finds in segment g, c'[g] = c[g] - joined[g] are records that START there. Their exclusive scan E puts every record at
+   its final place -- reads in order, a read's segments in order, a segment's runs in order: the canonical layout --, and the CSR offsets
+   of the reads are E at their first segments. The record form over segments stores every run that starts in its segment at E[g] and
+   on, and hands the length of a joined first run to cont[g]; the merge adds that to the length of record E[g] - 1: the last record that
+   starts before segment g, which is the run that the seam continues -- also through a chain of segments that lie wholly inside one run,
+   because those start no record (c' = 0) and so share one E. The length's bit 31, the strand, is safe: the lengths of one run add up to
+   fewer than 2^31 k-mers (the precondition on a read's length). The record's store and the adds are in different launches of one
+   stream, and integer adds commute: the bytes are those of the uncut call. ---- */
+__global__ void __launch_bounds__(256)
+stream_segment_run_starts_kernel(uint64_t* __restrict__ counts /* bound + 1 */, const uint8_t* __restrict__ joined, const uint64_t* __restrict__ n_segments,
+                                 const uint64_t bound) {
+    const uint64_t g = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (g > bound) return;
+    uint64_t starts = 0;
+    if (g < bound && g < *n_segments) {
+        const uint64_t c = counts[g], j = joined[g];
+        starts = c > j ? c - j : 0;  // (a joined segment has a run: its first k-mer is positive)
+    }
+    counts[g] = starts;  // (the entries behind the last segment, and the word the scan turns into the total: zero)
+}
+
+/* the reads' CSR offsets out of E: read r's records begin where those of its first segment do; word n_reads -- first[n_reads] is the
+   number of segments -- the number of records */
+__global__ void __launch_bounds__(256)
+stream_segment_run_offsets_kernel(const uint64_t* __restrict__ E, const uint64_t* __restrict__ first /* n_reads + 1 */, const uint64_t n_reads,
+                                  uint64_t* __restrict__ run_offsets) {
+    const uint64_t r = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (r <= n_reads) run_offsets[r] = E[first[r]];
+}
+
+/* one lane a segment: the length of a joined first run to the record it continues, unless the caller has no room for that record */
+__global__ void __launch_bounds__(256)
+stream_segment_run_merge_kernel(const uint64_t* __restrict__ E, const uint8_t* __restrict__ joined, const uint32_t* __restrict__ cont,
+                                const uint64_t* __restrict__ n_segments, const uint64_t bound, void* records, const uint64_t capacity) {
+    const uint64_t g = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (g >= bound || g >= *n_segments || !joined[g]) return;
+    const uint64_t at = E[g];
+    if (at == 0 || at - 1 >= capacity) return;  // (at > 0: the run that is continued started before this segment)
+    uint32_t* const length = static_cast<uint32_t*>(records) + 8 * (at - 1) + RUN_RECORD_LENGTH_WORD;
+    (void)__hip_atomic_fetch_add(length, cont[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 template <int W, bool CANON>
 void launch_seams(device_replica const* rep, dict_view const& d, hipStream_t s, uint64_t const* packed, uint64_t const* okay, uint64_t const* seg_begin,
                   uint64_t const* seg_read, uint64_t const* n_segments, uint64_t bound, uint8_t* joined, uint64_t* report) {
@@ -1293,14 +1383,20 @@ enum : int { RUNS_COUNT = 1, RUNS_WRITE = 2, RUNS_COVER = 4, RUNS_DEPTH = 8, RUN
 void launch_streaming_runs(device_replica const* rep, char const* bases, uint64_t const* offsets, uint64_t n_reads, uint64_t total_bases, uint64_t* report,
                            hipStream_t s, uint64_t* rows = nullptr /* per read: n_reads x 6 words; `report` may then be null */,
                            run_sink sink = run_sink{nullptr, nullptr, 0}, int run_phases = 0,
-                           uint64_t S = 0 /* the reads cut into segments of S k-mers (totals, rows, cover, depth, sums, classes; never the run records) */) {
+                           uint64_t S = 0 /* the reads cut into segments of S k-mers (totals, rows, run records, cover, depth, sums, classes; never the best run) */) {
     dict_view const& d = rep->view;
     const bool segmented = S != 0;
-    if (segmented && (run_phases & (RUNS_COUNT | RUNS_WRITE | RUNS_BEST_RUN))) throw error(error_kind::internal, "run records are not segmented");
+    if (segmented && (run_phases & RUNS_BEST_RUN)) throw error(error_kind::internal, "the best run is not segmented");
+    const bool segmented_records = segmented && (run_phases & (RUNS_COUNT | RUNS_WRITE)) != 0;
     segment_layout L{};
+    segment_runs_layout R{};
     if (segmented) {
         L = segment_scratch(n_reads, total_bases, S, SCAN_TILE, rows != nullptr);
         if (L.words == 0 || (L.bound + 255) / 256 >> 31) throw error(error_kind::argument, "too many segments for one call");
+        if (segmented_records) {
+            R = segment_runs_scratch(L.bound, SCAN_TILE);
+            if (R.words == 0) throw error(error_kind::argument, "too many segments for one call");
+        }
     }
     /* two bits and a validity bit a base, in words of 32 and 64 bases; three words of slack behind the last base (a seed and a
        run read up to two words past their first) */
@@ -1310,10 +1406,11 @@ void launch_streaming_runs(device_replica const* rep, char const* bases, uint64_
     const uint64_t runs_bytes = run_phases ? (scan_tiles(n_reads + 1) + 6) * 8 : 0;  // (the scan's tile sums; six counters nobody asked for)
     uint64_t* const caller_report = report;
     std::lock_guard<std::mutex> sequence(rep->launch_mutex);
-    uint64_t* packed = static_cast<uint64_t*>(rep->read_scratch_for(s, packed_bytes + okay_bytes + runs_bytes + L.words * 8));
+    uint64_t* packed = static_cast<uint64_t*>(rep->read_scratch_for(s, packed_bytes + okay_bytes + runs_bytes + (L.words + R.words) * 8));
     uint64_t* okay = packed + packed_bytes / 8;
     uint64_t* scan_sums = okay + okay_bytes / 8;
     uint64_t* const seg = scan_sums + runs_bytes / 8;  // (segmented) the table, the segments' rows, the seam flags: segments.hpp
+    uint64_t* const seg_runs = seg + L.words;           // (the run records over segments) segments.hpp: segment_runs_scratch
     if (total_bases) {
         const uint64_t lanes = (total_bases + 7) / 8;
         hipLaunchKernelGGL(stream_pack_kernel, dim3(uint32_t((lanes + 255) / 256)), dim3(256), 0, s, bases, total_bases,
@@ -1376,6 +1473,31 @@ void launch_streaming_runs(device_replica const* rep, char const* bases, uint64_
         else if (one_launch == RUNS_CLASSES) run(run_form<STREAM_CLASSES>{}, totals());
         else run(run_form<STREAM_BEST_RUN>{}, totals());
         if (segmented && caller_report) seams(nullptr, caller_report);  // (nobody reads the six counters: no seam is looked at; the best run is never segmented)
+    } else if (segmented_records) {
+        /* ("the run RECORDS over segments" above) Either phase needs the segments' counts, the seams and E: a call that only writes makes
+           them again -- the scratch is this call's alone only while it holds the launch mutex, so nothing is kept from the counting call. */
+        uint64_t* const E = seg_runs + R.counts;
+        uint8_t* const joined = reinterpret_cast<uint8_t*>(seg_runs + R.joined);
+        uint64_t const* const n_segments = seg + L.first + n_whole_reads;
+        const uint32_t entry_blocks = uint32_t((L.bound + 256) / 256);  // (bound + 1 lanes)
+        const run_sink counting{E, nullptr, 0};
+        launch_run_kernel<STREAM_RUN_COUNTS>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, totals(), counting);
+        seams(joined, (run_phases & RUNS_COUNT) ? caller_report : nullptr);
+        hipLaunchKernelGGL(stream_segment_run_starts_kernel, dim3(entry_blocks), dim3(256), 0, s, E, joined, n_segments, L.bound);
+        HIP_CHECK(hipGetLastError());
+        exclusive_scan_u64(E, L.bound + 1, seg_runs + R.sums, s);
+        if (run_phases & RUNS_COUNT) {
+            hipLaunchKernelGGL(stream_segment_run_offsets_kernel, dim3(uint32_t((n_whole_reads + 256) / 256)), dim3(256), 0, s, E, seg + L.first, n_whole_reads,
+                               sink.run_offsets);
+            HIP_CHECK(hipGetLastError());
+        }
+        if (run_phases & RUNS_WRITE) {
+            const run_sink writing{E, sink.records, sink.capacity, offsets /* the reads' begins, in the word of values_prefix */, seg + L.read};
+            launch_run_kernel<STREAM_RUN_RECORDS_SEGMENTS>(rep, d, grid, block, s, packed, okay, begins, ends, n_reads, reads_per_wave, move_out_every, nullptr, writing);
+            hipLaunchKernelGGL(stream_segment_run_merge_kernel, dim3(uint32_t((L.bound + 255) / 256)), dim3(256), 0, s, E, joined,
+                               reinterpret_cast<uint32_t const*>(seg_runs + R.cont), n_segments, L.bound, sink.records, sink.capacity);
+            HIP_CHECK(hipGetLastError());
+        }
     } else if (run_phases) {
         if (run_phases & RUNS_COUNT) {
             run(run_form<STREAM_RUN_COUNTS>{}, totals());
@@ -1416,20 +1538,14 @@ uint64_t resolve_total_bases(uint64_t const* d_read_offsets, uint64_t n_reads, u
     return total_bases;
 }
 
-/* The passes of streaming_runs_device: `count` -- sink.run_offsets from the reads, `d_report` accumulated into --, `write` -- the records,
-   for run_offsets that hold the offsets of these very reads (streaming_runs_host counts, sizes a piece's records from the count and
-   writes). */
-void streaming_runs_passes(engine const& eng, int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
-                           run_sink const& sink, uint64_t* d_report, hipStream_t s, bool count, bool write) {
-    device_replica const* rep = eng.replica(device);
+/* The writing pass of streaming_runs_host for one piece, behind its counting call (streaming_runs_device without room for a record, from
+   which the piece's records were sized): the records, for sink.run_offsets that hold the offsets of these very reads. `S`: what the
+   counting call cut the reads into (0: whole reads). The counting call is what counts as a segmented launch. */
+void streaming_runs_write(engine const& eng, int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
+                          run_sink const& sink, hipStream_t s, uint64_t S) {
+    if (n_reads == 0 || total_bases == 0) return;  // no read, or empty reads only: no run
     device_guard guard(device);
-    total_bases = resolve_total_bases(d_read_offsets, n_reads, total_bases, s);
-    if (n_reads == 0 || total_bases == 0) {  // no read, or empty reads only: no run
-        if (count) HIP_CHECK(hipMemsetAsync(sink.run_offsets, 0, (n_reads + 1) * sizeof(uint64_t), s));
-        return;
-    }
-    const int phases = (count ? RUNS_COUNT : 0) | (write ? RUNS_WRITE : 0);
-    if (phases) launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, total_bases, d_report, s, nullptr, sink, phases);
+    launch_streaming_runs(eng.replica(device), d_bases, d_read_offsets, n_reads, total_bases, nullptr, s, nullptr, sink, RUNS_WRITE, S);
 }
 
 }  // namespace
@@ -1494,15 +1610,26 @@ void engine::streaming_query_per_read_device(int device, char const* d_bases, ui
     });
 }
 
-/* The runs of every read (sshash_streaming_runs_device): count -> scan -> write, always the run kernel. */
+/* The runs of every read (sshash_streaming_runs_device): count -> scan -> write, always the run kernel -- one lane a read, or
+   (segment_kmers) one lane a segment and the merge of the runs that span seams behind it: the same offsets, the same bytes. */
 void engine::streaming_runs_device(int device, char const* d_bases, uint64_t const* d_read_offsets, uint64_t n_reads, uint64_t total_bases,
-                                   uint64_t* d_run_offsets, void* d_runs, uint64_t runs_capacity, uint64_t* d_report, void* stream) const {
-    (void)replica(device);  // (not resident: that error first)
+                                   uint64_t* d_run_offsets, void* d_runs, uint64_t runs_capacity, uint64_t* d_report, void* stream,
+                                   uint64_t segment_kmers) const {
+    device_replica const* rep = replica(device);  // (not resident: that error first)
     if (n_reads == 0 && !d_run_offsets) return;
     if (!d_run_offsets) throw error(error_kind::argument, "run_offsets pointer is null");
     if (!d_runs && runs_capacity) throw error(error_kind::argument, "runs pointer is null");
-    streaming_runs_passes(*this, device, d_bases, d_read_offsets, n_reads, total_bases, run_sink{d_run_offsets, d_runs, runs_capacity}, d_report,
-                          hipStream_t(stream), true, runs_capacity != 0);
+    bool launched = false;
+    if (n_reads)
+        run_kernel_call(device, d_read_offsets, n_reads, total_bases, stream, segment_kmers, nullptr, 0, [&](hipStream_t s, uint64_t nb, uint64_t S) {
+            launched = true;
+            launch_streaming_runs(rep, d_bases, d_read_offsets, n_reads, nb, d_report, s, nullptr, run_sink{d_run_offsets, d_runs, runs_capacity},
+                                  RUNS_COUNT | (runs_capacity ? RUNS_WRITE : 0), S);
+        });
+    if (!launched) {  // no read, or empty reads only: no run
+        device_guard guard(device);
+        HIP_CHECK(hipMemsetAsync(d_run_offsets, 0, (n_reads + 1) * sizeof(uint64_t), hipStream_t(stream)));
+    }
 }
 
 /* Which k-mers of the dictionary the reads hold (sshash_streaming_cover_device): the cover form of the run kernel, one launch. */
@@ -2559,7 +2686,7 @@ piece_cuts cut_lane_pieces(uint64_t const* read_offsets, uint64_t n_reads, uint6
 }
 
 /* One lane walks one read: a read of megabases (a contig, a multiline FASTA record) would keep a single lane busy for minutes. Where the
-   reads are not cut into segments (SSHASH_SEGMENTS_OFF, a minimizer shard, the run records) a piece that holds such a read goes through
+   reads are not cut into segments (SSHASH_SEGMENTS_OFF, a minimizer shard, the best run) a piece that holds such a read goes through
    the position-parallel pipeline, which gives the same results. */
 bool holds_long_read(uint64_t const* offsets, uint64_t n_reads) {
     constexpr uint64_t LONG_READ_BASES = uint64_t(1) << 16;
@@ -2900,52 +3027,91 @@ static void piece_runs_by_ids(engine const& eng, staged_piece const& p, run_sink
 /* The runs of every read, host buffers (sshash_streaming_runs): pieces and lanes as above (run_piece_lanes). A piece's
    run_offsets are local to the piece and its record count is known only after its counting pass, so a lane counts, reads the count
    back, sizes the piece's device records from it and writes them; the pieces' records wait on the host until every piece's count is
-   known -- only then is a piece's place in the caller's array --, and are stitched in piece order, clipped at `runs_capacity`. */
-streaming_report engine::streaming_runs_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* run_offsets,
-                                             void* runs, uint64_t runs_capacity) const {
+   known -- only then is a piece's place in the caller's array --, and are stitched in piece order (runs_host_stitch).
+   A piece that holds a read of more than S k-mers (p.segments) takes both passes over segments; the writing pass makes the table, the
+   counts and E again (launch_streaming_runs): the scratch they lie in is the stream's, not the call's. With the segments off, a piece
+   that holds a read above 2^16 bases takes the per-k-mer pipeline as it always did. */
+namespace {
+struct host_runs {
+    streaming_report report;
+    piece_cuts pieces;
+    std::vector<std::vector<uint64_t>> piece_records;  // (four words a record)
+    std::vector<uint64_t> piece_total;
+};
+
+/* run_offsets: n_reads + 1 words, on return [r] for r >= 1 local to r's piece */
+host_runs runs_host_pieces(engine const& eng, char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* run_offsets, bool want_records) {
     constexpr uint64_t RECORD_BYTES = 32;
-    if (n_reads == 0) {
-        if (run_offsets) run_offsets[0] = 0;
-        return {};
-    }
     for (uint64_t r = 0; r < n_reads; ++r)
         if ((read_offsets[r + 1] - read_offsets[r]) >> 31) throw error(error_kind::argument, "a read of 2^31 bases or more: a run record could not hold its positions");
-    const piece_cuts pieces = cut_lane_pieces(read_offsets, n_reads);
-    const uint64_t num_pieces = pieces.count();
-    std::vector<std::vector<uint64_t>> piece_records(num_pieces);  // (four words a record)
-    std::vector<uint64_t> piece_total(num_pieces, 0);
-    const streaming_report report = run_piece_lanes(*this, bases, read_offsets, pieces, (pieces.max_reads + 1) * sizeof(uint64_t), [&](staged_piece const& p) {
+    host_runs out;
+    out.pieces = cut_lane_pieces(read_offsets, n_reads);
+    const uint64_t num_pieces = out.pieces.count();
+    out.piece_records.resize(num_pieces);
+    out.piece_total.assign(num_pieces, 0);
+    out.report = run_piece_lanes(eng, bases, read_offsets, out.pieces, (out.pieces.max_reads + 1) * sizeof(uint64_t), [&](staged_piece const& p) {
         uint64_t* d_counts = reinterpret_cast<uint64_t*>(p.d_extra);
         uint64_t const* counts = reinterpret_cast<uint64_t const*>(p.h_extra);
+        const bool by_ids = p.long_read && !p.segments;  // (a long read that is not cut into segments: the per-k-mer pipeline)
         if (p.nb == 0) HIP_CHECK(hipMemsetAsync(d_counts, 0, (p.n + 1) * sizeof(uint64_t), p.s));
-        else if (p.long_read) piece_runs_by_ids(*this, p, run_sink{d_counts, nullptr, 0}, p.d_report);  // (run records are never segmented: a long read's piece takes the per-k-mer pipeline)
-        else streaming_runs_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, d_counts, nullptr, 0, p.d_report, p.s);
+        else if (by_ids) piece_runs_by_ids(eng, p, run_sink{d_counts, nullptr, 0}, p.d_report);
+        else eng.streaming_runs_device(p.device, p.d_bases, p.d_offsets, p.n, p.nb, d_counts, nullptr, 0, p.d_report, p.s, p.segments);
         HIP_CHECK(hipMemcpyAsync(p.h_extra, d_counts, (p.n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, p.s));
         HIP_CHECK(hipStreamSynchronize(p.s));
         const uint64_t total = counts[p.n];
-        piece_total[p.index] = total;
+        out.piece_total[p.index] = total;
         for (uint64_t i = 1; i <= p.n; ++i) run_offsets[p.first + i] = counts[i];  // (local to the piece until the pieces are stitched)
-        if (runs_capacity && total) {
-            std::vector<uint64_t>& mine = piece_records[p.index];
+        if (want_records && total) {
+            std::vector<uint64_t>& mine = out.piece_records[p.index];
             mine.resize(total * (RECORD_BYTES / 8));
-            device_buffers records(replica(p.device), p.s);
+            device_buffers records(eng.replica(p.device), p.s);
             void* d_records = records.alloc<uint64_t>(total * (RECORD_BYTES / 8));
             const run_sink writing{d_counts, d_records, total};
-            if (p.long_read) piece_runs_by_ids(*this, p, writing, nullptr);
-            else streaming_runs_passes(*this, p.device, p.d_bases, p.d_offsets, p.n, p.nb, writing, nullptr, p.s, false, true);
+            if (by_ids) piece_runs_by_ids(eng, p, writing, nullptr);
+            else streaming_runs_write(eng, p.device, p.d_bases, p.d_offsets, p.n, p.nb, writing, p.s, p.segments);
             HIP_CHECK(hipMemcpyAsync(mine.data(), d_records, total * RECORD_BYTES, hipMemcpyDeviceToHost, p.s));
             HIP_CHECK(hipStreamSynchronize(p.s));
         }
     });
+    return out;
+}
+
+/* the pieces' offsets made global and their records put behind one another, clipped at `runs_capacity` */
+void runs_host_stitch(host_runs const& got, uint64_t* run_offsets, void* runs, uint64_t runs_capacity) {
+    constexpr uint64_t RECORD_BYTES = 32;
     run_offsets[0] = 0;
     uint64_t base = 0;
-    for (uint64_t piece = 0; piece < num_pieces; ++piece) {
-        for (uint64_t r = pieces.cuts[piece] + 1; r <= pieces.cuts[piece + 1]; ++r) run_offsets[r] += base;
-        if (base < runs_capacity && piece_total[piece])
-            std::memcpy(static_cast<char*>(runs) + base * RECORD_BYTES, piece_records[piece].data(), std::min(piece_total[piece], runs_capacity - base) * RECORD_BYTES);
-        base += piece_total[piece];
+    for (uint64_t piece = 0; piece < got.pieces.count(); ++piece) {
+        for (uint64_t r = got.pieces.cuts[piece] + 1; r <= got.pieces.cuts[piece + 1]; ++r) run_offsets[r] += base;
+        if (base < runs_capacity && got.piece_total[piece])
+            std::memcpy(static_cast<char*>(runs) + base * RECORD_BYTES, got.piece_records[piece].data(), std::min(got.piece_total[piece], runs_capacity - base) * RECORD_BYTES);
+        base += got.piece_total[piece];
     }
-    return report;
+}
+}  // namespace
+
+streaming_report engine::streaming_runs_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, uint64_t* run_offsets,
+                                             void* runs, uint64_t runs_capacity) const {
+    if (n_reads == 0) {
+        if (run_offsets) run_offsets[0] = 0;
+        return {};
+    }
+    const host_runs got = runs_host_pieces(*this, bases, read_offsets, n_reads, run_offsets, runs_capacity != 0);
+    runs_host_stitch(got, run_offsets, runs, runs_capacity);
+    return got.report;
+}
+
+streaming_report engine::streaming_runs_host(char const* bases, uint64_t const* read_offsets, uint64_t n_reads, std::vector<uint64_t>& run_offsets,
+                                             std::vector<uint64_t>& records) const {
+    run_offsets.assign(n_reads + 1, 0);
+    records.clear();
+    if (n_reads == 0) return {};
+    const host_runs got = runs_host_pieces(*this, bases, read_offsets, n_reads, run_offsets.data(), true);
+    uint64_t total = 0;
+    for (uint64_t t : got.piece_total) total += t;
+    records.resize(total * 4);
+    runs_host_stitch(got, run_offsets.data(), records.data(), total);
+    return got.report;
 }
 
 /* what every route of the best run asks of the dictionary before it looks at a read: a resident replica, and no minimizer shard */
