@@ -234,6 +234,57 @@ sshash_status sshash_string_offsets(const sshash_dict* d, const uint64_t* string
  * forward neighbours of the string's last k-mer and the backward neighbours of its first one, same layout. */
 sshash_status sshash_string_neighbours(const sshash_dict* d, const uint64_t* string_ids, uint64_t n,
                                        int check_reverse_complement, const sshash_results* out);
+/* The same on the device, asynchronous on hip_stream: string_ids is a device pointer, or NULL for the strings first_string + i
+ * (first_string + n > num_strings is then SSHASH_ERR_ARGUMENT). Same layout -- every array of `out` holds 8*n entries, entry 8*i + c
+ * the forward neighbour "ACTG"[c] of the string's last k-mer, entry 8*i + 4 + c the backward neighbour of its first -- and the same
+ * pointer rules as sshash_neighbours_packed_device; any field may be asked for. One kernel decodes both end k-mers of every string
+ * out of the replica and expands them, the batched lookup follows. A string id >= num_strings in string_ids gives an all-ones
+ * query, as sshash_access_packed_device writes for an id past the end: eight not-found results (unless the dictionary holds the
+ * k-mer of k G's, which those words spell). */
+sshash_status sshash_string_neighbours_device(const sshash_dict* d, int device, const uint64_t* string_ids, uint64_t first_string, uint64_t n,
+                                              int check_reverse_complement, const sshash_results* out, void* hip_stream);
+
+/* ---- The dictionary as a graph: the LINKS between its strings, as CSR.
+ * One record per found neighbour among the eight of string_neighbours(s): the records of string begin_string + i are
+ * links[link_offsets[i] .. link_offsets[i + 1]), in increasing flags & 7, at most 8 per string. The layout is canonical: two calls
+ * over the same range give byte-identical arrays.
+ * Capacity, exactly as sshash_streaming_runs_device: link_offsets (end - begin + 1 words, [0] = 0) is always complete and exact,
+ * record i is written iff i < links_capacity, nothing at or beyond links + links_capacity is touched; links == NULL with capacity 0 is
+ * the counting call.
+ * Orientation (for a GFA): from_sign is '+' iff bit 2 is clear; to_sign is '+' iff (bit 3 clear) == (bit 2 clear). A link is END-TO-END --
+ * it joins two string ends, an L line -- iff
+ *     bit 2 clear and (bit 3 clear and bit 4 set, or bit 3 set and bit 5 set), or
+ *     bit 2 set   and (bit 3 clear and bit 5 set, or bit 3 set and bit 4 set);
+ * any other link lands inside to_string (a junction inside a stitched string).
+ * SSHASH_ERR_ARGUMENT, before anything runs: begin > end, end > num_strings, link_offsets NULL, links NULL with capacity > 0, or a
+ * minimizer shard (num_shards > 1: it answers only the k-mers it owns, as sshash_check_device). Table-shard replicas work. The device
+ * form is asynchronous on hip_stream with no host synchronisation: rounds of at most 2^22 strings -- the ends' neighbours, an
+ * ids-only lookup, a count per string --, a prefix sum over link_offsets and, with capacity > 0, the rounds again with the lookup of
+ * the record's fields and a scatter; scratch of one round out of the replica's stream-ordered pool. links: 16-byte aligned.
+ * The host form takes host arrays and runs on the first resident replica. */
+typedef struct sshash_string_link {
+    uint64_t from_string; /* the string whose end the link leaves */
+    uint64_t to_string;   /* lookup_result::string_id of the neighbour k-mer */
+    uint64_t to_kmer_id;  /* lookup_result::kmer_id of the neighbour k-mer */
+    uint32_t flags;       /* bits 0-1: the base's 2-bit code c; bit 2: leaves the string's START (backward neighbour; clear: its END);
+                             bit 3: neighbour found as reverse complement (orientation -1); bit 4: it is the FIRST k-mer of to_string;
+                             bit 5: it is the LAST k-mer of to_string (both set: a string of one k-mer) */
+    uint32_t reserved;    /* 0 */
+} sshash_string_link;     /* 32 bytes */
+sshash_status sshash_string_links_device(const sshash_dict* d, int device, uint64_t begin_string, uint64_t end_string, int check_reverse_complement,
+                                         uint64_t* link_offsets, sshash_string_link* links, uint64_t links_capacity, void* hip_stream);
+sshash_status sshash_string_links(const sshash_dict* d, uint64_t begin_string, uint64_t end_string, int check_reverse_complement,
+                                  uint64_t* link_offsets, sshash_string_link* links, uint64_t links_capacity);
+
+/* ---- The ADJACENCY of every k-mer of the ids [begin_kmer_id, end_kmer_id): bit c of masks[i - begin] is set iff the forward neighbour
+ * "ACTG"[c] of k-mer i is in the dictionary, bit 4 + c the same for its backward neighbour (a k-mer that is its own neighbour
+ * counts: the lookup finds it). This tells a junction inside a stitched string from a non-branching position, which no per-string
+ * call can. masks: end - begin bytes. Range errors as sshash_iterate_packed_device; SSHASH_ERR_ARGUMENT on a minimizer shard. The
+ * device form is asynchronous: rounds of at most 2^22 k-mers -- the iterator, the 8 neighbours, an ids-only lookup, 8 ids folded
+ * into a byte. The host form takes a host array and runs on the first resident replica. */
+sshash_status sshash_kmer_adjacency_device(const sshash_dict* d, int device, uint64_t begin_kmer_id, uint64_t end_kmer_id, int check_reverse_complement,
+                                           uint8_t* masks, void* hip_stream);
+sshash_status sshash_kmer_adjacency(const sshash_dict* d, uint64_t begin_kmer_id, uint64_t end_kmer_id, int check_reverse_complement, uint8_t* masks);
 
 /* ---- dictionary::streaming_query_from_file (include/dictionary.hpp:81-82, src/query.cpp:118-175)
  *      and streaming_query<Dict,canonical> over reads in memory (include/streaming_query.hpp) --

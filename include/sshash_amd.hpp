@@ -236,6 +236,22 @@ public:
         return ids;
     }
 
+    /* The dictionary as a graph (sshash_string_links, sshash_kmer_adjacency in sshash_amd.h): the links of the strings [begin, end) as
+       CSR -- the records of string begin + i are second[first[i] .. first[i + 1]) -- by a counting call and the exact one; and which
+       of its eight neighbours every k-mer of the ids [begin, end) has in the dictionary, a byte per k-mer. */
+    std::pair<std::vector<uint64_t>, std::vector<sshash_string_link>> string_links(uint64_t begin, uint64_t end, bool check_reverse_complement = true) const {
+        std::vector<uint64_t> offsets(end >= begin ? end - begin + 1 : 1);
+        check(sshash_string_links(m_h, begin, end, check_reverse_complement, offsets.data(), nullptr, 0));
+        std::vector<sshash_string_link> links(offsets.back());
+        if (!links.empty()) check(sshash_string_links(m_h, begin, end, check_reverse_complement, offsets.data(), links.data(), links.size()));
+        return {std::move(offsets), std::move(links)};
+    }
+    std::vector<uint8_t> kmer_adjacency(uint64_t begin, uint64_t end, bool check_reverse_complement = true) const {
+        std::vector<uint8_t> masks(end >= begin ? end - begin : 0);
+        check(sshash_kmer_adjacency(m_h, begin, end, check_reverse_complement, masks.empty() ? nullptr : masks.data()));
+        return masks;
+    }
+
     /* Membership queries -- include/dictionary.hpp:74-76 */
     bool is_member(char const* string_kmer, bool check_reverse_complement = true) const {
         uint8_t out = 0;

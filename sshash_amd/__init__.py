@@ -12,6 +12,7 @@ Method names and argument meaning follow ``sshash::dictionary`` (reference
 """
 from ._binding import (  # noqa: F401
     INVALID_U64,
+    LINK_DTYPE,
     MAX_CLASSES,
     NO_CLASS,
     READ_CLASS_DTYPE,
@@ -23,6 +24,7 @@ from ._binding import (  # noqa: F401
     LookupResult,
     SSHashError,
     StreamingQueryReport,
+    adjacency_degrees,
     class_best,
     class_totals,
     cover_to_ids,
@@ -31,12 +33,16 @@ from ._binding import (  # noqa: F401
     expand_runs,
     ids_to_cover,
     library_path,
+    link_degrees,
+    links_gfa,
     runs_best,
+    write_gfa,
     write_weighted_fasta,
 )
 
 __all__ = [
     "INVALID_U64",
+    "LINK_DTYPE",
     "MAX_CLASSES",
     "NO_CLASS",
     "READ_CLASS_DTYPE",
@@ -48,6 +54,7 @@ __all__ = [
     "LookupResult",
     "SSHashError",
     "StreamingQueryReport",
+    "adjacency_degrees",
     "class_best",
     "class_totals",
     "cover_to_ids",
@@ -56,6 +63,9 @@ __all__ = [
     "expand_runs",
     "ids_to_cover",
     "library_path",
+    "link_degrees",
+    "links_gfa",
     "runs_best",
+    "write_gfa",
     "write_weighted_fasta",
 ]

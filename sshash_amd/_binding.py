@@ -105,6 +105,10 @@ class _Run(C.Structure):  # (the same record for ctypes: its size and offsets ar
                 ("num_kmers", C.c_uint32)]
 
 
+# sshash_string_link (include/sshash_amd.h): one link of the dictionary's graph, from a string's end to a neighbour k-mer
+LINK_DTYPE = np.dtype([("from_string", "<u8"), ("to_string", "<u8"), ("to_kmer_id", "<u8"), ("flags", "<u4"), ("reserved", "<u4")])
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -150,6 +154,11 @@ _SIGNATURES = {
     "sshash_neighbours_packed_device": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.c_int, C.POINTER(_Results), _P]),
     "sshash_neighbours_packed": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.POINTER(_Results)]),
     "sshash_string_neighbours": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.POINTER(_Results)]),
+    "sshash_string_neighbours_device": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(_Results), _P]),
+    "sshash_string_links_device": (C.c_int, [_P, C.c_int, C.c_uint64, C.c_uint64, C.c_int, _P, _P, C.c_uint64, _P]),
+    "sshash_string_links": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_int, _P, _P, C.c_uint64]),
+    "sshash_kmer_adjacency_device": (C.c_int, [_P, C.c_int, C.c_uint64, C.c_uint64, C.c_int, _P, _P]),
+    "sshash_kmer_adjacency": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_int, _P]),
     "sshash_string_size": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "sshash_string_offsets": (C.c_int, [_P, _P, C.c_uint64, _P, _P]),
     "sshash_is_member_packed_device": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.c_int, _P, _P]),
@@ -578,6 +587,58 @@ class Dictionary:
         r.kmer_id = ids.ctypes.data
         _check(_load().sshash_string_neighbours(self._h, sids.ctypes.data, sids.size, 1 if check_reverse_complement else 0, C.byref(r)))
         return ids
+
+    def string_neighbours_device(self, device: int, d_string_ids: int, n: int, d_kmer_id: int, check_reverse_complement: bool = True,
+                                 stream: int = 0, first_string: int = 0, **optional_outputs: int) -> None:
+        """string_neighbours on the GPU: d_string_ids holds n uint64 string ids, or is 0 for the strings first_string + i; d_kmer_id (and
+        every optional output) has room for 8*n entries. An id past the last string gives eight not-found entries. Asynchronous."""
+        r = _Results()
+        r.kmer_id = d_kmer_id
+        for name, ptr in optional_outputs.items():
+            setattr(r, name, ptr)
+        _check(_load().sshash_string_neighbours_device(self._h, int(device), C.c_void_p(d_string_ids), int(first_string), int(n),
+                                                       1 if check_reverse_complement else 0, C.byref(r), C.c_void_p(stream)))
+
+    # ---- the dictionary as a graph (include/sshash_amd.h: sshash_string_link, sshash_kmer_adjacency) ----------------------------
+    def string_links(self, begin: int = 0, end: Optional[int] = None, check_reverse_complement: bool = True):
+        """The links of the strings [begin, end) (default: all) -> (link_offsets, links): one LINK_DTYPE record per neighbour of a
+        string's end k-mers that the dictionary holds, the records of string begin + i at links[link_offsets[i]:link_offsets[i + 1]]
+        in increasing flags & 7. A counting call, then the exact one, on the first resident replica. links_gfa() reads the flags."""
+        end = self.num_strings() if end is None else int(end)
+        begin = int(begin)
+        if begin < 0 or end < 0:
+            raise SSHashError(1, "string_links: string ids are non-negative")
+        rc = 1 if check_reverse_complement else 0
+        link_offsets = np.zeros(max(end - begin, 0) + 1, dtype=np.uint64)
+        _check(_load().sshash_string_links(self._h, begin, end, rc, link_offsets.ctypes.data, None, 0))
+        links = np.zeros(int(link_offsets[-1]), dtype=LINK_DTYPE)
+        if links.size:
+            _check(_load().sshash_string_links(self._h, begin, end, rc, link_offsets.ctypes.data, links.ctypes.data, links.size))
+        return link_offsets, links
+
+    def string_links_device(self, device: int, begin: int, end: int, d_link_offsets: int, d_links: int = 0, links_capacity: int = 0,
+                            check_reverse_complement: bool = True, stream: int = 0) -> None:
+        """Device buffers, asynchronous: d_link_offsets receives end - begin + 1 uint64 (exact whatever the capacity), d_links the
+        records below links_capacity (0 with capacity 0: the counting call)."""
+        _check(_load().sshash_string_links_device(self._h, int(device), int(begin), int(end), 1 if check_reverse_complement else 0,
+                                                  C.c_void_p(d_link_offsets), C.c_void_p(d_links), int(links_capacity), C.c_void_p(stream)))
+
+    def kmer_adjacency(self, begin: int = 0, end: Optional[int] = None, check_reverse_complement: bool = True) -> np.ndarray:
+        """Which of its eight neighbours every k-mer of the ids [begin, end) (default: all) has in the dictionary -> uint8 masks: bit c
+        the forward neighbour "ACTG"[c], bit 4 + c the backward one. On the first resident replica. adjacency_degrees() counts them."""
+        end = self.num_kmers() if end is None else int(end)
+        begin = int(begin)
+        if begin < 0 or end < 0:
+            raise SSHashError(1, "iterate: ids are non-negative")
+        masks = np.zeros(max(end - begin, 0), dtype=np.uint8)
+        _check(_load().sshash_kmer_adjacency(self._h, begin, end, 1 if check_reverse_complement else 0, masks.ctypes.data if masks.size else None))
+        return masks
+
+    def kmer_adjacency_device(self, device: int, begin: int, end: int, d_masks: int, check_reverse_complement: bool = True,
+                              stream: int = 0) -> None:
+        """The same into the device buffer d_masks (end - begin bytes), asynchronous on `stream`."""
+        _check(_load().sshash_kmer_adjacency_device(self._h, int(device), int(begin), int(end), 1 if check_reverse_complement else 0,
+                                                    C.c_void_p(d_masks), C.c_void_p(stream)))
 
     def neighbours_device(self, device: int, d_kmers: int, n: int, d_kmer_id: int, check_reverse_complement: bool = True,
                           stream: int = 0, **optional_outputs: int) -> None:
@@ -1191,6 +1252,16 @@ def write_weighted_fasta(d: "Dictionary", depth, path: str) -> None:
         raise ValueError(f"depth: {n_kmers} integer counts, one per k-mer id")
     if depth.dtype.kind == "i" and depth.size and int(depth.min()) < 0:
         raise ValueError("depth: counts are not negative")
+    with (gzip.open(path, "wt") if str(path).endswith(".gz") else open(path, "w")) as f:
+        for s, first, text in _strings_in_id_order(d):
+            counts = " ".join(map(str, depth[first:first + len(text) - k + 1].tolist()))
+            f.write(f">{s} LN:i:{len(text)} ab:Z:{counts}\n{text}\n")
+
+
+def _strings_in_id_order(d: "Dictionary"):
+    """-> (string id, id of its first k-mer, the string) for every string of the dictionary, decoded on the CPU through the k-mer
+    iterator, a few thousand strings at a time."""
+    n_strings, k = d.num_strings(), d.k()
     letters = np.frombuffer(b"ACTG", dtype=np.uint8)  # 2-bit code -> character
     W = d.words_per_kmer()
     last_word, last_shift = (k - 1) // 32, np.uint64(2 * ((k - 1) % 32))
@@ -1198,24 +1269,67 @@ def write_weighted_fasta(d: "Dictionary", depth, path: str) -> None:
     sid = np.arange(n_strings, dtype=np.uint64)
     first_id = (begin - sid * np.uint64(k - 1)).astype(np.int64)  # ids of string s: [first_id[s], first_id[s] + size[s])
     size = (end - begin).astype(np.int64) - (k - 1)
+    s0 = 0
+    while s0 < n_strings:
+        s1 = s0 + 1
+        while s1 < n_strings and s1 - s0 < 4096 and int(first_id[s1]) - int(first_id[s0]) < (1 << 22):
+            s1 += 1
+        lo, hi = int(first_id[s0]), int(first_id[s1 - 1] + size[s1 - 1])
+        packed = d.kmers(lo, hi).reshape(-1, W)
+        last = letters[((packed[:, last_word] >> last_shift) & np.uint64(3)).astype(np.uint8)]  # the last character of every k-mer
+        for s in range(s0, s1):
+            a, n = int(first_id[s]) - lo, int(size[s])
+            head = np.empty(k - 1, dtype=np.uint8)  # the first k-mer's characters but its last
+            for i in range(k - 1):
+                head[i] = letters[int((int(packed[a, i // 32]) >> (2 * (i % 32))) & 3)]
+            yield s, lo + a, (head.tobytes() + last[a:a + n].tobytes()).decode("ascii")
+        s0 = s1
+
+
+def link_degrees(link_offsets, links):
+    """-> (out_at_end, out_at_start): per string of a string_links() range, how many links leave its end and its start."""
+    link_offsets = np.asarray(link_offsets, dtype=np.uint64)
+    n = link_offsets.size - 1
+    owner = np.repeat(np.arange(n), np.diff(link_offsets).astype(np.int64))
+    at_start = (links["flags"] & 4) != 0
+    return (np.bincount(owner[~at_start], minlength=n).astype(np.uint8), np.bincount(owner[at_start], minlength=n).astype(np.uint8))
+
+
+def adjacency_degrees(masks):
+    """-> (forward, backward): per k-mer of a kmer_adjacency() range, how many of its forward and of its backward neighbours the
+    dictionary holds."""
+    masks = np.asarray(masks, dtype=np.uint8)
+    ones = np.array([bin(i).count("1") for i in range(16)], dtype=np.uint8)
+    return ones[masks & 15], ones[masks >> 4]
+
+
+def links_gfa(links):
+    """The sign rule of include/sshash_amd.h -> (is_end_to_end, from_sign, to_sign): which links join two string ends (the L lines of
+    a GFA), and the orientation of both strings in them, as arrays of b'+' / b'-'."""
+    flags = links["flags"]
+    at_start, rc, first, last = ((flags & bit) != 0 for bit in (4, 8, 16, 32))
+    end_to_end = np.where(at_start, np.where(rc, first, last), np.where(rc, last, first))
+    sign = np.array([b"-", b"+"])
+    return end_to_end, sign[(~at_start).astype(np.int64)], sign[(rc == at_start).astype(np.int64)]
+
+
+def write_gfa(d: "Dictionary", path: str, link_offsets=None, links=None) -> None:
+    """The dictionary as a GFA 1: H, one S line per string (named by its id) and one 'L from sign to sign (k-1)M' line per end-to-end
+    link, each as seen from its from_string -- a link between two string ends appears once from either side, as BCALM-style GFAs
+    list them. Links that land inside a string (junctions inside stitched strings) have no L line. `links` None: string_links() over
+    all strings (needs a replica); the strings are decoded on the CPU. gzip when `path` ends in .gz."""
+    import gzip
+
+    if links is None:
+        link_offsets, links = d.string_links()
+    end_to_end, from_sign, to_sign = links_gfa(links)
+    overlap = f"{d.k() - 1}M"
     with (gzip.open(path, "wt") if str(path).endswith(".gz") else open(path, "w")) as f:
-        s0 = 0
-        while s0 < n_strings:
-            s1 = s0 + 1
-            while s1 < n_strings and s1 - s0 < 4096 and int(first_id[s1]) - int(first_id[s0]) < (1 << 22):
-                s1 += 1
-            lo, hi = int(first_id[s0]), int(first_id[s1 - 1] + size[s1 - 1])
-            packed = d.kmers(lo, hi).reshape(-1, W)
-            last = letters[((packed[:, last_word] >> last_shift) & np.uint64(3)).astype(np.uint8)]  # the last character of every k-mer
-            for s in range(s0, s1):
-                a, n = int(first_id[s]) - lo, int(size[s])
-                head = np.empty(k - 1, dtype=np.uint8)  # the first k-mer's characters but its last
-                for i in range(k - 1):
-                    head[i] = letters[int((int(packed[a, i // 32]) >> (2 * (i % 32))) & 3)]
-                text = head.tobytes() + last[a:a + n].tobytes()
-                counts = " ".join(map(str, depth[lo + a:lo + a + n].tolist()))
-                f.write(f">{s} LN:i:{len(text)} ab:Z:{counts}\n{text.decode('ascii')}\n")
-            s0 = s1
+        f.write("H\tVN:Z:1.0\n")
+        for s, _, text in _strings_in_id_order(d):
+            f.write(f"S\t{s}\t{text}\tLN:i:{len(text)}\n")
+        for i in np.flatnonzero(end_to_end):
+            f.write(f"L\t{int(links['from_string'][i])}\t{from_sign[i].decode()}\t{int(links['to_string'][i])}\t{to_sign[i].decode()}\t{overlap}\n")
 
 
 def _class_rows(rows) -> np.ndarray:

@@ -436,6 +436,40 @@ sshash_status sshash_string_neighbours(const sshash_dict* d, const uint64_t* str
     });
 }
 
+sshash_status sshash_string_neighbours_device(const sshash_dict* d, int device, const uint64_t* string_ids, uint64_t first_string, uint64_t n,
+                                              int check_rc, const sshash_results* out, void* hip_stream) {
+    if (!d || !out) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] {
+        d->eng->string_neighbours_device(device, string_ids, first_string, n, check_rc != 0, wants_full(out) ? out_mode::full : out_mode::ids,
+                                         to_view(out), hip_stream);
+    });
+}
+
+static_assert(sizeof(sshash_string_link) == 32, "a link record is 32 bytes: two 16-byte stores on the device");
+
+sshash_status sshash_string_links_device(const sshash_dict* d, int device, uint64_t begin_string, uint64_t end_string, int check_rc,
+                                         uint64_t* link_offsets, sshash_string_link* links, uint64_t links_capacity, void* hip_stream) {
+    if (!d) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] { d->eng->string_links_device(device, begin_string, end_string, check_rc != 0, link_offsets, links, links_capacity, hip_stream); });
+}
+
+sshash_status sshash_string_links(const sshash_dict* d, uint64_t begin_string, uint64_t end_string, int check_rc, uint64_t* link_offsets,
+                                  sshash_string_link* links, uint64_t links_capacity) {
+    if (!d) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] { d->eng->string_links_host(begin_string, end_string, check_rc != 0, link_offsets, links, links_capacity); });
+}
+
+sshash_status sshash_kmer_adjacency_device(const sshash_dict* d, int device, uint64_t begin_kmer_id, uint64_t end_kmer_id, int check_rc,
+                                           uint8_t* masks, void* hip_stream) {
+    if (!d) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] { d->eng->kmer_adjacency_device(device, begin_kmer_id, end_kmer_id, check_rc != 0, masks, hip_stream); });
+}
+
+sshash_status sshash_kmer_adjacency(const sshash_dict* d, uint64_t begin_kmer_id, uint64_t end_kmer_id, int check_rc, uint8_t* masks) {
+    if (!d) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] { d->eng->kmer_adjacency_host(begin_kmer_id, end_kmer_id, check_rc != 0, masks); });
+}
+
 sshash_status sshash_is_member_packed_device(const sshash_dict* d, int device, const uint64_t* kmers, uint64_t n,
                                              int check_rc, uint8_t* out, void* hip_stream) {
     if (!d || !out || (!kmers && n)) return fail(SSHASH_ERR_ARGUMENT, "null argument");

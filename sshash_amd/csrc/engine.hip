@@ -1476,6 +1476,236 @@ void engine::check_device(int device, uint64_t out[8]) const {
     for (int i = 0; i < 8; ++i) out[i] = h[i];
 }
 
+/* ---- the dictionary's graph: string_neighbours on the device, the links between strings as CSR, the adjacency of every k-mer of an
+        id range. All three are function on top of the batched lookup: 8 lookups per string end or per k-mer, in
+        rounds of at most GRAPH_CHUNK strings or k-mers (hooks.hpp) whose scratch comes out of the replica's stream-ordered pool. ---- */
+
+/* One lane per (string, which): the string's last k-mer (which < 4) or its first, straight out of the endpoints and the atoms /
+   granules, and its neighbour `which` -- a wave stores 64 consecutive queries. A string id >= num_strings gives all-ones words, as
+   access_kernel gives for an id past the end. */
+template <int W>
+__global__ void __launch_bounds__(256)
+expand_string_ends_kernel(const dict_view d, const uint64_t* __restrict__ string_ids, const uint64_t first_string, const uint64_t n,
+                          uint64_t* __restrict__ out) {
+    const uint64_t t = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (t >= 8 * n) return;
+    const uint32_t which = uint32_t(t & 7);
+    const uint64_t s = string_ids ? string_ids[t >> 3] : first_string + (t >> 3);
+    kmer_w<W> y;
+    if (s >= d.num_strings) {
+        for (int j = 0; j < W; ++j) y.w[j] = INVALID_U64;
+    } else {
+        const uint64_t off = which < 4 ? d.endpoints[s + 1] - d.k : d.endpoints[s];  // suffix of the string forward, prefix backward
+        y = kmer_neighbour<W>(read_window<W>(d.granules, off, d.k).kmer, which, d.k);
+    }
+    for (int j = 0; j < W; ++j) out[t * W + j] = y.w[j];
+}
+
+/* 8 ids -> which of them were found: one lane reads the 64 contiguous bytes of its item (four 16-byte loads, eight compares) and
+   stores the mask as a byte (adjacency) or its population count as a word (the links' counting pass): 59 instructions for a wave's
+   64 items. Eight lanes with a ballot store coalesced but compile to 39 instructions for a wave's 8 items, five times as many an
+   item; every byte is read once either way. */
+template <bool COUNT>
+__global__ void __launch_bounds__(256)
+fold_found_kernel(const uint64_t* __restrict__ ids, const uint64_t n, uint8_t* __restrict__ masks, uint64_t* __restrict__ counts) {
+    const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const sk_u32x4* p = reinterpret_cast<const sk_u32x4*>(ids + 8 * i);
+    uint32_t mask = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const sk_u32x4 v = __builtin_nontemporal_load(p + j);
+        mask |= uint32_t((v.x & v.y) != 0xFFFFFFFFu) << (2 * j);
+        mask |= uint32_t((v.z & v.w) != 0xFFFFFFFFu) << (2 * j + 1);
+    }
+    if constexpr (COUNT) counts[i] = uint64_t(__popc(mask));
+    else masks[i] = uint8_t(mask);
+}
+
+/* The writing pass of the links: one lane per (string, which) of the round. The eight lanes of a string rank their found
+   neighbours with a ballot; record offsets[string] + rank is written iff it lies below `capacity`, as two 16-byte stores. Bit 5
+   (the neighbour is the last k-mer of its string) comes from the endpoints of that string, read here. */
+__global__ void __launch_bounds__(256)
+links_scatter_kernel(const dict_view d, const result_view r, const uint64_t first_string, const uint64_t n,
+                     const uint64_t* __restrict__ offsets, sk_u32x4* __restrict__ links, const uint64_t capacity) {
+    const uint64_t t = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    const bool active = t < 8 * n;
+    const uint64_t id = active ? r.kmer_id[t] : INVALID_U64;
+    const bool found = id != INVALID_U64;
+    const uint64_t ballot = __ballot(found);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t half = lane & 32u ? uint32_t(ballot >> 32) : uint32_t(ballot);
+    const uint32_t mine = (half >> (lane & 24u)) & 0xFFu;  // the eight lanes of this string
+    if (!found) return;
+    const uint64_t at = offsets[t >> 3] + __popc(mine & ((1u << (lane & 7u)) - 1u));
+    if (at >= capacity) return;
+    const uint64_t to = r.string_id[t], in_string = r.kmer_id_in_string[t];
+    const uint64_t size = d.endpoints[to + 1] - d.endpoints[to] - (d.k - 1);  // k-mers of the string the link lands in
+    const uint32_t flags = uint32_t(t & 7) | (r.kmer_orientation[t] < 0 ? 8u : 0u) | (in_string == 0 ? 16u : 0u) | (in_string + 1 == size ? 32u : 0u);
+    const uint64_t from = first_string + (t >> 3);
+    sk_u32x4 a, b;
+    a.x = uint32_t(from), a.y = uint32_t(from >> 32), a.z = uint32_t(to), a.w = uint32_t(to >> 32);
+    b.x = uint32_t(id), b.y = uint32_t(id >> 32), b.z = flags, b.w = 0;
+    links[2 * at] = a;
+    links[2 * at + 1] = b;
+}
+
+static void expand_string_ends(device_replica const* rep, uint64_t const* d_ids, uint64_t first, uint64_t n, uint64_t* expanded, hipStream_t s) {
+    const dim3 grid(uint32_t((8 * n + 255) / 256)), block(256);
+    if (rep->view.k <= 31) hipLaunchKernelGGL(expand_string_ends_kernel<1>, grid, block, 0, s, rep->view, d_ids, first, n, expanded);
+    else hipLaunchKernelGGL(expand_string_ends_kernel<2>, grid, block, 0, s, rep->view, d_ids, first, n, expanded);
+    HIP_CHECK(hipGetLastError());
+}
+
+void engine::string_neighbours_device(int device, uint64_t const* d_string_ids, uint64_t first_string, uint64_t n, bool check_rc,
+                                      out_mode mode, result_view const& d_out, void* stream) const {
+    check_outputs(mode, d_out, nullptr);
+    if (!d_string_ids && (first_string > m_idx->num_strings || n > m_idx->num_strings - first_string))
+        throw error(error_kind::argument, "string_neighbours: need first_string + n <= num_strings");
+    device_replica const* rep = replica(device);
+    if (n == 0) return;
+    check_single_launch(8 * n, "string_neighbours");
+    device_guard guard(device);
+    hipStream_t s = hipStream_t(stream);
+    device_buffers tmp(rep, s);
+    uint64_t* expanded = tmp.alloc<uint64_t>(8 * n * (rep->view.k <= 31 ? 1 : 2));
+    expand_string_ends(rep, d_string_ids, first_string, n, expanded, s);
+    launch_any<false>(mode, rep, expanded, 8 * n, check_rc, d_out, nullptr, s);
+}
+
+namespace {
+
+void links_arguments(host_index const& idx, uint64_t begin, uint64_t end, uint64_t const* offsets, void const* links, uint64_t capacity) {
+    if (begin > end || end > idx.num_strings) throw error(error_kind::argument, "string_links: need begin <= end <= num_strings");
+    if (!offsets) throw error(error_kind::argument, "string_links: link_offsets pointer is null");
+    if (!links && capacity) throw error(error_kind::argument, "string_links: links pointer is null, links_capacity is not 0");
+    if (idx.num_shards > 1)
+        throw error(error_kind::argument, "string_links: a minimizer shard answers only the k-mers it owns (ask the whole index)");
+}
+
+void adjacency_arguments(host_index const& idx, uint64_t begin, uint64_t end, uint8_t const* masks) {
+    if (begin > end || end > idx.num_kmers) throw error(error_kind::argument, "iterate: need begin <= end <= num_kmers");
+    if (!masks && end > begin) throw error(error_kind::argument, "kmer_adjacency: masks pointer is null");
+    if (idx.num_shards > 1)
+        throw error(error_kind::argument, "kmer_adjacency: a minimizer shard answers only the k-mers it owns (ask the whole index)");
+}
+
+/* The counting pass: per round the ends' neighbours, an ids-only lookup and the count of every string into its word of the offsets;
+   then word end - begin zero and the exclusive scan over all of them: complete, exact offsets. */
+void links_count(device_replica const* rep, uint64_t begin, uint64_t end, bool check_rc, uint64_t* d_offsets, hipStream_t s) {
+    const uint64_t n = end - begin, W = rep->view.k <= 31 ? 1 : 2;
+    HIP_CHECK(hipMemsetAsync(d_offsets + n, 0, sizeof(uint64_t), s));
+    if (n) {
+        const uint64_t chunk = std::min(n, links_chunk());
+        device_buffers tmp(rep, s);
+        uint64_t* expanded = tmp.alloc<uint64_t>(8 * chunk * W);
+        result_view ids{};
+        ids.kmer_id = tmp.alloc<uint64_t>(8 * chunk);
+        for (uint64_t b = 0; b < n; b += chunk) {
+            const uint64_t m = std::min(chunk, n - b);
+            expand_string_ends(rep, nullptr, begin + b, m, expanded, s);
+            launch_any<false>(out_mode::ids, rep, expanded, 8 * m, check_rc, ids, nullptr, s);
+            hipLaunchKernelGGL(fold_found_kernel<true>, dim3(uint32_t((m + 255) / 256)), dim3(256), 0, s, ids.kmer_id, m, nullptr, d_offsets + b);
+            HIP_CHECK(hipGetLastError());
+        }
+    }
+    exclusive_scan_words(rep, d_offsets, n + 1, s);
+}
+
+/* The writing pass over scanned offsets: the ends' neighbours again, a lookup with the fields of a record, the scatter. */
+void links_write(device_replica const* rep, uint64_t begin, uint64_t end, bool check_rc, uint64_t const* d_offsets, void* d_links,
+                 uint64_t capacity, hipStream_t s) {
+    const uint64_t n = end - begin, W = rep->view.k <= 31 ? 1 : 2;
+    if (n == 0 || capacity == 0) return;
+    const uint64_t chunk = std::min(n, links_chunk());
+    device_buffers tmp(rep, s);
+    uint64_t* expanded = tmp.alloc<uint64_t>(8 * chunk * W);
+    result_view r{};
+    r.kmer_id = tmp.alloc<uint64_t>(8 * chunk);
+    r.kmer_id_in_string = tmp.alloc<uint64_t>(8 * chunk);
+    r.string_id = tmp.alloc<uint64_t>(8 * chunk);
+    r.kmer_orientation = tmp.alloc<int8_t>(8 * chunk);
+    for (uint64_t b = 0; b < n; b += chunk) {
+        const uint64_t m = std::min(chunk, n - b);
+        expand_string_ends(rep, nullptr, begin + b, m, expanded, s);
+        launch_any<false>(out_mode::full, rep, expanded, 8 * m, check_rc, r, nullptr, s);
+        hipLaunchKernelGGL(links_scatter_kernel, dim3(uint32_t((8 * m + 255) / 256)), dim3(256), 0, s, rep->view, r, begin + b, m, d_offsets + b,
+                           static_cast<sk_u32x4*>(d_links), capacity);
+        HIP_CHECK(hipGetLastError());
+    }
+}
+
+}  // namespace
+
+void engine::string_links_device(int device, uint64_t begin, uint64_t end, bool check_rc, uint64_t* d_link_offsets, void* d_links,
+                                 uint64_t links_capacity, void* stream) const {
+    links_arguments(*m_idx, begin, end, d_link_offsets, d_links, links_capacity);
+    device_replica const* rep = replica(device);
+    device_guard guard(device);
+    links_count(rep, begin, end, check_rc, d_link_offsets, hipStream_t(stream));
+    links_write(rep, begin, end, check_rc, d_link_offsets, d_links, links_capacity, hipStream_t(stream));
+}
+
+void engine::string_links_host(uint64_t begin, uint64_t end, bool check_rc, uint64_t* link_offsets, void* links, uint64_t links_capacity) const {
+    links_arguments(*m_idx, begin, end, link_offsets, links, links_capacity);
+    const int device = resident_devices(*this)[0];
+    device_replica const* rep = replica(device);
+    device_guard guard(device);
+    const uint64_t n = end - begin;
+    device_buffers tmp;
+    const own_stream x(rep);
+    uint64_t* d_offsets = tmp.alloc<uint64_t>(n + 1);
+    links_count(rep, begin, end, check_rc, d_offsets, x.s);
+    HIP_CHECK(hipMemcpyAsync(link_offsets, d_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, x.s));
+    HIP_CHECK(hipStreamSynchronize(x.s));
+    const uint64_t room = std::min(links_capacity, link_offsets[n]);  // records the caller gets
+    if (room == 0) return;
+    void* d_links = tmp.alloc<uint64_t>(4 * room);
+    links_write(rep, begin, end, check_rc, d_offsets, d_links, room, x.s);
+    HIP_CHECK(hipMemcpyAsync(links, d_links, room * 32, hipMemcpyDeviceToHost, x.s));
+    HIP_CHECK(hipStreamSynchronize(x.s));
+}
+
+void engine::kmer_adjacency_device(int device, uint64_t begin, uint64_t end, bool check_rc, uint8_t* d_masks, void* stream) const {
+    adjacency_arguments(*m_idx, begin, end, d_masks);
+    device_replica const* rep = replica(device);
+    const uint64_t n = end - begin, W = rep->view.k <= 31 ? 1 : 2;
+    if (n == 0) return;
+    device_guard guard(device);
+    hipStream_t s = hipStream_t(stream);
+    const uint64_t chunk = std::min(n, adjacency_chunk());
+    device_buffers tmp(rep, s);
+    uint64_t* kmers = tmp.alloc<uint64_t>(chunk * W);
+    uint64_t* expanded = tmp.alloc<uint64_t>(8 * chunk * W);
+    result_view ids{};
+    ids.kmer_id = tmp.alloc<uint64_t>(8 * chunk);
+    for (uint64_t b = 0; b < n; b += chunk) {
+        const uint64_t m = std::min(chunk, n - b);
+        const dim3 grid(uint32_t((8 * m + 255) / 256)), block(256);
+        iterate_packed_device(device, begin + b, begin + b + m, kmers, s);
+        if (W == 1) hipLaunchKernelGGL(expand_neighbours_kernel<1>, grid, block, 0, s, kmers, m, rep->view.k, expanded);
+        else hipLaunchKernelGGL(expand_neighbours_kernel<2>, grid, block, 0, s, kmers, m, rep->view.k, expanded);
+        HIP_CHECK(hipGetLastError());
+        launch_any<false>(out_mode::ids, rep, expanded, 8 * m, check_rc, ids, nullptr, s);
+        hipLaunchKernelGGL(fold_found_kernel<false>, dim3(uint32_t((m + 255) / 256)), block, 0, s, ids.kmer_id, m, d_masks + b, nullptr);
+        HIP_CHECK(hipGetLastError());
+    }
+}
+
+void engine::kmer_adjacency_host(uint64_t begin, uint64_t end, bool check_rc, uint8_t* masks) const {
+    adjacency_arguments(*m_idx, begin, end, masks);
+    const int device = resident_devices(*this)[0];
+    device_replica const* rep = replica(device);
+    if (begin == end) return;
+    device_guard guard(device);
+    device_buffers tmp;
+    const own_stream x(rep);
+    uint8_t* d_masks = tmp.alloc<uint8_t>(end - begin);
+    kmer_adjacency_device(device, begin, end, check_rc, d_masks, x.s);
+    HIP_CHECK(hipMemcpyAsync(masks, d_masks, end - begin, hipMemcpyDeviceToHost, x.s));
+    HIP_CHECK(hipStreamSynchronize(x.s));
+}
+
 /* ---- host-buffer path -----------------------------------------------------------------------
    The caller's arrays are pageable host memory. Per replica the batch is cut into chunks that several
    *lanes* pull from a shared counter; a lane owns a HIP stream, a pinned staging block and a device block

@@ -174,6 +174,25 @@ public:
     void string_neighbours_host(uint64_t const* h_string_ids, uint64_t n, bool check_rc, out_mode mode,
                                 result_view const& h_out) const;
 
+    /* The same on the device (sshash_string_neighbours_device): `d_string_ids` null = the strings first_string + i; an id
+       >= num_strings gives an all-ones query. Asynchronous; the expanded queries come out of the replica's pool. */
+    void string_neighbours_device(int device, uint64_t const* d_string_ids, uint64_t first_string, uint64_t n, bool check_rc, out_mode mode,
+                                  result_view const& d_out, void* stream) const;
+
+    /* The links of the strings [begin, end) as CSR (sshash_string_links[_device] in include/sshash_amd.h): one record of 32 bytes per
+       found neighbour among the eight of string_neighbours(s). Count -> scan -> write, in rounds of at most 2^22 strings:
+       `d_link_offsets` (end - begin + 1 words) is always complete, record i is written iff i < links_capacity. Asynchronous, no host
+       synchronisation. Throws on a minimizer shard. The host form runs on the first resident replica. */
+    void string_links_device(int device, uint64_t begin, uint64_t end, bool check_rc, uint64_t* d_link_offsets, void* d_links,
+                             uint64_t links_capacity, void* stream) const;
+    void string_links_host(uint64_t begin, uint64_t end, bool check_rc, uint64_t* link_offsets, void* links, uint64_t links_capacity) const;
+
+    /* Which of its eight neighbours every k-mer of the ids [begin, end) has in the dictionary (sshash_kmer_adjacency[_device]): bit c of
+       byte i - begin forward neighbour c, bit 4 + c backward neighbour c. Iterate -> expand -> ids-only lookup -> fold, in rounds
+       of at most 2^22 k-mers. Asynchronous. Throws on a minimizer shard. The host form runs on the first resident replica. */
+    void kmer_adjacency_device(int device, uint64_t begin, uint64_t end, bool check_rc, uint8_t* d_masks, void* stream) const;
+    void kmer_adjacency_host(uint64_t begin, uint64_t end, bool check_rc, uint8_t* masks) const;
+
     /* access(kmer_id) for a batch of ids, device buffers: out gets n*W packed words
        (all-ones for an id >= num_kmers). */
     void access_packed_device(int device, uint64_t const* d_ids, uint64_t n, uint64_t* d_out, void* stream) const;

@@ -73,4 +73,10 @@ inline double test_hook_f64(char const* name, double fallback, double lo, double
     return v >= lo && v <= hi ? v : fallback;
 }
 
+/* The rounds of the graph calls (engine.hip): strings per round of the string links, k-mers per round of the k-mer adjacency, 1 .. 2^22
+   each. The tests put many rounds, and rounds of one item, over a small dictionary. */
+constexpr uint64_t GRAPH_CHUNK = uint64_t(1) << 22;  // 2^25 lookups a round
+inline uint64_t links_chunk() { return test_hook_u64("links_chunk", GRAPH_CHUNK, 1, GRAPH_CHUNK); }
+inline uint64_t adjacency_chunk() { return test_hook_u64("adjacency_chunk", GRAPH_CHUNK, 1, GRAPH_CHUNK); }
+
 }  // namespace sshash_amd

@@ -329,6 +329,10 @@ private:
 
 class engine;
 
+/* data[i] = data[0] + .. + data[i - 1] for i < n, 64-bit words in place on `s` (streaming.hip: the scan of the runs' CSR); its tile
+   sums are allocated and freed by the call, stream-ordered, from the replica's pool */
+void exclusive_scan_words(device_replica const* rep, uint64_t* data, uint64_t n, hipStream_t s);
+
 /* the devices holding a replica (engine::devices), or the error that there are none */
 std::vector<int> resident_devices(engine const& eng);
 

@@ -1658,6 +1658,12 @@ void engine::streaming_depth_device(int device, char const* d_bases, uint64_t co
     });
 }
 
+/* exclusive_scan_u64 for the callers outside this file (replica.hpp: the offsets of the string links, engine.hip) */
+void exclusive_scan_words(device_replica const* rep, uint64_t* data, uint64_t n, hipStream_t s) {
+    device_buffers tmp(rep, s);
+    exclusive_scan_u64(data, n, tmp.alloc<uint64_t>(scan_tiles(n)), s);
+}
+
 /* The prefix sums of a value per k-mer (sshash_value_prefix_device): widened, word num_kmers zero, scanned in place. */
 void engine::value_prefix_device(int device, uint32_t const* d_values, uint32_t at_least, uint64_t* d_prefix, void* stream) const {
     device_replica const* rep = replica(device);
