@@ -1,8 +1,9 @@
 #!/usr/bin/env python
-"""Worker of tests/test_gpu_forms_sweep.py, and the input generator it shares with tests/test_forms_sweep_inputs.py: ALL SEVEN output
+"""Worker of tests/test_gpu_forms_sweep.py, and the input generator it shares with tests/test_forms_sweep_inputs.py: ALL TEN output
 forms of the streaming run kernel -- the batch counters, the per-read rows, the run counts and records, the cover bitmap, the depth
-deltas, the per-read sums over a value per k-mer -- and the segment machinery for long reads, at one point (k, m, length of the table's
-keys, replica layer), regular then canonical. The run forms do arithmetic the per-k-mer forms never do (kmer_id = offset - string_id *
+deltas, the per-read sums over a value per k-mer, the per-read classes of the strings hit, the per-read best run, the run records over
+segments -- and the segment machinery for long reads, at one point (k, m, length of the table's keys, replica layer), regular then
+canonical. The run forms do arithmetic the per-k-mer forms never do (kmer_id = offset - string_id *
 (k - 1), the first id of a backward run, a segment's end at + S + k - 1, the first invalid base of a window, the funnel shift of a
 two-word seed), and the length of the table's keys is a parameter of its own (`hashed`, sk_key_persists); the points of the sweep are
 where these change: k = 33 (one base in the second word; for the sums, the first k at which a run's two words of the prefix are added
@@ -14,9 +15,16 @@ worker sets nothing itself and asserts from device_stats() that the setting took
 of read, run and seam the kernels have a branch for, and the ids of the oracle's restated state machine equal GroundTruth.lookup of
 every valid k-mer of every read -- two references, neither of them the library's GPU path. The sums have two references of their own,
 both numpy over the oracle's results: values[ids].sum() per read, and the kernel's formula restated -- per run record P[hi] - P[lo] over
-P = cumsum(values) --, asserted equal, over values under which a slip by one id at either end of any run changes the sum. Then every
-form through the host and the device entry point, uncut, cut into segments of 1, 7 and 64 k-mers, and uncut again; all comparisons
-exact. Prints one JSON line; any mismatch is an assertion error.
+P = cumsum(values) --, asserted equal, over values under which a slip by one id at either end of any run changes the sum. The three
+forms that came last consume a hit's string id in ways of their own -- an index into the labels; word 2 of a record stored at the read's
+own index; under segments, a record whose place the joined[] bytes decide -- and have two references each as well
+(tests/gpu_forms_later.py): the best run as the argmax with the tie rule over the oracle's run records and over the run rule applied to
+its per-k-mer results; the classes, for 3 and 65 classes under string id % C and under random labels a third of which are no class,
+from the per-k-mer ids through id -> string -> label and from the run records; the run records over segments are the uncut records. The
+reads hold what makes a wrong kernel show: ties for the longest run, a longest run that is not the first or is backward, reads of two
+strings of different classes, k-mers of a masked label, runs that span three whole segments and more. Then every form through the host
+and the device entry point, uncut, cut into segments of 1, 7 and 64 k-mers, and uncut again; all comparisons exact. Prints one JSON
+line; any mismatch is an assertion error.
 
     python tests/gpu_forms_worker.py <k> <m> <key_length or 0> <layer: table|directory> <table_keys binary> <scratch dir> [--cpu-only]"""
 from __future__ import annotations
@@ -169,6 +177,29 @@ def odd_sequences(k, m, key_length):
     return seqs
 
 
+def two_string_reads(seqs, k, seed):
+    """reads for the forms that tell a read's strings and its runs apart (the classes, the best run): pieces of two strings whose ids differ
+    modulo 3 and modulo 65 back to back, the first run the longer (k + 40 bases, then k + 30) or the second (k + 10, then k + 60), every other
+    one on the other strand; and a string's prefix with one substitution at base k + 5: a run of 6 k-mers, k k-mers that are nowhere, the rest"""
+    rng = np.random.default_rng(seed)
+    usable = [i for i, s in enumerate(seqs) if len(s) >= k + 60]
+    reads = []
+    for j in range(16):
+        while True:
+            a, b = (int(i) for i in rng.choice(usable, 2, replace=False))
+            if (a - b) % 3 and (a - b) % 65:
+                break
+        first, second = ((k + 40, k + 30), (k + 10, k + 60))[j % 2]
+        r = seqs[a][:first] + seqs[b][-second:]
+        reads.append(revcomp(r) if j % 4 >= 2 else r)
+    lengthy = [s for s in seqs if len(s) >= 3 * k + 30]
+    for j in range(4):
+        r = list(lengthy[int(rng.integers(0, len(lengthy)))][:3 * k + 30])
+        r[k + 5] = "ACGT"[("ACGT".index(r[k + 5]) + 1) % 4]
+        reads.append(revcomp("".join(r)) if j % 2 else "".join(r))
+    return reads
+
+
 class Point:
     """one dictionary with its reads and everything the references say about them (on the CPU)"""
 
@@ -203,7 +234,7 @@ def make_inputs(k, m, key_length, canonical, exe, scratch):
     reads = make_reads(seqs, k) + synthetic_reads(seqs, k, 160, seed=k + m, read_len=3 * k) + own + pt.jumps
     for s in seqs:
         reads += [s, revcomp(s)]
-    pt.reads = reads
+    pt.reads = reads + two_string_reads(seqs, k, 9200 * k + m)  # (behind the others: what the references say of those stays)
     pt.long_reads = [long_read_of(seqs, False), long_read_of(seqs, True)]
     assert all(len(r) > (1 << 16) for r in pt.long_reads)
     hot = next(s for s in seqs if len(s) >= 800)[40:40 + k + 100]
@@ -344,6 +375,7 @@ def gate(pt):
     """on the CPU, before any device call: every kind of read, run and seam is there, and the oracle's ids are the input's"""
     from gpu_cover_worker import bitmap_of
     from gpu_depth_worker import depth_of, runs_of
+    from gpu_forms_later import references as later_references
     from gpu_segments_worker import kinds_of
 
     case, k, reads = pt.case, pt.k, pt.reads
@@ -405,16 +437,18 @@ def gate(pt):
     assert backward_runs.any() and not backward_runs.all()
     pt.batch = reads[:20] + [pt.long_reads[0], ""] + reads[20:40] + [pt.long_reads[1]]
     batch_ids = pt.ids[:20] + [pt.long_ids[0], pt.ids[0][:0]] + pt.ids[20:40] + [pt.long_ids[1]]
-    pt.want_batch_sums, _ = sums_references(pt, pt.sums_cases, pt.batch, batch_ids, case.oracle)
-    pt.want_hot_sums, (_, hot_runs) = sums_references(pt, pt.sums_cases[:1], pt.repeated[:1], hids, case.oracle)
+    pt.want_batch_sums, (pt.batch_offsets, pt.batch_runs) = sums_references(pt, pt.sums_cases, pt.batch, batch_ids, case.oracle)
+    pt.want_hot_sums, (hot_offsets, hot_runs) = sums_references(pt, pt.sums_cases[:1], pt.repeated[:1], hids, case.oracle)
     assert hot_runs.size == 1
+    # the classes, the best run and the run records over segments: two references each, and what the reads hold for them
+    later = later_references(pt, case.oracle, string_of_ids(case.gt, k)[0], batch_ids, hids, (hot_offsets, hot_runs), SEGMENT_SIZES)
     sums = {"positive_kmers": int(pt.want_sums["random"]["positive_kmers"].sum(dtype=np.uint64)), "largest_row_sum": int(pt.want_sums["random"]["sum"].max()),
             "largest_row_sum_of_the_long_reads": int(pt.want_batch_sums["all ones"]["sum"].max()), "runs": int(pt.want_runs.size),
             "runs_without_an_id_below": no_id_below, "runs_without_an_id_above": no_id_above}
     assert sums["positive_kmers"] == int(pt.want_totals[1]) > 0 and sums["largest_row_sum"] > (1 << 32)
     return {"kmers": n_kmers, "sums": sums, "strings": len(pt.sequences), "reads": len(reads), "read_kmers": int(pt.want_totals[0]), "runs": int(pt.want_totals[4]),
             "seams_joined": {str(S): found[f"seam_in_forward_run@{S}"] + found[f"seam_in_backward_run@{S}"] for S in SEGMENT_SIZES}, "kinds": kinds,
-            "floors": pt.floors}
+            "floors": pt.floors, **later}
 
 
 # ---- the device --------------------------------------------------------------------------------------------------------------------------
@@ -449,6 +483,7 @@ def check_flavour(pt, key_length, layer):
     import sshash_amd
     from gpu_cover_worker import bitmap_of, device_string_counts
     from gpu_depth_worker import depth_of, device_depth, device_string_sums
+    from gpu_forms_later import DEFAULT_S, check_long, check_segmented, check_uncut
     from gpu_per_read_worker import oracle_rows
     from gpu_runs_worker import check_both
     from gpu_segments_worker import accumulated, everything, launches, same
@@ -469,7 +504,7 @@ def check_flavour(pt, key_length, layer):
     cases = pt.sums_cases
     sums_host, sums_device = sums_wanted(pt.want_sums, cases, totals)
 
-    # ---- uncut: the seven forms, host and device (rows into a prefilled array between guard rows) ----
+    # ---- uncut: the first seven forms, host and device (rows into a prefilled array between guard rows) ----
     assert d.read_segments()["kmers"] == sshash_amd.SEGMENTS_OFF, "a new dictionary does not segment"
     d.set_read_segments(sshash_amd.SEGMENTS_OFF, device_calls=True)
     assert _as_dict(d.streaming_query(reads)) == case.oracle.streaming_query(reads), f"{what}: streaming_query"
@@ -534,6 +569,8 @@ def check_flavour(pt, key_length, layer):
     long_sums_host, long_sums_device = sums_wanted(pt.want_batch_sums, cases, brows.sum(0))
     same(sums_everything(d, batch, cases, prefixes, False), long_sums_host, f"{what}: sums, the long reads uncut, host calls (the per-k-mer route)")
     same(sums_everything(d, batch, cases, prefixes, True), long_sums_device, f"{what}: sums, the long reads uncut, device calls (one lane each)")
+    # ---- the classes, the best run, and the run records of the long reads: uncut ----
+    check_uncut(d, pt, totals, brows.sum(0), f"{what}: uncut", REPEATS)
     assert launches(d) == 0, "SEGMENTS_OFF launched over segments"
 
     # ---- segments of S k-mers: byte for byte the uncut answers, also into arrays that hold values ----
@@ -545,7 +582,7 @@ def check_flavour(pt, key_length, layer):
     acc_host = {"cover": cover | before_cover, "depth": depth + before_depth}
     acc_device = dict(cover=acc_host["cover"], depth=depth + np.cumsum(before_depth, dtype=np.uint32), totals=totals + start, rows_report=totals + start,
                       cover_report=totals + start, depth_report=totals + start)  # (the device call adds to DELTAS: what they held is scanned with them)
-    segmented = {}
+    segmented, of_runs, of_classes = {}, {}, {}
     for S in SEGMENT_SIZES:
         d.set_read_segments(S, device_calls=True)
         assert d.read_segments()["kmers"] == S
@@ -563,11 +600,13 @@ def check_flavour(pt, key_length, layer):
         at = launches(d)
         same(sums_everything(d, reads, cases, prefixes, True), sums_device, f"{what}: sums, S = {S}, device calls")
         assert launches(d) == at + 2 * len(cases), f"{what}: S = {S}: every device call of the sums launches over segments once"
+        of_runs[str(S)], of_classes[str(S)] = check_segmented(d, pt, S, totals, what)
         segmented[str(S)] = launches(d)
     # ---- the long reads at the default S ----
     d.set_read_segments(device_calls=True)
     S = d.read_segments()["kmers"]
     assert 1 < S < (1 << 14), S
+    assert S == DEFAULT_S, "the gate counted the runs over three segments of the long reads at another S"
     at = launches(d)
     same(everything(d, batch, False), long_host, f"{what}: the long reads at the default S, host calls")
     same(everything(d, batch, True), long_device, f"{what}: the long reads at the default S, device calls")
@@ -578,6 +617,7 @@ def check_flavour(pt, key_length, layer):
     at = launches(d)
     same(sums_everything(d, batch, cases, prefixes, True), long_sums_device, f"{what}: sums, the long reads at the default S, device calls")
     assert launches(d) == at + 2 * len(cases)
+    check_long(d, pt, brows.sum(0), f"{what}: the long reads at the default S")
     # ---- and off again ----
     d.set_read_segments(sshash_amd.SEGMENTS_OFF, device_calls=True)
     at = launches(d)
@@ -585,11 +625,12 @@ def check_flavour(pt, key_length, layer):
     same(everything(d, reads, True), want_device, f"{what}: SEGMENTS_OFF again, device calls")
     same(sums_everything(d, reads, cases, prefixes, False), sums_host, f"{what}: sums, SEGMENTS_OFF again, host calls")
     same(sums_everything(d, reads, cases, prefixes, True), sums_device, f"{what}: sums, SEGMENTS_OFF again, device calls")
+    check_uncut(d, pt, totals, brows.sum(0), f"{what}: SEGMENTS_OFF again", REPEATS, first=False)
     assert launches(d) == at, "SEGMENTS_OFF launched over segments"
     del prefixes
     d.close()
     return {"sk_slots": st["sk_slots"], "directory_sectors": st["directory_sectors"], "sk_key_length": st["sk_key_length"], "sk_heavy_kmers": st["sk_heavy_kmers"],
-            "default_S": S, "segmented_launches": segmented}
+            "default_S": S, "segmented_launches": segmented, "segmented_launches_of_run_records": of_runs, "segmented_launches_of_classes": of_classes}
 
 
 def main():

@@ -3,12 +3,21 @@ tests/gpu_forms_worker.py runs ahead of its first device call, for every row of 
 of read and of run (forward, backward, of one k-mer, of 64 and more, from id 0, to the last id, reads shorter than k, empty, without a
 hit, with N's), seams of every kind fall where segments of 1, 2, 7 and 64 k-mers are cut, the ids of the oracle's restated state machine
 equal GroundTruth.lookup of every valid k-mer of every read (the long reads above 2^16 bases among them), the repeated read is one run,
-and at an even m the reads walk over at least FLOOR tying k-mers of the dictionary. The sweep holds all seven forms of the run kernel:
-for the sums the gate computes, per read, values[ids].sum() and the number of ids over those oracle ids, and once more the kernel's
+and at an even m the reads walk over at least FLOOR tying k-mers of the dictionary. The sweep holds all ten forms of the run kernel.
+For the sums the gate computes, per read, values[ids].sum() and the number of ids over those oracle ids, and once more the kernel's
 own formula over the oracle's run records -- P[hi] - P[lo] over P = numpy.cumsum(values) in 64 bits, [lo, hi) from the record's kmer_id,
 its length and its backward bit -- and asserts the two equal, for full-range random values, for whether they reach 2^31, and for all
 0xFFFFFFFF; under the random values a run moved by one id, at either end or both, sums to something else, except where there is no
-such id: runs from id 0 and runs to the last id, of which there are some at every point."""
+such id: runs from id 0 and runs to the last id, of which there are some at every point. For the classes, the best run and the run
+records over segments (tests/gpu_forms_later.py) the gate computes two references each and asserts them equal: the best run as the
+argmax with the tie rule (the largest num_kmers & 0x7FFFFFFF, the first of equals, 32 zero bytes without a hit) over the oracle's run
+records and over the run rule applied to its per-k-mer results; the rows of 3 and of 65 classes, under string id % C and under random
+labels a third of which are no class, from the per-k-mer ids through id -> string -> label and from the run records,
+rows[read, labels[string_id]] += length; the run records over segments are the uncut records. At every point the reads hold reads with
+two and more runs of the maximal length (the four jump reads by construction), reads whose best run is not their first, is backward,
+reads without a hit, reads with two and more non-zero columns, k-mers that a masked label drops, rows whose columns sum to the read's
+positive k-mers where no label is masked, and runs that span three whole segments of 1, 7 and 64 k-mers and more -- of 256 in the reads
+above 2^16 bases."""
 from __future__ import annotations
 
 import pytest
@@ -41,6 +50,15 @@ def test_gate(k, m, key_length, layer, canonical, table_keys_exe, tmp_path):
     assert sums["runs"] == got["runs"] and sums["runs_without_an_id_below"] > 0 and sums["runs_without_an_id_above"] > 0
     assert sums["positive_kmers"] > 0 and sums["largest_row_sum"] > (1 << 32) and sums["largest_row_sum_of_the_long_reads"] > 20000 * 0xFFFFFFFF
     assert set(pt.want_sums) == set(pt.want_batch_sums) == {"random", "at least 2^31", "all ones"}
+    # the three forms that came after the sweep of seven: what a wrong kernel needs to show is in the reads, at every point
+    best, classes, spanning = got["best_run"], got["classes"], got["runs_over_three_segments"]
+    print(f"best run {best}, classes {classes}, runs over three segments and more {spanning}")
+    assert best["ties_for_the_longest"] >= 4 and best["longest_is_not_the_first"] > 0 and best["longest_is_backward"] > 0 and best["reads_without_a_hit"] > 0
+    assert best["longest_of_the_long_reads"] > 600
+    assert set(classes) == {f"{name} / {C}" for name in ("reads_with_two_columns", "kmers_of_a_masked_label") for C in (3, 65)} and all(v > 0 for v in classes.values())
+    assert set(spanning) == {str(S) for S in SEGMENT_SIZES} | {"long reads, default S"} and all(v > 0 for v in spanning.values())
+    assert pt.want_best.size == len(pt.reads) and pt.want_batch_best.size == len(pt.batch) == 43
+    assert set(pt.want_classes) == set(pt.want_batch_classes) == {"mod / 3", "random / 3", "mod / 65", "random / 65"}
     if m % 2 == 0:
         assert all(c["read_kmers_found"] >= FLOOR for c in got["floors"].values()), got["floors"]
     else:
