@@ -215,19 +215,21 @@ def long_read_of(sequences, with_n):
     return ("N" if with_n else "").join(parts)
 
 
-def make_inputs(k, m, key_length, canonical, exe, scratch):
-    """-> Point: the dictionary (conftest.Case), the reads, the long reads and the repeated read"""
+def make_inputs(k, m, key_length, canonical, exe, scratch, extend=None):
+    """-> Point: the dictionary (conftest.Case), the reads, the long reads and the repeated read. `extend`: strings -> the strings with
+    more behind them (tests/gpu_walks_worker.py; None: the sweep's dictionary)"""
     from conftest import Case
     from gpu_segments_worker import make_reads
 
     pt = Point()
     pt.k, pt.m, pt.canonical, pt.W, pt.floors = k, m, canonical, 1 if k <= 31 else 2, None
     if m % 2 == 0:
-        even = make_point(k, m, canonical, exe, scratch, extend=lambda seqs: with_long_strings(seqs, k, 9100 * k + m), key_length=key_length or None)
+        even = make_point(k, m, canonical, exe, scratch, key_length=key_length or None,
+                          extend=lambda seqs: (extend or list)(with_long_strings(seqs, k, 9100 * k + m)))
         pt.floors = assert_floors(even)  # at least FLOOR tying k-mers that the reads hold and the dictionary contains, of every kind
         pt.case, own = even.case, even.reads
     else:
-        seqs = odd_sequences(k, m, key_length)
+        seqs = (extend or list)(odd_sequences(k, m, key_length))
         pt.case, own = Case(f"forms_k{k}_m{m}_{int(canonical)}", seqs, k, m, canonical, scratch), []
     seqs = pt.sequences = pt.case.sequences
     pt.jumps = jump_reads(k, 9100 * k + m)
@@ -479,7 +481,10 @@ def sums_wanted(want, cases, totals):
     return host, device
 
 
-def check_flavour(pt, key_length, layer):
+def check_flavour(pt, key_length, layer, upload=None, replica=None, then=None):
+    """`upload`: dictionary -> the dictionary on device 0, where that is not a plain to_device(0); `replica`: (stats, what) -> None, what
+    device_stats() has to show beyond the layer's own, asserted before the first streaming call; `then`: (d, what) -> None, more calls
+    on the same replica behind the sweep's own (tests/gpu_walks_worker.py passes all three; the sweep none)"""
     import sshash_amd
     from gpu_cover_worker import bitmap_of, device_string_counts
     from gpu_depth_worker import depth_of, device_depth, device_string_sums
@@ -492,10 +497,12 @@ def check_flavour(pt, key_length, layer):
 
     case, k, m, reads = pt.case, pt.k, pt.m, pt.reads
     what = f"{layer} k={k} m={m} key={key_length} {'canonical' if pt.canonical else 'regular'}"
-    d = case.dict.to_device(0)
+    d = case.dict.to_device(0) if upload is None else upload(case.dict)
     st = d.device_stats(0)
     assert LAYERS[layer][1](st), f"{what}: the replica is not the {layer} layer: {st}"
     assert st["sk_key_length"] == (key_length or key_length_of(k, m)), (what, st["sk_key_length"])
+    if replica is not None:
+        replica(st, what)
     n_kmers = case.gt.num_kmers
     assert d.num_kmers() == n_kmers and d.cover_words() == pt.cover_words
     totals, rows, cover, depth = pt.want_totals, pt.want_rows, pt.want_cover, pt.want_depth
@@ -628,6 +635,8 @@ def check_flavour(pt, key_length, layer):
     check_uncut(d, pt, totals, brows.sum(0), f"{what}: SEGMENTS_OFF again", REPEATS, first=False)
     assert launches(d) == at, "SEGMENTS_OFF launched over segments"
     del prefixes
+    if then is not None:
+        then(d, what)
     d.close()
     return {"sk_slots": st["sk_slots"], "directory_sectors": st["directory_sectors"], "sk_key_length": st["sk_key_length"], "sk_heavy_kmers": st["sk_heavy_kmers"],
             "default_S": S, "segmented_launches": segmented, "segmented_launches_of_run_records": of_runs, "segmented_launches_of_classes": of_classes}
