@@ -143,6 +143,14 @@ sshash_status sshash_device_stats(const sshash_dict* d, int device, uint64_t out
  *         in each of these bins, [18] super-k-mers in all, [19] slots asked for (inline occurrences + markers + k-mers of heavy
  *         keys), [20..31] zero }; all zero when the replica has no table. */
 sshash_status sshash_device_table_histogram(const sshash_dict* d, int device, uint64_t out[32]);
+/* A read-only copy of the replica's super-k-mer table as it lies in HBM, for tests and diagnosis -- the whole
+ * table crosses to the host, so it is sized for small replicas:
+ * info = { [0] bytes of the table, [1] buckets of the keys' region, [2] buckets of the k-mers' region, [3] bytes per bucket of the
+ *          keys' region (64, or 128 at k > 31), [4] bytes per bucket of the k-mers' region (64), [5] length of the table's keys,
+ *          [6] table shards, [7] shard id }; all zero (and nothing copied) when the replica has no table.
+ * out == NULL: info only. Otherwise the device is synchronised and info[0] bytes are copied to `out`; SSHASH_ERR_ARGUMENT if
+ * capacity_bytes < info[0]. The keys' region comes first, the k-mers' region behind it. */
+sshash_status sshash_device_table_export(const sshash_dict* d, int device, uint64_t info[8], void* out, uint64_t capacity_bytes);
 
 /* ---- dictionary::lookup(Kmer, bool) / lookup(char const*, bool): include/dictionary.hpp:41-42,
  *      src/dictionary.cpp:58-78. Batched. ------------------------------------------------------

@@ -143,6 +143,7 @@ _SIGNATURES = {
     "sshash_device_bytes": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
     "sshash_device_stats": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64 * 16)]),
     "sshash_device_table_histogram": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64 * 32)]),
+    "sshash_device_table_export": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64 * 8), C.c_void_p, C.c_uint64]),
     "sshash_sharded_lookup_device": (C.c_int, [_P, C.c_int, C.c_uint32, C.c_int, _P, C.c_uint64, C.c_int, _P, C.POINTER(_Exchange), _P]),
     "sshash_sharded_lookup_rccl": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint64, C.c_int, _P, _P]),
     "sshash_streaming_lookup_device": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, C.c_uint64, C.POINTER(_Results), _P, _P]),
@@ -482,6 +483,17 @@ class Dictionary:
         bins = ["1", "2", "3", "4", "5-8", "9-16", "17-64", "65-1024", ">1024"]
         return {"keys_by_occurrences": dict(zip(bins, v[0:9])), "super_kmers_by_occurrences_of_their_key": dict(zip(bins, v[9:18])),
                 "super_kmers": v[18], "slots_asked_for": v[19]}
+
+    def device_table(self, device: int = 0):
+        """-> (info, words): the replica's super-k-mer table copied to the host as uint32 words, the keys' region first
+        (sshash_device_table_export). A test and diagnosis call, sized for small replicas."""
+        names = ("bytes", "key_buckets", "kmer_buckets", "key_bucket_bytes", "kmer_bucket_bytes", "key_length", "table_shards", "table_shard_id")
+        raw = (C.c_uint64 * 8)()
+        _check(_load().sshash_device_table_export(self._h, int(device), C.byref(raw), None, 0))
+        words = np.zeros(int(raw[0]) // 4, dtype=np.uint32)
+        if words.size:
+            _check(_load().sshash_device_table_export(self._h, int(device), C.byref(raw), words.ctypes.data_as(C.c_void_p), words.nbytes))
+        return dict(zip(names, (int(x) for x in raw))), words
 
     def _as_batch(self, kmers: KmerBatch):
         """-> (is_ascii, contiguous ndarray, n)"""

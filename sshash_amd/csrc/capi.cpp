@@ -352,6 +352,11 @@ sshash_status sshash_device_table_histogram(const sshash_dict* d, int device, ui
     return guarded([&] { d->eng->device_table_histogram(device, out); });
 }
 
+sshash_status sshash_device_table_export(const sshash_dict* d, int device, uint64_t info[8], void* out, uint64_t capacity_bytes) {
+    if (!d || !info) return fail(SSHASH_ERR_ARGUMENT, "null argument");
+    return guarded([&] { d->eng->device_table_export(device, info, out, capacity_bytes); });
+}
+
 sshash_status sshash_lookup_packed_device(const sshash_dict* d, int device, const uint64_t* kmers, uint64_t n,
                                           int check_rc, const sshash_results* out, void* hip_stream) {
     if (!d || !out || (!kmers && n)) return fail(SSHASH_ERR_ARGUMENT, "null argument");

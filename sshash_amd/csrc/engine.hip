@@ -202,6 +202,26 @@ void engine::device_table_histogram(int device, uint64_t out[32]) const {
     for (int i = 0; i < 32; ++i) out[i] = i < 20 && r->view.sk.enabled ? r->sk_histogram[i] : 0;
 }
 
+void engine::device_table_export(int device, uint64_t info[8], void* out, uint64_t capacity_bytes) const {
+    device_replica const* r = replica(device);
+    for (int i = 0; i < 8; ++i) info[i] = 0;
+    sk_view const& sk = r->view.sk;
+    if (!sk.enabled) return;  // (as the histogram: a replica without a table has nothing to show)
+    info[0] = r->sk_bytes;
+    info[1] = sk.num_buckets;
+    info[2] = sk.kmer_buckets;
+    info[3] = SK_BUCKET_SLOTS * (r->view.k > 31 ? 64u : 32u);
+    info[4] = 64;
+    info[5] = sk.m;
+    info[6] = sk.num_shards;
+    info[7] = sk.shard_id;
+    if (!out) return;
+    if (capacity_bytes < r->sk_bytes) throw error(error_kind::argument, "sshash_device_table_export: the buffer is smaller than the table (info[0])");
+    device_guard guard(device);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out, sk.slots, r->sk_bytes, hipMemcpyDeviceToHost));
+}
+
 device_replica const* engine::replica(int device) const {
     std::shared_lock<std::shared_mutex> lock(m_replicas_mutex);
     for (auto const& r : m_replicas)

@@ -153,6 +153,9 @@ public:
         super-k-mer table slots (0 = disabled), its keys, its inline keys, its keys left to the complete path} */
     void device_stats(int device, uint64_t out[16]) const;
     void device_table_histogram(int device, uint64_t out[32]) const;
+    /* the replica's super-k-mer table as it lies in HBM, for tests and diagnosis: info = {bytes, buckets of the keys' region, of the
+       k-mers' region, bytes per bucket of either, key length, table shards, shard id}; out == nullptr: info only */
+    void device_table_export(int device, uint64_t info[8], void* out, uint64_t capacity_bytes) const;
 
     /* Device-pointer entry points: queries and outputs already live in the HBM of `device`;
        the launch is asynchronous on `stream` (a hipStream_t, may be null = default stream).
